@@ -2,7 +2,7 @@
 """PDHG inner-loop benchmark (BASELINE.json metric: PDHG iterations/s and
 achieved GB/s of the CSR SpMV vs the HBM roofline).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one ``take_step`` of the adaptive policy (pdhg.jl:653-731): one
 accepted PDHG iteration including any rejected trials, from the zero start,
@@ -14,15 +14,25 @@ all-gather over xGMI) is issued by the library itself (csrc/dist.hpp) --
 torch.distributed (gloo) is used here only for the harness: handing out the
 communicator id, the barriers around the timed region and the max over ranks.
 
-Prints ONE compact JSON line (<= 4 KB: the contract's keys, `roofline`,
-`cpu_baseline`, one short row per other config) as the LAST line of rank 0's
-stdout; the whole record -- `kernels`, `scaling_model`, `ceiling`,
+A plain run does only what the headline figure needs: it generates the LP,
+creates the engine, runs W untimed and K timed steps and prints ONE compact JSON
+line (the contract's keys: `value`, `ms_per_step`, ...) as the LAST line of
+rank 0's stdout.  --dump-outputs DIR then also writes what the last timed step
+left in the solver state (the current and averaged iterates, seeded samples of
+at most DUMP_SAMPLE entries each, and the state's scalars) as DIR/<name>.npy.
+
+--full adds everything else the benchmark measures: the steady rate, the
+per-kernel HIP-event profile and the roofline (`roofline`, with the
+rocprofv3 child runs of tools/selfprof.py), the rocSPARSE comparator, the CPU
+baselines (`cpu_baseline`), the traced trial timeline and, at N=1, the same
+measurement for BASELINE configs[2] (PageRank LP, 1M nodes) and configs[3]
+(L1-SVM LP on rcv1-shaped data) under "other_configs" unless
+--no-other-configs is given; --workload picks one of them as the headline.
+The line then stays <= 4 KB (`roofline`, `cpu_baseline`, one short row per
+other config); the whole record -- `kernels`, `scaling_model`, `ceiling`,
 `self_profile`, the CPU comparator's variants, `trial_timeline`, the full
 `other_configs` legs -- goes to bench_details.json next to this script and to
-stderr.  At N=1 the record also carries, under "other_configs", the same
-measurement for BASELINE configs[2] (PageRank LP, 1M nodes) and configs[3]
-(L1-SVM LP on rcv1-shaped data) unless --no-other-configs is given;
---workload picks one of them as the headline.
+stderr.
 """
 import argparse
 import json
@@ -88,6 +98,13 @@ def parse():
     ap.add_argument("--n", "--cols", dest="n", type=int, default=10_000_000)
     ap.add_argument("--nnz-per-row", type=int, default=10)
     ap.add_argument("--seed", type=int, default=12345)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure (steady rate, kernel profile and roofline, "
+                         "rocprofv3 child runs, rocSPARSE and CPU comparators, trial timeline, other configs) and write "
+                         "bench_details.json; a plain run times the K steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left in the solver state as DIR/<name>.npy "
+                         "(float64; a vector longer than 2^20 entries as a fixed seeded sample of 2^20)")
     ap.add_argument("--workload", choices=["random", "pagerank", "l1svm"], default="random",
                     help="random: BASELINE configs[4] (default); pagerank: configs[2]; l1svm: configs[3]")
     ap.add_argument("--pagerank-nodes", type=int, default=1_000_000)
@@ -153,6 +170,38 @@ def initial_scalars(problem):
     return step0, (cn / bn if cn > 0 and bn > 0 else 1.0)                      # saddle_point.jl:1049
 
 
+DUMP_SAMPLE = 1 << 20       # entries --dump-outputs keeps of one vector: five float64 vectors, 40 MiB at most
+DUMP_SEED = 7
+
+
+def sample_index(length):
+    """The indices --dump-outputs keeps of a vector of `length` entries: all of them up to DUMP_SAMPLE, else DUMP_SAMPLE
+    of them drawn without replacement by a generator seeded with DUMP_SEED + length (the same on every run), sorted."""
+    import numpy as np
+    if length <= DUMP_SAMPLE:
+        return np.arange(length)
+    return np.sort(np.random.default_rng(DUMP_SEED + length).choice(length, DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(dump_dir, eng, state, write=True):
+    """What a caller of take_steps holds after the last timed step: the current iterates and A'y, the weighted averages
+    (each through sample_index) and the solver state's scalars, as float64 DIR/<name>.npy.  Every rank reads (the
+    getters of a multi-rank engine may synchronise the ranks); `write`: only rank 0 writes."""
+    import numpy as np
+    x, y = eng.get_current()
+    arrays = {"primal": x, "dual": y, "dual_product": eng.get_dual_product()}
+    arrays["primal_average"], arrays["dual_average"] = eng.get_average()
+    arrays = {k: np.ascontiguousarray(v[sample_index(len(v))], dtype=np.float64) for k, v in arrays.items()}
+    # step_size, primal_weight, total_number_iterations, cumulative_kkt_passes, numerical_error
+    arrays["scalars"] = np.array([state.step_size, state.primal_weight, state.total_number_iterations,
+                                  state.cumulative_kkt_passes, float(state.numerical_error)], dtype=np.float64)
+    if not write:
+        return
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), v)
+
+
 def shard_for_rank(args, workload, ctx):
     """Rank 0 generates the LP, computes the row partition and writes one file per rank;
     every rank then loads only its own rows.  Returns (shard dict for
@@ -202,9 +251,9 @@ def shard_for_rank(args, workload, ctx):
     return shard, meta
 
 
-def measure(args, workload, ctx, steps, warmup, cpu_seconds, with_socket=True):
-    """Build the engine for `workload`, time `steps` adaptive take_steps, profile
-    the kernels with HIP events, time the CPU restatement.  Returns a dict."""
+def measure(args, workload, ctx, steps, warmup, cpu_seconds, with_socket=True, dump_dir=None):
+    """Build the engine for `workload`, time `steps` adaptive take_steps (`dump_dir`: then write their outputs there);
+    with --full also profile the kernels with HIP events and time the CPU restatement.  Returns a dict."""
     import numpy as np
     import torch
     from firstorderlp_jl_amd import _lib
@@ -276,6 +325,17 @@ def measure(args, workload, ctx, steps, warmup, cpu_seconds, with_socket=True):
         elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / steps
     value = steps / elapsed
+    if dump_dir is not None:
+        dump_outputs(dump_dir, eng, state, write=rank == 0)
+    config = {"id": {"random": "configs[4]", "pagerank": "configs[2]", "l1svm": "configs[3]"}[workload],
+              "workload": wl + ", adaptive step, zero start, no restarts/rescaling",
+              "m": m, "n": n, "nnz": nnz, "parallelism": parallelism}
+    if not args.full:
+        # a plain run: the headline figure and nothing that costs a run of its own (everything below is --full)
+        eng.close()
+        return {"value": round(value, 3), "unit": "iterations/s", "steps": steps, "warmup": warmup,
+                "ms_per_step": round(ms_per_step, 5), "config": config, "trials_per_step": round(trials / steps, 4),
+                "setup_sec": {"generate": round(t_gen, 1), "create_upload": round(t_create, 1)}}
     # the contract times EXACTLY the K steps asked for; when K is small (the driver's 20: 32 ms on config S) the line
     # also carries the rate over 200 further steps, timed the same way
     steady = None
@@ -531,9 +591,7 @@ def measure(args, workload, ctx, steps, warmup, cpu_seconds, with_socket=True):
     out = {
         "value": round(value, 3), "unit": "iterations/s", "steps": steps, "warmup": warmup,
         "ms_per_step": round(ms_per_step, 5),
-        "config": {"id": {"random": "configs[4]", "pagerank": "configs[2]", "l1svm": "configs[3]"}[workload],
-                   "workload": wl + ", adaptive step, zero start, no restarts/rescaling",
-                   "m": m, "n": n, "nnz": nnz, "parallelism": parallelism},
+        "config": config,
         "trials_per_step": round(trials / steps, 4),
         "steady_rate": steady,
         "whole_iteration_GBps": round(b_iter * (trials / steps) / (ms_per_step * 1e-3) / 1e9, 1),
@@ -829,6 +887,8 @@ def multi_gpu_failure(args, world, rank, exc, real_stdout):
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.dist_overlap:
         os.environ["PDHG_DIST_AG_OVERLAP"] = "1"
         os.environ["PDHG_DIST_OVERLAP"] = "1"
@@ -892,13 +952,13 @@ def main():
 
     cpu_s = 0.0 if args.no_cpu_baseline else args.cpu_baseline_seconds
     try:
-        head = measure(args, args.workload, ctx, args.steps, args.warmup, cpu_s)
+        head = measure(args, args.workload, ctx, args.steps, args.warmup, cpu_s, dump_dir=args.dump_outputs)
     except Exception as exc:
         if dist is None:
             raise
         multi_gpu_failure(args, world, rank, exc, real_stdout)
     others = []
-    if dist is None and not args.no_other_configs and args.workload == "random" and args.shards == 0:
+    if args.full and dist is None and not args.no_other_configs and args.workload == "random" and args.shards == 0:
         for wl in ("pagerank", "l1svm"):
             try:
                 # an iteration of these LPs takes 0.05-0.2 ms: 2000 timed steps after 300 untimed ones (each leg states
@@ -911,7 +971,8 @@ def main():
                 others.append({"config": {"workload": wl}, "error": repr(exc)})
 
     # ---- the roofline's rocprofv3 figures from THIS run: short child runs of this script under rocprofv3
-    # (tools/selfprof.py); the committed files stay as the fallback, marked as such
+    # (tools/selfprof.py); the committed files stay as the fallback, marked as such.  (A plain run's legs carry no
+    # `_selfprof`: nothing happens here without --full.)
     t_prof0 = time.time()
     for leg in [head] + others:
         sp = leg.pop("_selfprof", None)
@@ -965,7 +1026,7 @@ def main():
     if rank == 0:
         # the compact line is the LAST thing this script writes (the process then exits NORMALLY: rocprofv3 writes its
         # databases from exit handlers, so the child runs of tools/selfprof.py must not be cut short)
-        emit(out, real_stdout, details=not args.no_details, full_line=args.full_line)
+        emit(out, real_stdout, details=args.full and not args.no_details, full_line=args.full_line)
 
 
 if __name__ == "__main__":
