@@ -10,3 +10,4 @@ from .quadratic_programming import (  # noqa: F401
     is_linear_programming_problem, equality_range, inequality_range)
 from .engine import HipPdhgEngine  # noqa: F401
 from . import _lib  # noqa: F401
+from .batch import HipPdhgBatch, optimize_batch  # noqa: F401

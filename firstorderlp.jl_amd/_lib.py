@@ -37,6 +37,8 @@ EXPORTS = [
     "pdhg_point_sumsq", "pdhg_rescale", "pdhg_get_problem_vectors", "pdhg_matrix_max_abs",
     "pdhg_partition_rows", "pdhg_create_dist_rows", "pdhg_rccl_info", "pdhg_host_issue_stats",
     "pdhg_measure_launch_overhead", "pdhg_selftest_wave_sums", "pdhg_layout_checksums",
+    "pdhg_create_batch", "pdhg_batch_member", "pdhg_batch_trial_step", "pdhg_batch_accept",
+    "pdhg_batch_take_steps_adaptive",
 ]
 
 ABI_VERSION = 11
@@ -207,6 +209,18 @@ def lib():
     L.pdhg_kernel_algorithmic_bytes.argtypes = [_vp, i32]
     L.pdhg_layout_describe.restype = i32
     L.pdhg_layout_describe.argtypes = [_vp, ctypes.c_char_p, i32]
+    _int_p = ctypes.POINTER(i32)
+    L.pdhg_create_batch.restype = i32
+    L.pdhg_create_batch.argtypes = [ctypes.POINTER(_vp), i32, i64, i64, i64, _ip, _ip, _dp, i32, _dp, _dp, _dp, _dp, i64,
+                                    i32, _vp]
+    L.pdhg_batch_member.restype = i32
+    L.pdhg_batch_member.argtypes = [_vp, i32, ctypes.POINTER(_vp)]
+    L.pdhg_batch_trial_step.restype = i32
+    L.pdhg_batch_trial_step.argtypes = [_vp, _dp, _dp, d, _int_p, _dp]
+    L.pdhg_batch_accept.restype = i32
+    L.pdhg_batch_accept.argtypes = [_vp, _int_p, _dp]
+    L.pdhg_batch_take_steps_adaptive.restype = i32
+    L.pdhg_batch_take_steps_adaptive.argtypes = [_vp, i64, d, d, _dp, _dp, _ip, _dp, _int_p, _int_p, _ip]
     L.pdhg_kernel_name.restype = ctypes.c_char_p
     L.pdhg_kernel_name.argtypes = [_vp, i32]
     L.pdhg_layout_info.restype = i32

@@ -1,0 +1,445 @@
+"""Batched PDHG solves of LPs that share one constraint matrix.
+
+``optimize_batch(params, problems)`` returns what ``optimize(params, problems[k])`` returns, for every k, while the
+batch reads the matrix once per trial for all members (``pdhg_batch_trial_step``: member-interleaved iterates,
+csrc/batch_kernels.hpp).  The members run in lockstep on accepted steps: one batch iteration is one ``take_step``
+of every active member; evaluations, restarts and primal-weight updates happen per member at the iterations
+``optimize`` would use, with the same helpers; a member that terminates leaves the batch.
+
+``HipPdhgBatch`` is the device side: one ``pdhg_handle`` that owns the matrix plus K member handles that borrow it
+(``.members``: ``HipPdhgEngine`` views -- every single-LP method works on them).
+"""
+import ctypes
+import math
+import os
+import time as _time
+
+import numpy as np
+import scipy.sparse as sp
+
+from . import _lib
+from .engine import HipPdhgEngine, _d, _i, _pd, _pi
+from .evaluation import POINT_AVERAGE, POINT_CURRENT, DeviceEvaluator, HostEvaluator
+from .iteration_stats_utils import print_to_screen_this_iteration
+from .preprocess import rescale_problem, validate
+from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams, EngineOps,
+                                          MalitskyPockStepsizeParameters, PdhgSolverState, UnscaledEngineOps,
+                                          _display_iteration_stats, estimate_maximum_singular_value,
+                                          interaction_and_movement, julia_min)
+from .quadratic_programming import QuadraticProgrammingProblem, ScaledQpProblem
+from .saddle_point import (compute_new_primal_weight, create_last_restart_info, run_restart_scheme,
+                           select_initial_primal_weight, unscaled_saddle_point_output,
+                           update_objective_bound_estimates)
+from .solve_log import PointType, RestartChoice, TerminationReason
+from .termination import cached_quadratic_program_info, check_termination_criteria
+
+MAX_BATCH = 32
+_int_p = ctypes.POINTER(ctypes.c_int)
+
+
+class _MemberEngine(HipPdhgEngine):
+    """A non-owning view of member k: the batch frees it (``close`` only forgets the handle)."""
+
+    def close(self):
+        self._h = None
+
+    def rescale(self, *args, **kw):
+        raise ValueError("a batch member shares its batch's matrix: rescale the batch")
+
+
+class HipPdhgBatch:
+    """K LPs with one constraint matrix on one GPU (``pdhg_create_batch``)."""
+
+    def __init__(self, constraint_matrix, objective_vectors, right_hand_sides, variable_lower_bounds,
+                 variable_upper_bounds, num_equalities, device_id=-1, stream=None):
+        self._L = _lib.lib()
+        A = sp.csc_matrix(constraint_matrix)
+        self.m, self.n = int(A.shape[0]), int(A.shape[1])
+        c = _d(np.asarray(objective_vectors, dtype=np.float64))
+        K = c.shape[0]
+        if not 1 <= K <= MAX_BATCH:
+            raise ValueError(f"a batch holds 1..{MAX_BATCH} problems, not {K}")
+        b = _d(np.asarray(right_hand_sides, dtype=np.float64))
+        lb = _d(np.asarray(variable_lower_bounds, dtype=np.float64))
+        ub = _d(np.asarray(variable_upper_bounds, dtype=np.float64))
+        if c.shape != (K, self.n) or lb.shape != (K, self.n) or ub.shape != (K, self.n) or b.shape != (K, self.m):
+            raise ValueError("vector shapes do not match K members of the constraint matrix")
+        colptr, rowval, nzval = _i(A.indptr), _i(A.indices), _d(A.data)
+        h = ctypes.c_void_p()
+        _lib.check(self._L.pdhg_create_batch(
+            ctypes.byref(h), K, self.m, self.n, len(nzval), _pi(colptr), _pi(rowval), _pd(nzval), 0,
+            _pd(c), _pd(b), _pd(lb), _pd(ub), int(num_equalities), int(device_id),
+            ctypes.c_void_p(stream) if stream else None))
+        self._h = h
+        self.K = K
+        self.members = []
+        for k in range(K):
+            mh = ctypes.c_void_p()
+            _lib.check(self._L.pdhg_batch_member(self._h, k, ctypes.byref(mh)))
+            eng = _MemberEngine.__new__(_MemberEngine)
+            eng._L, eng._h, eng.m, eng.n = self._L, mh, self.m, self.n
+            self.members.append(eng)
+
+    @classmethod
+    def from_problems(cls, problems, **kw):
+        check_batch(problems)
+        p0 = problems[0]
+        return cls(p0.constraint_matrix, [p.objective_vector for p in problems],
+                   [p.right_hand_side for p in problems], [p.variable_lower_bound for p in problems],
+                   [p.variable_upper_bound for p in problems], p0.num_equalities, **kw)
+
+    takes_original_problem = True
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for eng in self.members:
+                eng._h = None
+            self._L.pdhg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _mask(self, active):
+        a = np.ones(self.K, dtype=np.int32) if active is None else np.asarray(active, dtype=np.int32).copy()
+        if a.shape != (self.K,):
+            raise ValueError("one mask entry per member")
+        return a
+
+    def rescale(self, l_inf_ruiz_iterations, l2_norm_rescaling, pock_chambolle_alpha):
+        """``rescale_problem`` once on the shared matrix, applied to every member's vectors; returns
+        (constraint_rescaling, variable_rescaling), the same for every member."""
+        e, dvec = np.empty(self.m), np.empty(self.n)
+        use_pc = pock_chambolle_alpha is not None
+        _lib.check(self._L.pdhg_rescale(self._h, int(l_inf_ruiz_iterations), int(bool(l2_norm_rescaling)), int(use_pc),
+                                        float(pock_chambolle_alpha) if use_pc else 0.0, _pd(e), _pd(dvec)))
+        return e, dvec
+
+    def trial_step(self, step_sizes, primal_weights, theta=1.0, active=None):
+        """One trial of every active member: a (K, 5) array of ``pdhg_trial_step``'s sums (rows of inactive
+        members are NaN)."""
+        a = self._mask(active)
+        ss, pw = _d(np.broadcast_to(step_sizes, (self.K,))), _d(np.broadcast_to(primal_weights, (self.K,)))
+        out = np.full(5 * self.K, np.nan)
+        _lib.check(self._L.pdhg_batch_trial_step(self._h, _pd(ss), _pd(pw), float(theta),
+                                                 a.ctypes.data_as(_int_p), _pd(out)))
+        return out.reshape(self.K, 5)
+
+    def accept(self, accept, avg_weights):
+        a = self._mask(accept)
+        w = _d(np.broadcast_to(avg_weights, (self.K,)))
+        _lib.check(self._L.pdhg_batch_accept(self._h, a.ctypes.data_as(_int_p), _pd(w)))
+
+    def take_steps_adaptive(self, n_steps, reduction_exponent, growth_exponent, step_sizes, primal_weights,
+                            total_number_iterations, cumulative_kkt_passes, active=None):
+        """``n_steps`` take_steps of every active member in lockstep.  Returns arrays (step_sizes,
+        total_number_iterations, cumulative_kkt_passes, numerical_error, steps_done)."""
+        a = self._mask(active)
+        ss = _d(np.array(step_sizes, dtype=np.float64))
+        pw = _d(np.array(primal_weights, dtype=np.float64))
+        it = np.array(total_number_iterations, dtype=np.int64)
+        kkt = _d(np.array(cumulative_kkt_passes, dtype=np.float64))
+        err = np.zeros(self.K, dtype=np.int32)
+        done = np.zeros(self.K, dtype=np.int64)
+        _lib.check(self._L.pdhg_batch_take_steps_adaptive(
+            self._h, int(n_steps), float(reduction_exponent), float(growth_exponent), _pd(ss), _pd(pw), _pi(it),
+            _pd(kkt), err.ctypes.data_as(_int_p), a.ctypes.data_as(_int_p), _pi(done)))
+        return ss, it, kkt, err.astype(bool), done
+
+
+def check_batch(problems, params=None):
+    """The batch's preconditions, checked before any device work (ValueError)."""
+    problems = list(problems)
+    if not 1 <= len(problems) <= MAX_BATCH:
+        raise ValueError(f"optimize_batch takes 1..{MAX_BATCH} problems, not {len(problems)}")
+    if params is not None and isinstance(params.step_size_policy_params, MalitskyPockStepsizeParameters):
+        raise ValueError("optimize_batch supports the adaptive and constant step-size policies, not Malitsky-Pock")
+    A0 = sp.csc_matrix(problems[0].constraint_matrix)
+    A0.sort_indices()
+    for k, p in enumerate(problems):
+        Q = p.objective_matrix
+        if Q is not None and Q.nnz > 0 and np.any(sp.csc_matrix(Q).data != 0):
+            raise ValueError(f"problem {k} is a QP: optimize_batch takes LPs only")
+        if int(p.num_equalities) != int(problems[0].num_equalities):
+            raise ValueError(f"problem {k} has num_equalities {p.num_equalities}, problem 0 {problems[0].num_equalities}")
+        if k == 0:
+            continue
+        A = sp.csc_matrix(p.constraint_matrix)
+        if A.shape != A0.shape:
+            raise ValueError(f"problem {k}'s constraint matrix has shape {A.shape}, problem 0's {A0.shape}")
+        A.sort_indices()
+        if not (np.array_equal(A.indptr, A0.indptr) and np.array_equal(A.indices, A0.indices)):
+            raise ValueError(f"problem {k}'s constraint matrix has another sparsity pattern than problem 0's")
+        if not np.array_equal(A.data, A0.data):
+            raise ValueError(f"problem {k}'s constraint matrix has other values than problem 0's")
+    return problems
+
+
+def _default_batch_factory(problems):
+    return HipPdhgBatch.from_problems(problems)
+
+
+_default_batch_factory.takes_original_problem = True
+
+
+class _Member:
+    """One member's host-side state: what ``_optimize``'s locals are for a single solve."""
+
+    def __init__(self, params, original_problem, scaled_problem, problem, engine, matrix_max_abs):
+        self.original = original_problem
+        self.scaled_problem = scaled_problem
+        self.problem = problem
+        self.engine = engine
+        self.qp_cache = cached_quadratic_program_info(original_problem)
+        self.ops = EngineOps(engine, problem)
+        self.original_ops = UnscaledEngineOps(engine, scaled_problem)
+        self.state = PdhgSolverState(engine)
+        self.matrix_max_abs = matrix_max_abs
+        self.iteration = 0
+        self.iteration_stats = []
+        self.time_basic = 0.0
+        self.output = None
+        self.last_restart_info = create_last_restart_info()
+        self.params = params
+
+    def inv_max_abs(self):
+        return math.inf if self.matrix_max_abs == 0.0 else 1.0 / self.matrix_max_abs
+
+    def start(self, power_estimate):
+        params, st, problem = self.params, self.state, self.problem
+        policy = params.step_size_policy_params
+        if isinstance(policy, AdaptiveStepsizeParams):
+            st.cumulative_kkt_passes += 0.5
+            st.step_size = self.inv_max_abs()
+        else:
+            desired_relative_error, maximum_singular_value, number_of_power_iterations = power_estimate(self)
+            st.step_size = (1 - desired_relative_error) / maximum_singular_value
+            st.cumulative_kkt_passes += number_of_power_iterations
+        if params.scale_invariant_initial_primal_weight:
+            st.primal_weight = select_initial_primal_weight(problem, np.ones(problem.num_variables),
+                                                            np.ones(problem.num_constraints),
+                                                            params.primal_importance, params.verbosity)
+        else:
+            st.primal_weight = params.primal_importance
+        if getattr(self.engine, "supports_device_evaluation", False):
+            self.ev = DeviceEvaluator(self.engine, self.scaled_problem, self.qp_cache)
+        else:
+            self.ev = HostEvaluator(self.engine, self.scaled_problem, self.qp_cache, self.ops, self.original_ops)
+        st.numerical_error = False
+        self.start_time = _time.time()
+
+    def evaluate(self):
+        """The top of one iteration of optimize's loop (pdhg.jl:862-1023).  Returns the number of take_steps to
+        run before the next evaluation, or 0 once the member has terminated (self.output set)."""
+        params, st, engine, ev = self.params, self.state, self.engine, self.ev
+        tc = params.termination_criteria
+        freq = params.termination_evaluation_frequency
+        iteration_limit = tc.iteration_limit
+        self.iteration += 1
+        iteration = self.iteration
+        if ((iteration - 1) % freq == 0 or iteration == iteration_limit + 1 or iteration <= 10 or
+                st.numerical_error):
+            st.cumulative_kkt_passes += 2.0
+            count_x, count_y, _, _ = engine.average_info()
+            avg_point = POINT_CURRENT if (st.numerical_error or count_x == 0 or count_y == 0) else POINT_AVERAGE
+            stats = ev.iteration_stats(avg_point, tc, params.record_iteration_stats, iteration,
+                                       _time.time() - self.start_time, st.cumulative_kkt_passes, st.step_size,
+                                       st.primal_weight, PointType.POINT_TYPE_AVERAGE_ITERATE)
+            stats.method_specific_stats["time_spent_doing_basic_algorithm"] = self.time_basic
+            with np.errstate(divide="ignore"):
+                primal_weight_norm = float(np.float64(1) / st.step_size * st.primal_weight)
+                dual_weight_norm = float(np.float64(1) / st.step_size / st.primal_weight)
+            reason = check_termination_criteria(tc, self.qp_cache, stats)
+            if st.numerical_error and reason is False:
+                reason = TerminationReason.TERMINATION_REASON_NUMERICAL_ERROR
+            if params.record_iteration_stats or reason is not False:
+                update_objective_bound_estimates(stats.method_specific_stats, ev, avg_point, primal_weight_norm,
+                                                 dual_weight_norm)
+                self.iteration_stats.append(stats)
+            if print_to_screen_this_iteration(reason, iteration, params.verbosity, freq):
+                _display_iteration_stats(stats)
+            if reason is not False:
+                if params.verbosity >= 2:
+                    print(f"Terminated after {iteration - 1} iterations: {reason.name}")
+                x, y = ev.solution(avg_point)
+                self.output = unscaled_saddle_point_output(self.scaled_problem, x, y, reason, iteration - 1,
+                                                           self.iteration_stats)
+                return 0
+            stats.restart_used = run_restart_scheme(ev, self.last_restart_info, iteration - 1, primal_weight_norm,
+                                                    dual_weight_norm, st.primal_weight, params.verbosity,
+                                                    params.restart_params)
+            if stats.restart_used != RestartChoice.RESTART_CHOICE_NO_RESTART:
+                st.primal_weight = compute_new_primal_weight(
+                    self.last_restart_info, st.primal_weight,
+                    params.restart_params.primal_weight_update_smoothing, params.verbosity)
+                st.ratio_step_sizes = 1.0
+        next_evaluation = ((iteration - 1) // freq + 1) * freq + 1
+        if iteration < 10:
+            next_evaluation = iteration + 1
+        if iteration < iteration_limit + 1:
+            next_evaluation = min(next_evaluation, iteration_limit + 1)
+        return next_evaluation - iteration
+
+
+def _take_steps_python(batch, members, n_steps, policy):
+    """The lockstep loop of pdhg_batch_take_steps_adaptive (and the constant policy's) through the batch's trial /
+    accept calls: for batches without a native multi-step call."""
+    K = len(batch.members)
+    slot = [_slot(batch, mb) for mb in members]
+    live = {k: mb for k, mb in zip(slot, members)}
+    done = {k: 0 for k in slot}
+    for _ in range(n_steps):
+        if not live:
+            break
+        entry = {k: mb.state.step_size for k, mb in live.items()}
+        need = dict(live)
+        while need:
+            mask = np.zeros(K, dtype=np.int32)
+            ss, pw = np.ones(K), np.ones(K)
+            for k, mb in need.items():
+                mask[k] = 1
+                ss[k], pw[k] = mb.state.step_size, mb.state.primal_weight
+                if isinstance(policy, AdaptiveStepsizeParams):
+                    mb.state.total_number_iterations += 1
+            raw = batch.trial_step(ss, pw, 1.0, mask)
+            acc = np.zeros(K, dtype=np.int32)
+            for k in list(need):
+                st = need[k].state
+                st.cumulative_kkt_passes += 1
+                if not isinstance(policy, AdaptiveStepsizeParams):
+                    acc[k] = 1
+                    done[k] += 1
+                    del need[k]
+                    continue
+                interaction, movement = interaction_and_movement(raw[k], st.primal_weight)
+                if movement == 0.0:
+                    st.numerical_error = True
+                    done[k] += 1
+                    del need[k]
+                    del live[k]
+                    continue
+                limit = movement / interaction if interaction > 0 else math.inf
+                step = st.step_size
+                if step <= limit:
+                    acc[k] = 1
+                    done[k] += 1
+                    del need[k]
+                k1 = float(st.total_number_iterations + 1)
+                first_term = (1 - k1 ** (-policy.reduction_exponent)) * limit
+                second_term = (1 + k1 ** (-policy.growth_exponent)) * step
+                st.step_size = julia_min(first_term, second_term)
+            weights = np.ones(K)
+            for k in range(K):
+                if acc[k]:
+                    weights[k] = entry[k]
+            batch.accept(acc, weights)
+    return [done[k] for k in slot]
+
+
+def _slot(batch, member):
+    return next(k for k, e in enumerate(batch.members) if e is member.engine)
+
+
+def _take_steps(batch, members, n_steps, policy):
+    """``n_steps`` take_steps of every member in ``members`` (lockstep); returns the steps each took."""
+    if (isinstance(policy, AdaptiveStepsizeParams) and isinstance(batch, HipPdhgBatch)
+            and os.environ.get("PDHG_PY_TAKE_STEP", "0") != "1"):
+        K = batch.K
+        slot = [_slot(batch, mb) for mb in members]
+        mask = np.zeros(K, dtype=np.int32)
+        ss, pw, kkt = np.ones(K), np.ones(K), np.zeros(K)
+        it = np.zeros(K, dtype=np.int64)
+        for k, mb in zip(slot, members):
+            mask[k] = 1
+            ss[k], pw[k] = mb.state.step_size, mb.state.primal_weight
+            it[k], kkt[k] = mb.state.total_number_iterations, mb.state.cumulative_kkt_passes
+        ss, it, kkt, err, done = batch.take_steps_adaptive(n_steps, policy.reduction_exponent,
+                                                           policy.growth_exponent, ss, pw, it, kkt, mask)
+        for k, mb in zip(slot, members):
+            mb.state.step_size, mb.state.total_number_iterations = float(ss[k]), int(it[k])
+            mb.state.cumulative_kkt_passes = float(kkt[k])
+            if err[k]:
+                mb.state.numerical_error = True
+        return [int(done[k]) for k in slot]
+    return _take_steps_python(batch, members, n_steps, policy)
+
+
+def optimize_batch(params, problems, batch_factory=None):
+    """``optimize(params, problems[k])`` for every k, as one batch: a list of ``SaddlePointOutput`` in input order.
+
+    The problems must be LPs that share the constraint matrix (shape, pattern, values) and ``num_equalities``;
+    ``batch_factory(problems) -> batch`` builds the device side (default ``HipPdhgBatch``; a factory whose
+    ``takes_original_problem`` is true receives the original problems and rescales on the device, any other one
+    receives the host-rescaled problems).  Malitsky-Pock, QPs, an empty list or more than 32 problems raise
+    ``ValueError`` before any device work."""
+    problems = check_batch(problems, params)
+    for p in problems:
+        validate(p)
+    if params.primal_importance <= 0 or not math.isfinite(params.primal_importance):
+        raise ValueError("primal_importance must be positive and finite")
+    policy = params.step_size_policy_params
+    if not isinstance(policy, (AdaptiveStepsizeParams, ConstantStepsizeParams)):
+        raise ValueError(f"optimize_batch does not support the step-size policy {type(policy).__name__}")
+    batch = None
+    try:
+        factory = batch_factory or _default_batch_factory
+        device_rescale = getattr(factory, "takes_original_problem", False) and \
+            os.environ.get("PDHG_HOST_RESCALE", "0") != "1"
+        members = []
+        if device_rescale:
+            batch = factory(problems)
+            E, D = batch.rescale(params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
+            matrix_max_abs = batch.members[0].matrix_max_abs()
+            m0, n0 = problems[0].constraint_matrix.shape
+            for p, eng in zip(problems, batch.members):
+                c_s, b_s, lb_s, ub_s = eng.get_problem_vectors()
+                scaled_qp = QuadraticProgrammingProblem(lb_s, ub_s, sp.csc_matrix((n0, n0)), c_s, p.objective_constant,
+                                                        sp.csc_matrix((m0, n0)), b_s, p.num_equalities)
+                scaled = ScaledQpProblem(p, scaled_qp, E.copy(), D.copy())
+                members.append(_Member(params, p, scaled, scaled_qp, eng, matrix_max_abs))
+        else:
+            scaled = [rescale_problem(params.l_inf_ruiz_iterations, params.l2_norm_rescaling,
+                                      params.pock_chambolle_alpha, params.verbosity, p) for p in problems]
+            data = scaled[0].scaled_qp.constraint_matrix.data
+            matrix_max_abs = float(np.max(np.abs(data))) if len(data) else 0.0
+            batch = factory([s.scaled_qp for s in scaled])
+            for p, s, eng in zip(problems, scaled, batch.members):
+                members.append(_Member(params, p, s, s.scaled_qp, eng, matrix_max_abs))
+
+        # the constant policy's power method depends on the matrix only: run once, on member 0's operators
+        estimate = {}
+
+        def power_estimate(mb):
+            if not estimate:
+                desired_relative_error = 0.2
+                sv, iters = estimate_maximum_singular_value(members[0].ops, members[0].problem.num_variables,
+                                                            probability_of_failure=0.001,
+                                                            desired_relative_error=desired_relative_error)
+                estimate["v"] = (desired_relative_error, sv, iters)
+            return estimate["v"]
+
+        for mb in members:
+            mb.start(power_estimate)
+
+        active = list(members)
+        while active:
+            requests = {}
+            for mb in active:
+                steps = mb.evaluate()
+                if steps > 0:
+                    requests.setdefault(steps, []).append(mb)
+            active = [mb for mb in active if mb.output is None]
+            for steps, group in sorted(requests.items()):
+                t0 = _time.time()
+                done = _take_steps(batch, group, steps, policy)
+                dt = _time.time() - t0
+                for mb, d in zip(group, done):
+                    mb.iteration += d - 1
+                    mb.time_basic += dt
+        return [mb.output for mb in members]
+    finally:
+        if batch is not None and hasattr(batch, "close"):
+            batch.close()

@@ -214,6 +214,7 @@ int pdhg_set_objective_matrix(pdhg_handle *h0, int64_t q_nnz, const int64_t *q_c
                               const int64_t *q_rowval, const double *q_nzval, int index_base) {
   int rc = check_handle(h0);
   if (rc) return rc;
+  if (h0->owner || h0->bat) return fail(-1, "pdhg_set_objective_matrix: batches hold LPs only");
   const Shards L = shards_of(h0);
   bump_version(L);
   bool all_zero = true;
@@ -248,6 +249,8 @@ int pdhg_set_objective_matrix(pdhg_handle *h0, int64_t q_nnz, const int64_t *q_c
 
 void pdhg_destroy(pdhg_handle *h) {
   if (!h) return;
+  if (h->owner) return;               // a batch member lives and dies with its batch
+  if (h->bat) batch_release(h);
   if (h->grp) destroy_group(h->grp);
   else destroy_shard(h);
 }

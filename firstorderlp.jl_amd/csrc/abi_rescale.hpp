@@ -90,14 +90,16 @@ static int apply_scaling(pdhg_handle *h, RescaleTmp &t) {
   hipLaunchKernelGGL(resc_apply_vectors_kernel, dim3(h->ew_grid_nm), dim3(TPB), 0, h->stream, n, m, t.dv, t.ev,
                      h->c, h->lb, h->ub, h->b, t.cum_d, t.cum_e);
   HIP_TRY(hipGetLastError());
+  if (h->bat) return batch_scale_members(h, t.dv, t.ev);   // the same step on every batch member's vectors
   return 0;
 }
 
 int pdhg_rescale(pdhg_handle *h0, int l_inf_ruiz_iterations, int l2_norm_rescaling,
                  int use_pock_chambolle, double pock_chambolle_alpha,
                  double *constraint_rescaling_out, double *variable_rescaling_out) {
-  int rc = check_handle(h0);
+  int rc = check_handle(h0, true, true);
   if (rc) return rc;
+  if (h0->owner) return fail(-1, "pdhg_rescale: a batch member shares its batch's matrix: rescale the batch handle");
   if (use_pock_chambolle && !(pock_chambolle_alpha >= 0.0 && pock_chambolle_alpha <= 2.0))
     return fail(-1, "pock_chambolle_alpha must be in [0, 2]");
   const Shards L = shards_of(h0);

@@ -49,8 +49,10 @@
 #include "trial_kernel.hpp"
 #include "small_lp_kernel.hpp"
 #include "tr_coop_kernel.hpp"
+#include "batch_kernels.hpp"
 
 namespace { struct DistGroup; }
+struct BatchState;
 
 struct pdhg_handle {
   int device = 0;
@@ -209,6 +211,11 @@ struct pdhg_handle {
   // host-side breakdown of graph trials (PDHG_VERBOSE): seconds in node updates, in hipGraphLaunch, waiting
   double t_set = 0.0, t_launch = 0.0, t_wait = 0.0;
   long n_graph_trials = 0;
+
+  // ---- batched solves (abi_batch.hpp).  A batch handle owns the matrix and `bat` (its members, the interleaved
+  // vectors); a member's A / At are the batch's layouts, borrowed (`owner` = the batch): it is freed with the batch.
+  BatchState *bat = nullptr;
+  pdhg_handle *owner = nullptr;
 };
 
 #include "dist.hpp"
@@ -739,9 +746,13 @@ int pdhg_create(pdhg_handle **out, int64_t m, int64_t n, int64_t nnz,
                       device_id, stream, n, 0);
 }
 
+static void batch_release(pdhg_handle *h);
+static int batch_scale_members(pdhg_handle *h, const double *dv, const double *ev);
+
 #include "abi_dist.hpp"
 #include "abi_trial.hpp"
 #include "abi_eval.hpp"
 #include "abi_rescale.hpp"
 #include "abi_measure.hpp"
+#include "abi_batch.hpp"
 }  // extern "C"

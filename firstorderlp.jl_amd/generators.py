@@ -189,3 +189,39 @@ def l1_svm_rcv1_like_lp(num_samples=20242, num_features=47236, nnz_per_row=74,
     """BASELINE configs[3] on the synthetic rcv1-shaped data."""
     X, labels = synthetic_rcv1_like(num_samples, num_features, nnz_per_row, seed)
     return l1_svm_lp(preprocess_training_data(X), labels, regularizer_weight)
+
+
+def personalized_pagerank_lps(num_nodes, teleports, approx_num_edges=None, damping_factor=0.99, seed=0):
+    """Personalized PageRank: one PageRank LP (``pagerank_lp``) per teleport vector, all on the same graph.
+    Row i + 1 of the LP reads ``x_i - d * sum_j x_j / deg_j >= (1 - d) * t_i`` for the teleport distribution t
+    (t = 1/n everywhere is ``pagerank_lp`` itself), so the members share the constraint matrix and differ in
+    ``right_hand_side[1:]`` only.  ``teleports``: K vectors of length num_nodes, each non-negative with sum 1."""
+    base = pagerank_lp(num_nodes, approx_num_edges, damping_factor, seed)
+    n = int(num_nodes)
+    out = []
+    for t in teleports:
+        t = np.asarray(t, dtype=np.float64)
+        if t.shape != (n,):
+            raise ValueError("every teleport vector must have num_nodes entries")
+        b = base.right_hand_side.copy()
+        b[1:] = (1.0 - damping_factor) * t
+        out.append(linear_programming_problem(base.variable_lower_bound.copy(), base.variable_upper_bound.copy(),
+                                              base.objective_vector.copy(), 0.0, base.constraint_matrix, b,
+                                              base.num_equalities))
+    return out
+
+
+def l1_svm_regularization_path(features, labels, weights):
+    """The L1-SVM LP (``l1_svm_lp``) for every regularizer weight in ``weights``: the members share the constraint
+    matrix and differ in ``objective_vector`` only.  ``features`` is used as given (``preprocess_training_data`` first
+    for the reference's benchmark form)."""
+    first = None
+    out = []
+    for w in weights:
+        p = l1_svm_lp(features, labels, w)
+        if first is None:
+            first = p.constraint_matrix
+        else:
+            p.constraint_matrix = first
+        out.append(p)
+    return out

@@ -481,6 +481,49 @@ int pdhg_measure_launch_overhead(pdhg_handle *h, int reps, double out[2]);
  * whose bits differ (0 expected).  No reference counterpart: a property of this implementation. */
 int pdhg_selftest_wave_sums(pdhg_handle *h, int64_t seed, int64_t out[2]);
 
+/*
+ * ---- batched solves: K LPs that share one constraint matrix ----------------------------------
+ * No reference counterpart (the reference solves one LP per call); every member runs the reference's
+ * take_step (src/primal_dual_hybrid_gradient.jl:653-767) on its own LP.  Members share the matrix
+ * (shape, pattern, values) and num_equalities; each has its own c, b, lb, ub.
+ *
+ * pdhg_create_batch: `count` (1..32) members, vectors member-major: c[count*n], b[count*m],
+ * lb[count*n], ub[count*n]; the matrix as in pdhg_create, held once.  nnz must stay below 2^31.
+ * The returned handle is the BATCH: it holds the shared matrix, and pdhg_rescale on it scales the matrix once
+ * and every member's c, b, lb, ub (the rescaling depends on the matrix only); pdhg_destroy frees the batch
+ * and its members.  Every other single-LP entry point refuses the batch handle with -1 (it runs no
+ * iterations of its own): call them on the members.
+ */
+int pdhg_create_batch(pdhg_handle **out, int count, int64_t m, int64_t n, int64_t nnz,
+                      const int64_t *colptr, const int64_t *rowval, const double *nzval,
+                      int index_base, const double *c, const double *b, const double *lb,
+                      const double *ub, int64_t num_equalities, int device_id, void *stream);
+/* Member k (0..count-1): an ordinary handle that BORROWS the batch's matrix and runs on its stream.
+ * Every single-LP entry point works on it (trial / accept, averages, restarts, get / set_current,
+ * the evaluation branch, trust-region bounds) except pdhg_rescale and pdhg_set_objective_matrix,
+ * which return -1.  pdhg_destroy on a member does nothing: members live and die with the batch. */
+int pdhg_batch_member(pdhg_handle *batch, int k, pdhg_handle **member);
+/* One trial for every member k with active[k] != 0: out[5k .. 5k+4] = what pdhg_trial_step(member k,
+ * step_size[k], primal_weight[k], theta) returns, and the same x', y', A'y' in member k's shadow
+ * buffers.  Members not active are neither read nor written.  Bitwise pdhg_trial_step for rows
+ * of <= 2048 entries (strict order) / <= 256 (relaxed); longer rows are summed in a fixed
+ * chunked order within the relaxed bar.  The matrix is read once for all active members. */
+int pdhg_batch_trial_step(pdhg_handle *batch, const double *step_size, const double *primal_weight,
+                          double theta, const int *active, double *out);
+/* pdhg_accept(member k, avg_weight[k]) for every k with accept[k] != 0. */
+int pdhg_batch_accept(pdhg_handle *batch, const int *accept, const double *avg_weight);
+/* pdhg_take_steps_adaptive for every active member, in lockstep: per step, every active member
+ * takes exactly one take_step; a member that rejects keeps trialling while those that accepted
+ * are masked.  All arrays have `count` entries; step_size, total_number_iterations and
+ * cumulative_kkt_passes are in/out per member as in pdhg_take_steps_adaptive.  A member that
+ * raises numerical_error[k] stops after that step (counted in steps_done[k]) and takes no more
+ * trials; the others go on.  Inactive members' entries are left as they are. */
+int pdhg_batch_take_steps_adaptive(pdhg_handle *batch, int64_t n_steps, double reduction_exponent,
+                                   double growth_exponent, double *step_size,
+                                   const double *primal_weight, int64_t *total_number_iterations,
+                                   double *cumulative_kkt_passes, int *numerical_error,
+                                   const int *active, int64_t *steps_done);
+
 #ifdef __cplusplus
 }
 #endif

@@ -976,4 +976,65 @@ function trial_timeline(s::HipSolverState)
   return rc == 0 ? out : nothing
 end
 
+
+# ---- batched solves: K LPs that share one constraint matrix (include/pdhg_hip.h) ----------------------------
+"""K problems with one constraint matrix as a batch (`pdhg_create_batch`): returns (batch handle, member handles).
+The members borrow the batch's matrix; every single-LP call above works on them (wrap one in a `HipSolverState`-like
+holder without a finalizer: `pdhg_destroy` on a member does nothing, `destroy_batch` frees the batch and its members)."""
+function create_batch(problems::Vector{FirstOrderLp.QuadraticProgrammingProblem}; device_id::Integer = -1)
+  K = length(problems)
+  A = problems[1].constraint_matrix
+  m, n = size(A)
+  c = reduce(vcat, [p.objective_vector for p in problems])
+  b = reduce(vcat, [p.right_hand_side for p in problems])
+  lb = reduce(vcat, [p.variable_lower_bound for p in problems])
+  ub = reduce(vcat, [p.variable_upper_bound for p in problems])
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ccall((:pdhg_create_batch, LIB), Cint,
+    (Ref{Ptr{Cvoid}}, Cint, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint,
+     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Cint, Ptr{Cvoid}),
+    h, K, m, n, length(A.nzval), A.colptr, A.rowval, A.nzval, 1, c, b, lb, ub,
+    problems[1].num_equalities, device_id, C_NULL))
+  members = Ptr{Cvoid}[]
+  for k in 0:K-1
+    mh = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pdhg_batch_member, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), h[], k, mh))
+    push!(members, mh[])
+  end
+  return h[], members
+end
+
+destroy_batch(batch::Ptr{Cvoid}) = ccall((:pdhg_destroy, LIB), Cvoid, (Ptr{Cvoid},), batch)
+
+"One trial of every active member (`pdhg_batch_trial_step`): a 5 x K matrix of the raw sums."
+function batch_trial_step(batch::Ptr{Cvoid}, step_size::Vector{Float64}, primal_weight::Vector{Float64},
+                          theta::Float64, active::Vector{Cint})
+  out = fill(NaN, 5, length(active))
+  check(ccall((:pdhg_batch_trial_step, LIB), Cint,
+    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Cint}, Ptr{Float64}),
+    batch, step_size, primal_weight, theta, active, out))
+  return out
+end
+
+"`pdhg_accept` on every member with accept[k] != 0 (`pdhg_batch_accept`)."
+function batch_accept(batch::Ptr{Cvoid}, accept::Vector{Cint}, avg_weight::Vector{Float64})
+  check(ccall((:pdhg_batch_accept, LIB), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Float64}), batch, accept, avg_weight))
+end
+
+"`n_steps` adaptive take_steps of every active member in lockstep (`pdhg_batch_take_steps_adaptive`); the vectors are updated in place."
+function batch_take_steps_adaptive(batch::Ptr{Cvoid}, n_steps::Integer, reduction_exponent::Float64,
+                                   growth_exponent::Float64, step_size::Vector{Float64},
+                                   primal_weight::Vector{Float64}, total_number_iterations::Vector{Int64},
+                                   cumulative_kkt_passes::Vector{Float64}, active::Vector{Cint})
+  K = length(active)
+  numerical_error = zeros(Cint, K)
+  steps_done = zeros(Int64, K)
+  check(ccall((:pdhg_batch_take_steps_adaptive, LIB), Cint,
+    (Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Cint},
+     Ptr{Cint}, Ptr{Int64}),
+    batch, n_steps, reduction_exponent, growth_exponent, step_size, primal_weight, total_number_iterations,
+    cumulative_kkt_passes, numerical_error, active, steps_done))
+  return numerical_error, steps_done
+end
+
 end # module
