@@ -4,13 +4,13 @@
 batch reads the matrix once per trial for all members (``pdhg_batch_trial_step``: member-interleaved iterates,
 csrc/batch_kernels.hpp).  The members run in lockstep on accepted steps: one batch iteration is one ``take_step``
 of every active member; evaluations, restarts and primal-weight updates happen per member at the iterations
-``optimize`` would use, with the same helpers; a member that terminates leaves the batch.
+``optimize`` would use, with the same helpers; a member that terminates leaves the batch.  Both drivers run the same
+per-problem solve object (``primal_dual_hybrid_gradient._Solve``): only the stepping between evaluations differs.
 
 ``HipPdhgBatch`` is the device side: one ``pdhg_handle`` that owns the matrix plus K member handles that borrow it
 (``.members``: ``HipPdhgEngine`` views -- every single-LP method works on them).
 """
 import ctypes
-import math
 import os
 import time as _time
 
@@ -19,19 +19,10 @@ import scipy.sparse as sp
 
 from . import _lib
 from .engine import HipPdhgEngine, _d, _i, _pd, _pi
-from .evaluation import POINT_AVERAGE, POINT_CURRENT, DeviceEvaluator, HostEvaluator
-from .iteration_stats_utils import print_to_screen_this_iteration
-from .preprocess import rescale_problem, validate
-from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams, EngineOps,
-                                          MalitskyPockStepsizeParameters, PdhgSolverState, UnscaledEngineOps,
-                                          _display_iteration_stats, estimate_maximum_singular_value,
-                                          interaction_and_movement, julia_min)
-from .quadratic_programming import QuadraticProgrammingProblem, ScaledQpProblem
-from .saddle_point import (compute_new_primal_weight, create_last_restart_info, run_restart_scheme,
-                           select_initial_primal_weight, unscaled_saddle_point_output,
-                           update_objective_bound_estimates)
-from .solve_log import PointType, RestartChoice, TerminationReason
-from .termination import cached_quadratic_program_info, check_termination_criteria
+from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams,
+                                          MalitskyPockStepsizeParameters, _check_inputs, _constant_step_estimate,
+                                          _device_scaled_problem, _host_scaled_problem, _rescales_on_device, _Solve,
+                                          adaptive_step_rule)
 
 MAX_BATCH = 32
 _int_p = ctypes.POINTER(ctypes.c_int)
@@ -76,9 +67,7 @@ class HipPdhgBatch:
         for k in range(K):
             mh = ctypes.c_void_p()
             _lib.check(self._L.pdhg_batch_member(self._h, k, ctypes.byref(mh)))
-            eng = _MemberEngine.__new__(_MemberEngine)
-            eng._L, eng._h, eng.m, eng.n = self._L, mh, self.m, self.n
-            self.members.append(eng)
+            self.members.append(_MemberEngine._wrap(self._L, mh, self.m, self.n))
 
     @classmethod
     def from_problems(cls, problems, **kw):
@@ -185,105 +174,6 @@ def _default_batch_factory(problems):
 _default_batch_factory.takes_original_problem = True
 
 
-class _Member:
-    """One member's host-side state: what ``_optimize``'s locals are for a single solve."""
-
-    def __init__(self, params, original_problem, scaled_problem, problem, engine, matrix_max_abs):
-        self.original = original_problem
-        self.scaled_problem = scaled_problem
-        self.problem = problem
-        self.engine = engine
-        self.qp_cache = cached_quadratic_program_info(original_problem)
-        self.ops = EngineOps(engine, problem)
-        self.original_ops = UnscaledEngineOps(engine, scaled_problem)
-        self.state = PdhgSolverState(engine)
-        self.matrix_max_abs = matrix_max_abs
-        self.iteration = 0
-        self.iteration_stats = []
-        self.time_basic = 0.0
-        self.output = None
-        self.last_restart_info = create_last_restart_info()
-        self.params = params
-
-    def inv_max_abs(self):
-        return math.inf if self.matrix_max_abs == 0.0 else 1.0 / self.matrix_max_abs
-
-    def start(self, power_estimate):
-        params, st, problem = self.params, self.state, self.problem
-        policy = params.step_size_policy_params
-        if isinstance(policy, AdaptiveStepsizeParams):
-            st.cumulative_kkt_passes += 0.5
-            st.step_size = self.inv_max_abs()
-        else:
-            desired_relative_error, maximum_singular_value, number_of_power_iterations = power_estimate(self)
-            st.step_size = (1 - desired_relative_error) / maximum_singular_value
-            st.cumulative_kkt_passes += number_of_power_iterations
-        if params.scale_invariant_initial_primal_weight:
-            st.primal_weight = select_initial_primal_weight(problem, np.ones(problem.num_variables),
-                                                            np.ones(problem.num_constraints),
-                                                            params.primal_importance, params.verbosity)
-        else:
-            st.primal_weight = params.primal_importance
-        if getattr(self.engine, "supports_device_evaluation", False):
-            self.ev = DeviceEvaluator(self.engine, self.scaled_problem, self.qp_cache)
-        else:
-            self.ev = HostEvaluator(self.engine, self.scaled_problem, self.qp_cache, self.ops, self.original_ops)
-        st.numerical_error = False
-        self.start_time = _time.time()
-
-    def evaluate(self):
-        """The top of one iteration of optimize's loop (pdhg.jl:862-1023).  Returns the number of take_steps to
-        run before the next evaluation, or 0 once the member has terminated (self.output set)."""
-        params, st, engine, ev = self.params, self.state, self.engine, self.ev
-        tc = params.termination_criteria
-        freq = params.termination_evaluation_frequency
-        iteration_limit = tc.iteration_limit
-        self.iteration += 1
-        iteration = self.iteration
-        if ((iteration - 1) % freq == 0 or iteration == iteration_limit + 1 or iteration <= 10 or
-                st.numerical_error):
-            st.cumulative_kkt_passes += 2.0
-            count_x, count_y, _, _ = engine.average_info()
-            avg_point = POINT_CURRENT if (st.numerical_error or count_x == 0 or count_y == 0) else POINT_AVERAGE
-            stats = ev.iteration_stats(avg_point, tc, params.record_iteration_stats, iteration,
-                                       _time.time() - self.start_time, st.cumulative_kkt_passes, st.step_size,
-                                       st.primal_weight, PointType.POINT_TYPE_AVERAGE_ITERATE)
-            stats.method_specific_stats["time_spent_doing_basic_algorithm"] = self.time_basic
-            with np.errstate(divide="ignore"):
-                primal_weight_norm = float(np.float64(1) / st.step_size * st.primal_weight)
-                dual_weight_norm = float(np.float64(1) / st.step_size / st.primal_weight)
-            reason = check_termination_criteria(tc, self.qp_cache, stats)
-            if st.numerical_error and reason is False:
-                reason = TerminationReason.TERMINATION_REASON_NUMERICAL_ERROR
-            if params.record_iteration_stats or reason is not False:
-                update_objective_bound_estimates(stats.method_specific_stats, ev, avg_point, primal_weight_norm,
-                                                 dual_weight_norm)
-                self.iteration_stats.append(stats)
-            if print_to_screen_this_iteration(reason, iteration, params.verbosity, freq):
-                _display_iteration_stats(stats)
-            if reason is not False:
-                if params.verbosity >= 2:
-                    print(f"Terminated after {iteration - 1} iterations: {reason.name}")
-                x, y = ev.solution(avg_point)
-                self.output = unscaled_saddle_point_output(self.scaled_problem, x, y, reason, iteration - 1,
-                                                           self.iteration_stats)
-                return 0
-            stats.restart_used = run_restart_scheme(ev, self.last_restart_info, iteration - 1, primal_weight_norm,
-                                                    dual_weight_norm, st.primal_weight, params.verbosity,
-                                                    params.restart_params)
-            if stats.restart_used != RestartChoice.RESTART_CHOICE_NO_RESTART:
-                st.primal_weight = compute_new_primal_weight(
-                    self.last_restart_info, st.primal_weight,
-                    params.restart_params.primal_weight_update_smoothing, params.verbosity)
-                st.ratio_step_sizes = 1.0
-        next_evaluation = ((iteration - 1) // freq + 1) * freq + 1
-        if iteration < 10:
-            next_evaluation = iteration + 1
-        if iteration < iteration_limit + 1:
-            next_evaluation = min(next_evaluation, iteration_limit + 1)
-        return next_evaluation - iteration
-
-
 def _take_steps_python(batch, members, n_steps, policy):
     """The lockstep loop of pdhg_batch_take_steps_adaptive (and the constant policy's) through the batch's trial /
     accept calls: for batches without a native multi-step call."""
@@ -314,23 +204,15 @@ def _take_steps_python(batch, members, n_steps, policy):
                     done[k] += 1
                     del need[k]
                     continue
-                interaction, movement = interaction_and_movement(raw[k], st.primal_weight)
-                if movement == 0.0:
+                accept, numerical_error, st.step_size = adaptive_step_rule(
+                    raw[k], st.primal_weight, st.step_size, st.total_number_iterations, policy)
+                if numerical_error:
                     st.numerical_error = True
-                    done[k] += 1
-                    del need[k]
                     del live[k]
-                    continue
-                limit = movement / interaction if interaction > 0 else math.inf
-                step = st.step_size
-                if step <= limit:
-                    acc[k] = 1
+                if accept or numerical_error:
+                    acc[k] = int(accept)
                     done[k] += 1
                     del need[k]
-                k1 = float(st.total_number_iterations + 1)
-                first_term = (1 - k1 ** (-policy.reduction_exponent)) * limit
-                second_term = (1 + k1 ** (-policy.growth_exponent)) * step
-                st.step_size = julia_min(first_term, second_term)
             weights = np.ones(K)
             for k in range(K):
                 if acc[k]:
@@ -376,53 +258,28 @@ def optimize_batch(params, problems, batch_factory=None):
     receives the host-rescaled problems).  Malitsky-Pock, QPs, an empty list or more than 32 problems raise
     ``ValueError`` before any device work."""
     problems = check_batch(problems, params)
-    for p in problems:
-        validate(p)
-    if params.primal_importance <= 0 or not math.isfinite(params.primal_importance):
-        raise ValueError("primal_importance must be positive and finite")
+    _check_inputs(params, problems)
     policy = params.step_size_policy_params
     if not isinstance(policy, (AdaptiveStepsizeParams, ConstantStepsizeParams)):
         raise ValueError(f"optimize_batch does not support the step-size policy {type(policy).__name__}")
+    factory = batch_factory or _default_batch_factory
     batch = None
     try:
-        factory = batch_factory or _default_batch_factory
-        device_rescale = getattr(factory, "takes_original_problem", False) and \
-            os.environ.get("PDHG_HOST_RESCALE", "0") != "1"
-        members = []
-        if device_rescale:
+        if _rescales_on_device(factory):
             batch = factory(problems)
             E, D = batch.rescale(params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
             matrix_max_abs = batch.members[0].matrix_max_abs()
-            m0, n0 = problems[0].constraint_matrix.shape
-            for p, eng in zip(problems, batch.members):
-                c_s, b_s, lb_s, ub_s = eng.get_problem_vectors()
-                scaled_qp = QuadraticProgrammingProblem(lb_s, ub_s, sp.csc_matrix((n0, n0)), c_s, p.objective_constant,
-                                                        sp.csc_matrix((m0, n0)), b_s, p.num_equalities)
-                scaled = ScaledQpProblem(p, scaled_qp, E.copy(), D.copy())
-                members.append(_Member(params, p, scaled, scaled_qp, eng, matrix_max_abs))
+            scaled = [_device_scaled_problem(p, eng, E.copy(), D.copy()) for p, eng in zip(problems, batch.members)]
         else:
-            scaled = [rescale_problem(params.l_inf_ruiz_iterations, params.l2_norm_rescaling,
-                                      params.pock_chambolle_alpha, params.verbosity, p) for p in problems]
-            data = scaled[0].scaled_qp.constraint_matrix.data
-            matrix_max_abs = float(np.max(np.abs(data))) if len(data) else 0.0
+            scaled, max_abs = zip(*[_host_scaled_problem(params, p) for p in problems])
+            matrix_max_abs = max_abs[0]
             batch = factory([s.scaled_qp for s in scaled])
-            for p, s, eng in zip(problems, scaled, batch.members):
-                members.append(_Member(params, p, s, s.scaled_qp, eng, matrix_max_abs))
+        members = [_Solve(params, p, s, eng, matrix_max_abs) for p, s, eng in zip(problems, scaled, batch.members)]
 
         # the constant policy's power method depends on the matrix only: run once, on member 0's operators
-        estimate = {}
-
-        def power_estimate(mb):
-            if not estimate:
-                desired_relative_error = 0.2
-                sv, iters = estimate_maximum_singular_value(members[0].ops, members[0].problem.num_variables,
-                                                            probability_of_failure=0.001,
-                                                            desired_relative_error=desired_relative_error)
-                estimate["v"] = (desired_relative_error, sv, iters)
-            return estimate["v"]
-
+        estimate = _constant_step_estimate(members[0]) if isinstance(policy, ConstantStepsizeParams) else None
         for mb in members:
-            mb.start(power_estimate)
+            mb.start(estimate)
 
         active = list(members)
         while active:
@@ -437,8 +294,7 @@ def optimize_batch(params, problems, batch_factory=None):
                 done = _take_steps(batch, group, steps, policy)
                 dt = _time.time() - t0
                 for mb, d in zip(group, done):
-                    mb.iteration += d - 1
-                    mb.time_basic += dt
+                    mb.stepped(d, dt)
         return [mb.output for mb in members]
     finally:
         if batch is not None and hasattr(batch, "close"):

@@ -51,7 +51,7 @@ static void batch_release(pdhg_handle *h) {
 }
 
 // A member: the batch's matrix layouts (struct copies: the same device arrays), its own vectors -- what create_shard
-// allocates for a plain handle.
+// allocates for a plain handle (alloc_shard_vectors).
 static int batch_create_member(pdhg_handle *o, const double *c, const double *b, const double *lb, const double *ub,
                                pdhg_handle **out) {
   *out = nullptr;
@@ -65,33 +65,7 @@ static int batch_create_member(pdhg_handle *o, const double *c, const double *b,
   h->remap = o->remap; h->relaxed = o->relaxed; h->lazy_accept = o->lazy_accept;
   h->A = o->A; h->At = o->At;
   h->coop_mode = 0;
-  const int64_t m = h->m, n = h->n;
-#define CK(expr) do { int _rc = (expr); if (_rc) { destroy_shard(h); return _rc; } } while (0)
-  auto up = [&](double **dst, const double *src, int64_t len) -> int {
-    int r2 = alloc_zero(dst, len);
-    if (r2) return r2;
-    if (len > 0) HIP_TRY(hipMemcpy(*dst, src, sizeof(double) * (size_t)len, hipMemcpyHostToDevice));
-    return 0;
-  };
-  CK(up(&h->c, c, n)); CK(up(&h->b, b, m)); CK(up(&h->lb, lb, n)); CK(up(&h->ub, ub, n));
-  CK(alloc_zero(&h->x, n)); CK(alloc_zero(&h->x_next, n)); CK(alloc_zero(&h->xbar, n));
-  CK(alloc_zero(&h->y, m)); CK(alloc_zero(&h->y_next, m));
-  CK(alloc_zero(&h->aty, n + 1)); CK(alloc_zero(&h->aty_next, n + 1));
-  CK(alloc_zero(&h->sum_x, n)); CK(alloc_zero(&h->sum_y, m));
-  CK(alloc_zero(&h->tmp_n, n)); CK(alloc_zero(&h->tmp_m, m));
-  h->ew_grid_n = o->ew_grid_n; h->ew_grid_m = o->ew_grid_m; h->ew_grid_nm = o->ew_grid_nm;
-  h->pAt_stride = o->pAt_stride;
-  CK(alloc_zero(&h->pA, 2 * (int64_t)std::max(h->A.slots(), 1)));
-  CK(alloc_zero(&h->pAt, 6 * (int64_t)std::max(h->pAt_stride, 1)));
-  CK(alloc_zero(&h->pQ, 2 * (int64_t)h->ew_grid_n));
-  CK(alloc_zero(&h->scal_dev, SCAL_MAX));
-  {
-    hipError_t e = hipHostMalloc((void **)&h->scal_host, sizeof(double) * SCAL_MAX * DIST_MAX_WORLD, hipHostMallocDefault);
-    if (e != hipSuccess) { destroy_shard(h); return fail((int)e, "hipHostMalloc failed"); }
-    e = hipEventCreate(&h->ev0); if (e == hipSuccess) e = hipEventCreate(&h->ev1);
-    if (e != hipSuccess) { destroy_shard(h); return fail((int)e, "hipEventCreate failed"); }
-  }
-#undef CK
+  if (int rc = alloc_shard_vectors(h, c, b, lb, ub)) { destroy_shard(h); return rc; }
   *out = h;
   return 0;
 }

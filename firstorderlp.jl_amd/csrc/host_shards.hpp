@@ -528,6 +528,39 @@ int tune_tiled_variant(pdhg_handle *h, CsrDev &D, const double *xin, double *out
   return 0;
 }
 
+// A handle's own vectors: c, b, lb, ub uploaded, the iterate / average / scratch vectors, the block partials of the
+// two products (sized by h->A and h->At, which are in place), the scalar buffers and the two events.  h->n, h->n_alloc
+// and h->m are set.  On failure the caller unwinds (destroy_shard).
+static int alloc_shard_vectors(pdhg_handle *h, const double *c, const double *b, const double *lb, const double *ub) {
+  const int64_t m = h->m, n = h->n, n_alloc = h->n_alloc;
+#define CK(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+  auto up = [&](double **dst, const double *src, int64_t len) -> int {
+    int r2 = alloc_zero(dst, len);
+    if (r2) return r2;
+    if (len > 0) { HIP_TRY(hipMemcpy(*dst, src, sizeof(double) * (size_t)len, hipMemcpyHostToDevice)); HIP_TRY(hipStreamSynchronize(nullptr)); }
+    return 0;
+  };
+  CK(up(&h->c, c, n)); CK(up(&h->b, b, m)); CK(up(&h->lb, lb, n)); CK(up(&h->ub, ub, n));
+  CK(alloc_zero(&h->x, n_alloc)); CK(alloc_zero(&h->x_next, n_alloc)); CK(alloc_zero(&h->xbar, n_alloc));
+  CK(alloc_zero(&h->y, m)); CK(alloc_zero(&h->y_next, m));
+  CK(alloc_zero(&h->aty, n_alloc + 1)); CK(alloc_zero(&h->aty_next, n_alloc + 1));
+  CK(alloc_zero(&h->sum_x, n)); CK(alloc_zero(&h->sum_y, m));
+  CK(alloc_zero(&h->tmp_n, n_alloc)); CK(alloc_zero(&h->tmp_m, m));
+  h->ew_grid_n = ew_grid(n); h->ew_grid_m = ew_grid(m); h->ew_grid_nm = ew_grid(std::max(n, m));
+  h->pAt_stride = std::max(h->At.slots(), h->ew_grid_n);
+  // block partials are double-double: hi parts, then lo parts
+  CK(alloc_zero(&h->pA, 2 * (int64_t)std::max(h->A.slots(), 1)));
+  CK(alloc_zero(&h->pAt, 6 * (int64_t)std::max(h->pAt_stride, 1)));
+  CK(alloc_zero(&h->pQ, 2 * (int64_t)h->ew_grid_n));
+  CK(alloc_zero(&h->scal_dev, SCAL_MAX));
+#undef CK
+  hipError_t e = hipHostMalloc((void **)&h->scal_host, sizeof(double) * SCAL_MAX * DIST_MAX_WORLD, hipHostMallocDefault);
+  if (e != hipSuccess) return fail((int)e, "hipHostMalloc failed");
+  e = hipEventCreate(&h->ev0); if (e == hipSuccess) e = hipEventCreate(&h->ev1);
+  if (e != hipSuccess) return fail((int)e, "hipEventCreate failed");
+  return 0;
+}
+
 int create_shard(pdhg_handle **out, int64_t m, int64_t n, int64_t nnz,
                  const int64_t *colptr, const int64_t *rowval, const double *nzval,
                  int index_base, const double *c, const double *b, const double *lb,
@@ -566,31 +599,7 @@ int create_shard(pdhg_handle **out, int64_t m, int64_t n, int64_t nnz,
 #define CK(expr) do { int _rc = (expr); if (_rc) { destroy_shard(h); return _rc; } } while (0)
   if (seg_cap > 0 && nnz > seg_cap) CK(build_segments(dev, h, m, n, nnz, colptr, rowval, nzval, index_base, seg_cap));   // 64-bit extents
   else CK(build_layout_pair(dev, h->remap, h->relaxed, m, n, nnz, colptr, rowval, nzval, index_base, &h->A, &h->At));
-  auto up = [&](double **dst, const double *src, int64_t len) -> int {
-    int r2 = alloc_zero(dst, len);
-    if (r2) return r2;
-    if (len > 0) { HIP_TRY(hipMemcpy(*dst, src, sizeof(double) * (size_t)len, hipMemcpyHostToDevice)); HIP_TRY(hipStreamSynchronize(nullptr)); }
-    return 0;
-  };
-  CK(up(&h->c, c, n)); CK(up(&h->b, b, m)); CK(up(&h->lb, lb, n)); CK(up(&h->ub, ub, n));
-  CK(alloc_zero(&h->x, n_alloc)); CK(alloc_zero(&h->x_next, n_alloc)); CK(alloc_zero(&h->xbar, n_alloc));
-  CK(alloc_zero(&h->y, m)); CK(alloc_zero(&h->y_next, m));
-  CK(alloc_zero(&h->aty, n_alloc + 1)); CK(alloc_zero(&h->aty_next, n_alloc + 1));
-  CK(alloc_zero(&h->sum_x, n)); CK(alloc_zero(&h->sum_y, m));
-  CK(alloc_zero(&h->tmp_n, n_alloc)); CK(alloc_zero(&h->tmp_m, m));
-  h->ew_grid_n = ew_grid(n); h->ew_grid_m = ew_grid(m); h->ew_grid_nm = ew_grid(std::max(n, m));
-  h->pAt_stride = std::max(h->At.slots(), h->ew_grid_n);
-  // block partials are double-double: hi parts, then lo parts
-  CK(alloc_zero(&h->pA, 2 * (int64_t)std::max(h->A.slots(), 1)));
-  CK(alloc_zero(&h->pAt, 6 * (int64_t)std::max(h->pAt_stride, 1)));
-  CK(alloc_zero(&h->pQ, 2 * (int64_t)h->ew_grid_n));
-  CK(alloc_zero(&h->scal_dev, SCAL_MAX));
-  {
-    hipError_t e = hipHostMalloc((void **)&h->scal_host, sizeof(double) * SCAL_MAX * DIST_MAX_WORLD, hipHostMallocDefault);
-    if (e != hipSuccess) { destroy_shard(h); return fail((int)e, "hipHostMalloc failed"); }
-    e = hipEventCreate(&h->ev0); if (e == hipSuccess) e = hipEventCreate(&h->ev1);
-    if (e != hipSuccess) { destroy_shard(h); return fail((int)e, "hipEventCreate failed"); }
-  }
+  CK(alloc_shard_vectors(h, c, b, lb, ub));
   CK(tune_tiled_variant(h, h->A, h->xbar, h->tmp_m));
   CK(tune_tiled_variant(h, h->At, h->y, h->tmp_n));
 #undef CK

@@ -75,11 +75,20 @@ class HipPdhgEngine:
                 ctypes.byref(h), *common, int(device_id),
                 ctypes.c_void_p(stream) if stream else None))
         self._h = h
+        self._upload_objective_matrix(objective_matrix)
+
+    @classmethod
+    def _wrap(cls, library, handle, m, n):
+        """An engine over an existing ``pdhg_handle`` of an m x n problem: no create call."""
+        self = cls.__new__(cls)
+        self._L, self._h, self.m, self.n = library, handle, int(m), int(n)
+        return self
+
+    def _upload_objective_matrix(self, objective_matrix):
         if objective_matrix is not None and objective_matrix.nnz > 0:
             Q = objective_matrix
             qc, qr, qv = _i(Q.indptr), _i(Q.indices), _d(Q.data)
-            _lib.check(self._L.pdhg_set_objective_matrix(
-                self._h, len(qv), _pi(qc), _pi(qr), _pd(qv), 0))
+            _lib.check(self._L.pdhg_set_objective_matrix(self._h, len(qv), _pi(qc), _pi(qr), _pd(qv), 0))
 
     @classmethod
     def from_row_shard(cls, m_global, row_bounds, constraint_rows, objective_vector, right_hand_side_rows,
@@ -90,32 +99,28 @@ class HipPdhgEngine:
         the global matrix as an (hi - lo) x n sparse matrix, ``right_hand_side_rows`` their
         right-hand sides -- plus the global n-vectors; ``num_equalities`` is global.  The handle
         behaves exactly like one from ``unique_id=, rank=, world=`` (global vector lengths)."""
-        self = cls.__new__(cls)
-        self._L = _lib.lib()
+        L = _lib.lib()
         A = constraint_rows.tocsc()
         bounds = _i(row_bounds)
         if bounds.shape != (world + 1,):
             raise ValueError("row_bounds must hold world + 1 entries")
         lo, hi = int(bounds[rank]), int(bounds[rank + 1])
-        self.m, self.n = int(m_global), int(A.shape[1])
+        m, n = int(m_global), int(A.shape[1])
         if A.shape[0] != hi - lo:
             raise ValueError("constraint_rows does not match row_bounds[rank]..row_bounds[rank+1]")
         colptr, rowval, nzval = _i(A.indptr), _i(A.indices), _d(A.data)
         c, b = _d(objective_vector), _d(right_hand_side_rows)
         lb, ub = _d(variable_lower_bound), _d(variable_upper_bound)
-        if c.shape != (self.n,) or lb.shape != (self.n,) or ub.shape != (self.n,) or b.shape != (hi - lo,):
+        if c.shape != (n,) or lb.shape != (n,) or ub.shape != (n,) or b.shape != (hi - lo,):
             raise ValueError("vector lengths do not match the row shard")
         h = ctypes.c_void_p()
         uid = ctypes.create_string_buffer(bytes(unique_id), _lib.UNIQUE_ID_BYTES)
-        _lib.check(self._L.pdhg_create_dist_rows(
-            ctypes.byref(h), self.m, self.n, _pi(bounds), len(nzval), _pi(colptr), _pi(rowval), _pd(nzval), 0,
+        _lib.check(L.pdhg_create_dist_rows(
+            ctypes.byref(h), m, n, _pi(bounds), len(nzval), _pi(colptr), _pi(rowval), _pd(nzval), 0,
             _pd(c), _pd(b), _pd(lb), _pd(ub), int(num_equalities), int(device_id),
             ctypes.c_void_p(stream) if stream else None, uid, int(rank), int(world)))
-        self._h = h
-        if objective_matrix is not None and objective_matrix.nnz > 0:
-            Q = objective_matrix
-            qc, qr, qv = _i(Q.indptr), _i(Q.indices), _d(Q.data)
-            _lib.check(self._L.pdhg_set_objective_matrix(self._h, len(qv), _pi(qc), _pi(qr), _pd(qv), 0))
+        self = cls._wrap(L, h, m, n)
+        self._upload_objective_matrix(objective_matrix)
         return self
 
     @staticmethod

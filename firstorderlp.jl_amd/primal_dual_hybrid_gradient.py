@@ -8,10 +8,27 @@ step-size rules of ``take_step`` (pdhg.jl:555-767), counters, and -- in
 """
 import math
 import os
+import time as _time
 from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
+import scipy.sparse as sp
+
+from .evaluation import (POINT_AVERAGE, POINT_CURRENT, DeviceEvaluator,
+                         HostEvaluator)
+from .iteration_stats_utils import print_to_screen_this_iteration
+from .preprocess import rescale_problem, validate
+from .quadratic_programming import (QuadraticProgrammingProblem, ScaledQpProblem,
+                                    is_linear_programming_problem)
+from .saddle_point import (RestartParameters, compute_new_primal_weight,
+                           create_last_restart_info, run_restart_scheme,
+                           select_initial_primal_weight,
+                           unscaled_saddle_point_output,
+                           update_objective_bound_estimates)
+from .solve_log import PointType, RestartChoice, TerminationReason
+from .termination import (TerminationCriteria, cached_quadratic_program_info,
+                          check_termination_criteria)
 
 
 # ---- step-size policy parameter structs (pdhg.jl:19-68) ----------------------
@@ -87,6 +104,24 @@ def julia_min(a, b):
     return a if a < b else b
 
 
+def adaptive_step_rule(raw, primal_weight, step_size, total_number_iterations, step_params):
+    """What the adaptive policy does with one trial's sums (pdhg.jl:691-729; ``adaptive_step_rule`` of
+    csrc/common.hpp is the same statements): (accept, numerical_error, next step size).
+    ``total_number_iterations`` counts this trial."""
+    interaction, movement = interaction_and_movement(raw, primal_weight)
+    if movement == 0.0:
+        # The algorithm will terminate at the beginning of the next iteration
+        return False, True, step_size
+    if interaction > 0:
+        step_size_limit = movement / interaction
+    else:
+        step_size_limit = math.inf
+    k1 = float(total_number_iterations + 1)
+    first_term = (1 - k1 ** (-step_params.reduction_exponent)) * step_size_limit
+    second_term = (1 + k1 ** (-step_params.growth_exponent)) * step_size
+    return step_size <= step_size_limit, False, julia_min(first_term, second_term)
+
+
 def take_step_adaptive(step_params, solver_state):
     """take_step(::AdaptiveStepsizeParams, ...)  pdhg.jl:653-731.
 
@@ -109,26 +144,16 @@ def take_step_adaptive(step_params, solver_state):
     while not done:
         solver_state.total_number_iterations += 1
         raw = eng.trial_step(step_size, solver_state.primal_weight, 1.0)
-        interaction, movement = interaction_and_movement(
-            raw, solver_state.primal_weight)
         solver_state.cumulative_kkt_passes += 1
-        if movement == 0.0:
-            # The algorithm will terminate at the beginning of the next iteration
+        done, numerical_error, step_size = adaptive_step_rule(
+            raw, solver_state.primal_weight, step_size, solver_state.total_number_iterations, step_params)
+        if numerical_error:
             solver_state.numerical_error = True
             break
-        if interaction > 0:
-            step_size_limit = movement / interaction
-        else:
-            step_size_limit = math.inf
-        if step_size <= step_size_limit:
+        if done:
             # update_solution_in_solver_state: weight = solver_state.step_size,
             # the value on entry to take_step (pdhg.jl:512)
             eng.accept(solver_state.step_size)
-            done = True
-        k1 = float(solver_state.total_number_iterations + 1)
-        first_term = (1 - k1 ** (-step_params.reduction_exponent)) * step_size_limit
-        second_term = (1 + k1 ** (-step_params.growth_exponent)) * step_size
-        step_size = julia_min(first_term, second_term)
     solver_state.step_size = step_size
 
 
@@ -220,23 +245,6 @@ def take_steps(step_params, solver_state, n_steps, is_lp=True):
 # optimize(): the reference's outer loop (pdhg.jl:782-1049) on the host, with
 # every n-/m-length vector operation behind ``engine``.
 # ==============================================================================
-import os
-import time as _time
-
-from .evaluation import (POINT_AVERAGE, POINT_CURRENT, DeviceEvaluator,
-                         HostEvaluator)
-from .iteration_stats_utils import print_to_screen_this_iteration
-from .preprocess import rescale_problem, validate
-from .quadratic_programming import is_linear_programming_problem
-from .saddle_point import (RestartParameters, compute_new_primal_weight,
-                           create_last_restart_info, run_restart_scheme,
-                           select_initial_primal_weight,
-                           unscaled_saddle_point_output,
-                           update_objective_bound_estimates)
-from .solve_log import PointType, RestartChoice, TerminationReason
-from .termination import (TerminationCriteria, cached_quadratic_program_info,
-                          check_termination_criteria)
-
 
 @dataclass
 class PdhgParameters:
@@ -336,142 +344,141 @@ def _default_engine_factory(problem):
     return HipPdhgEngine.from_problem(problem)
 
 
-def optimize(params, original_problem, engine_factory=None):
-    """``optimize(params::PdhgParameters, original_problem)`` -- pdhg.jl:782-1049.
-
-    ``engine_factory(scaled_qp) -> engine`` builds the device state; the
-    default is the HIP engine on the current GPU and there is no CPU fallback.
-    Returns a ``SaddlePointOutput``.  The engine (device memory) is released on
-    every exit path, exceptions included."""
-    created = []
-    try:
-        return _optimize(params, original_problem, engine_factory, created)
-    finally:
-        for eng in created:
-            if hasattr(eng, "close"):
-                eng.close()
+_default_engine_factory.takes_original_problem = True
 
 
-def _optimize(params, original_problem, engine_factory, created):
-    validate(original_problem)
-    qp_cache = cached_quadratic_program_info(original_problem)
+def _check_inputs(params, problems):
+    for problem in problems:
+        validate(problem)
     if params.primal_importance <= 0 or not math.isfinite(params.primal_importance):
         raise ValueError("primal_importance must be positive and finite")
-    is_lp_original = is_linear_programming_problem(original_problem)
-    engine = None
-    device_rescale = engine_factory is None or getattr(engine_factory, "takes_original_problem", False)
-    if device_rescale and os.environ.get("PDHG_HOST_RESCALE", "0") != "1":
-        # Product path: upload the ORIGINAL problem and rescale on the device
-        # (pdhg_rescale); only the n-/m-length vectors come back.  The scaled
-        # constraint (and objective) matrix lives on the device only.
-        from .quadratic_programming import QuadraticProgrammingProblem, ScaledQpProblem
-        import scipy.sparse as _sp
-        engine = (engine_factory or _default_engine_factory)(original_problem)
-        created.append(engine)
-        constraint_rescaling, variable_rescaling = engine.rescale(
-            params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
-        c_s, b_s, lb_s, ub_s = engine.get_problem_vectors()
-        m0, n0 = original_problem.constraint_matrix.shape
-        problem = QuadraticProgrammingProblem(
-            lb_s, ub_s, _sp.csc_matrix((n0, n0)), c_s, original_problem.objective_constant,
-            _sp.csc_matrix((m0, n0)),      # the scaled matrix lives on the device only
-            b_s, original_problem.num_equalities)
-        scaled_problem = ScaledQpProblem(original_problem, problem, constraint_rescaling,
-                                         variable_rescaling)
-        matrix_max_abs = engine.matrix_max_abs()
-    else:
-        scaled_problem = rescale_problem(params.l_inf_ruiz_iterations,
-                                         params.l2_norm_rescaling,
-                                         params.pock_chambolle_alpha,
-                                         params.verbosity, original_problem)
-        problem = scaled_problem.scaled_qp
-        data = problem.constraint_matrix.data
-        matrix_max_abs = float(np.max(np.abs(data))) if len(data) else 0.0   # norm(A, Inf) on a sparse matrix
-    primal_size = problem.num_variables
-    dual_size = problem.num_constraints
 
-    if engine is None:
-        engine = (engine_factory or _default_engine_factory)(problem)
-        created.append(engine)
-    ops = EngineOps(engine, problem)
-    original_ops = UnscaledEngineOps(engine, scaled_problem)
-    is_lp = is_lp_original       # (the host copy of a device-rescaled problem carries no matrices)
-    solver_state = PdhgSolverState(engine)   # zeros(...) state, pdhg.jl:805-819
-    policy = params.step_size_policy_params
 
-    def inv_max_abs():
-        return math.inf if matrix_max_abs == 0.0 else 1.0 / matrix_max_abs
+def _rescales_on_device(factory):
+    """A factory whose ``takes_original_problem`` is true receives the ORIGINAL problem(s) and what it builds
+    rescales on the device (the product path); PDHG_HOST_RESCALE=1 turns that off."""
+    return getattr(factory, "takes_original_problem", False) and os.environ.get("PDHG_HOST_RESCALE", "0") != "1"
 
-    if isinstance(policy, AdaptiveStepsizeParams):
-        solver_state.cumulative_kkt_passes += 0.5
-        solver_state.step_size = inv_max_abs()
-    elif isinstance(policy, MalitskyPockStepsizeParameters):
-        solver_state.cumulative_kkt_passes += 0.5
-        solver_state.step_size = inv_max_abs()
-        solver_state.ratio_step_sizes = 1.0
-    else:
-        desired_relative_error = 0.2
-        maximum_singular_value, number_of_power_iterations = \
-            estimate_maximum_singular_value(ops, primal_size,
-                                            probability_of_failure=0.001,
-                                            desired_relative_error=desired_relative_error)
-        solver_state.step_size = (1 - desired_relative_error) / maximum_singular_value
-        solver_state.cumulative_kkt_passes += number_of_power_iterations
 
-    KKT_PASSES_PER_TERMINATION_EVALUATION = 2.0
+def _device_scaled_problem(original_problem, engine, constraint_rescaling, variable_rescaling):
+    """The host's ``ScaledQpProblem`` of an engine that was rescaled on the device (``rescale``): only the
+    n-/m-length vectors come back; the scaled constraint (and objective) matrix lives on the device only."""
+    c_s, b_s, lb_s, ub_s = engine.get_problem_vectors()
+    m0, n0 = original_problem.constraint_matrix.shape
+    problem = QuadraticProgrammingProblem(
+        lb_s, ub_s, sp.csc_matrix((n0, n0)), c_s, original_problem.objective_constant,
+        sp.csc_matrix((m0, n0)), b_s, original_problem.num_equalities)
+    return ScaledQpProblem(original_problem, problem, constraint_rescaling, variable_rescaling)
 
-    if params.scale_invariant_initial_primal_weight:
-        solver_state.primal_weight = select_initial_primal_weight(
-            problem, np.ones(primal_size), np.ones(dual_size),
-            params.primal_importance, params.verbosity)
-    else:
-        solver_state.primal_weight = params.primal_importance
 
-    primal_weight_update_smoothing = params.restart_params.primal_weight_update_smoothing
-    iteration_stats = []
-    start_time = _time.time()
-    time_spent_doing_basic_algorithm = 0.0
+def _host_scaled_problem(params, original_problem):
+    """``rescale_problem`` on the host: (scaled problem, norm(A, Inf) of its sparse constraint matrix)."""
+    scaled_problem = rescale_problem(params.l_inf_ruiz_iterations, params.l2_norm_rescaling,
+                                     params.pock_chambolle_alpha, params.verbosity, original_problem)
+    data = scaled_problem.scaled_qp.constraint_matrix.data
+    return scaled_problem, (float(np.max(np.abs(data))) if len(data) else 0.0)
 
-    if getattr(engine, "supports_device_evaluation", False):
-        ev = DeviceEvaluator(engine, scaled_problem, qp_cache)
-    else:
-        ev = HostEvaluator(engine, scaled_problem, qp_cache, ops, original_ops)
-    last_restart_info = create_last_restart_info()
 
-    termination_criteria = params.termination_criteria
-    iteration_limit = termination_criteria.iteration_limit
-    termination_evaluation_frequency = params.termination_evaluation_frequency
-    solver_state.numerical_error = False
+CONSTANT_STEP_DESIRED_RELATIVE_ERROR = 0.2
+KKT_PASSES_PER_TERMINATION_EVALUATION = 2.0
 
-    iteration = 0
-    while True:
-        iteration += 1
+
+def _constant_step_estimate(solve):
+    """The constant policy's power method on one solve's operators (pdhg.jl:829-838): what ``_Solve.start`` takes."""
+    return estimate_maximum_singular_value(solve.ops, solve.problem.num_variables, probability_of_failure=0.001,
+                                           desired_relative_error=CONSTANT_STEP_DESIRED_RELATIVE_ERROR)
+
+
+class _Solve:
+    """One problem's host-side solve: the state of the reference's ``optimize`` (pdhg.jl:782-1049) and what it does
+    at an evaluation.  ``optimize`` drives one of these, ``batch.optimize_batch`` one per member; the caller takes
+    the steps in between."""
+
+    def __init__(self, params, original_problem, scaled_problem, engine, matrix_max_abs):
+        self.params = params
+        self.scaled_problem = scaled_problem
+        self.problem = scaled_problem.scaled_qp
+        self.engine = engine
+        self.matrix_max_abs = matrix_max_abs
+        # (from the original problem: the host copy of a device-rescaled problem carries no matrices)
+        self.is_lp = is_linear_programming_problem(original_problem)
+        self.qp_cache = cached_quadratic_program_info(original_problem)
+        self.ops = EngineOps(engine, self.problem)
+        self.original_ops = UnscaledEngineOps(engine, scaled_problem)
+        self.state = PdhgSolverState(engine)   # zeros(...) state, pdhg.jl:805-819
+        self.last_restart_info = create_last_restart_info()
+        self.iteration = 0
+        self.iteration_stats = []
+        self.time_spent_doing_basic_algorithm = 0.0
+        self.output = None
+
+    def start(self, singular_value_estimate=None):
+        """Initial step size and primal weight, the evaluator, the clock (pdhg.jl:821-860).  The constant policy takes
+        ``singular_value_estimate`` = (maximum_singular_value, number_of_power_iterations) from the caller
+        (``_constant_step_estimate``: it depends on the matrix only)."""
+        params, st, problem = self.params, self.state, self.problem
+        policy = params.step_size_policy_params
+        inv_max_abs = math.inf if self.matrix_max_abs == 0.0 else 1.0 / self.matrix_max_abs
+        if isinstance(policy, AdaptiveStepsizeParams):
+            st.cumulative_kkt_passes += 0.5
+            st.step_size = inv_max_abs
+        elif isinstance(policy, MalitskyPockStepsizeParameters):
+            st.cumulative_kkt_passes += 0.5
+            st.step_size = inv_max_abs
+            st.ratio_step_sizes = 1.0
+        else:
+            maximum_singular_value, number_of_power_iterations = singular_value_estimate
+            st.step_size = (1 - CONSTANT_STEP_DESIRED_RELATIVE_ERROR) / maximum_singular_value
+            st.cumulative_kkt_passes += number_of_power_iterations
+
+        if params.scale_invariant_initial_primal_weight:
+            st.primal_weight = select_initial_primal_weight(
+                problem, np.ones(problem.num_variables), np.ones(problem.num_constraints),
+                params.primal_importance, params.verbosity)
+        else:
+            st.primal_weight = params.primal_importance
+
+        self.start_time = _time.time()
+        if getattr(self.engine, "supports_device_evaluation", False):
+            self.ev = DeviceEvaluator(self.engine, self.scaled_problem, self.qp_cache)
+        else:
+            self.ev = HostEvaluator(self.engine, self.scaled_problem, self.qp_cache, self.ops, self.original_ops)
+        st.numerical_error = False
+
+    def evaluate(self):
+        """The top of one iteration of optimize's loop (pdhg.jl:862-1023).  Returns the number of take_steps to
+        run before the next evaluation, or 0 once the solve has terminated (``self.output`` set)."""
+        params, st, ev = self.params, self.state, self.ev
+        termination_criteria = params.termination_criteria
+        iteration_limit = termination_criteria.iteration_limit
+        termination_evaluation_frequency = params.termination_evaluation_frequency
+        self.iteration += 1
+        iteration = self.iteration
         if ((iteration - 1) % termination_evaluation_frequency == 0 or
                 iteration == iteration_limit + 1 or iteration <= 10 or
-                solver_state.numerical_error):
-            solver_state.cumulative_kkt_passes += KKT_PASSES_PER_TERMINATION_EVALUATION
-            count_x, count_y, _, _ = engine.average_info()
-            if solver_state.numerical_error or count_x == 0 or count_y == 0:
+                st.numerical_error):
+            st.cumulative_kkt_passes += KKT_PASSES_PER_TERMINATION_EVALUATION
+            count_x, count_y, _, _ = self.engine.average_info()
+            if st.numerical_error or count_x == 0 or count_y == 0:
                 avg_point = POINT_CURRENT
             else:
                 avg_point = POINT_AVERAGE
 
             current_iteration_stats = ev.iteration_stats(
                 avg_point, termination_criteria, params.record_iteration_stats, iteration,
-                _time.time() - start_time, solver_state.cumulative_kkt_passes,
-                solver_state.step_size, solver_state.primal_weight,
-                PointType.POINT_TYPE_AVERAGE_ITERATE)
+                _time.time() - self.start_time, st.cumulative_kkt_passes,
+                st.step_size, st.primal_weight, PointType.POINT_TYPE_AVERAGE_ITERATE)
             method_specific_stats = current_iteration_stats.method_specific_stats
             method_specific_stats["time_spent_doing_basic_algorithm"] = \
-                time_spent_doing_basic_algorithm
+                self.time_spent_doing_basic_algorithm
 
             # define_norms (pdhg.jl:265-277): uniform weights, kept as scalars
             with np.errstate(divide="ignore"):
-                primal_weight_norm = float(np.float64(1) / solver_state.step_size * solver_state.primal_weight)
-                dual_weight_norm = float(np.float64(1) / solver_state.step_size / solver_state.primal_weight)
+                primal_weight_norm = float(np.float64(1) / st.step_size * st.primal_weight)
+                dual_weight_norm = float(np.float64(1) / st.step_size / st.primal_weight)
             termination_reason = check_termination_criteria(
-                termination_criteria, qp_cache, current_iteration_stats)
-            if solver_state.numerical_error and termination_reason is False:
+                termination_criteria, self.qp_cache, current_iteration_stats)
+            if st.numerical_error and termination_reason is False:
                 termination_reason = TerminationReason.TERMINATION_REASON_NUMERICAL_ERROR
             # update_objective_bound_estimates (pdhg.jl:938-945) fills three entries of method_specific_stats that are
             # only ever read from KEPT stats (solve_log; the final log, saddle_point.jl:961-993) -- neither the
@@ -480,11 +487,8 @@ def _optimize(params, original_problem, engine_factory, created):
             # the reference's (both functions only read the state, so their order does not matter).
             if params.record_iteration_stats or termination_reason is not False:
                 update_objective_bound_estimates(
-                    current_iteration_stats.method_specific_stats, ev, avg_point,
-                    primal_weight_norm, dual_weight_norm)
-
-            if params.record_iteration_stats or termination_reason is not False:
-                iteration_stats.append(current_iteration_stats)
+                    method_specific_stats, ev, avg_point, primal_weight_norm, dual_weight_norm)
+                self.iteration_stats.append(current_iteration_stats)
 
             if print_to_screen_this_iteration(termination_reason, iteration, params.verbosity,
                                               termination_evaluation_frequency):
@@ -496,21 +500,21 @@ def _optimize(params, original_problem, engine_factory, created):
                     print(f"Terminated after {iteration - 1} iterations: "
                           f"{termination_reason.name}")
                 avg_primal_solution, avg_dual_solution = ev.solution(avg_point)
-                out = unscaled_saddle_point_output(
-                    scaled_problem, avg_primal_solution, avg_dual_solution,
-                    termination_reason, iteration - 1, iteration_stats)
-                return out
+                self.output = unscaled_saddle_point_output(
+                    self.scaled_problem, avg_primal_solution, avg_dual_solution,
+                    termination_reason, iteration - 1, self.iteration_stats)
+                return 0
 
             current_iteration_stats.restart_used = run_restart_scheme(
-                ev, last_restart_info, iteration - 1, primal_weight_norm,
-                dual_weight_norm, solver_state.primal_weight, params.verbosity,
+                ev, self.last_restart_info, iteration - 1, primal_weight_norm,
+                dual_weight_norm, st.primal_weight, params.verbosity,
                 params.restart_params)
 
             if current_iteration_stats.restart_used != RestartChoice.RESTART_CHOICE_NO_RESTART:
-                solver_state.primal_weight = compute_new_primal_weight(
-                    last_restart_info, solver_state.primal_weight,
-                    primal_weight_update_smoothing, params.verbosity)
-                solver_state.ratio_step_sizes = 1.0
+                st.primal_weight = compute_new_primal_weight(
+                    self.last_restart_info, st.primal_weight,
+                    params.restart_params.primal_weight_update_smoothing, params.verbosity)
+                st.ratio_step_sizes = 1.0
             # RESTART_TO_AVERAGE: A'y was recomputed inside
             # engine.restart_to_average() (pdhg.jl:1018-1022).
 
@@ -522,11 +526,49 @@ def _optimize(params, original_problem, engine_factory, created):
             next_evaluation = iteration + 1
         if iteration < iteration_limit + 1:
             next_evaluation = min(next_evaluation, iteration_limit + 1)
-        batch = next_evaluation - iteration
-        time_spent_doing_basic_algorithm_checkpoint = _time.time()
-        iteration += take_steps(policy, solver_state, batch, is_lp) - 1
-        time_spent_doing_basic_algorithm += \
-            _time.time() - time_spent_doing_basic_algorithm_checkpoint
+        return next_evaluation - iteration
+
+    def stepped(self, steps_taken, seconds):
+        """The caller took ``steps_taken`` take_steps since ``evaluate`` (fewer than asked after a numerical error)."""
+        self.iteration += steps_taken - 1
+        self.time_spent_doing_basic_algorithm += seconds
+
+
+def optimize(params, original_problem, engine_factory=None):
+    """``optimize(params::PdhgParameters, original_problem)`` -- pdhg.jl:782-1049.
+
+    ``engine_factory(problem) -> engine`` builds the device state; the default is the HIP engine on the current GPU
+    and there is no CPU fallback.  A factory whose ``takes_original_problem`` is true (the default is one) receives
+    the original problem and rescales it on the device, any other one the host-rescaled problem.
+    Returns a ``SaddlePointOutput``.  The engine (device memory) is released on every exit path, exceptions
+    included."""
+    _check_inputs(params, [original_problem])
+    factory = engine_factory or _default_engine_factory
+    engine = None
+    try:
+        if _rescales_on_device(factory):
+            engine = factory(original_problem)
+            constraint_rescaling, variable_rescaling = engine.rescale(
+                params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
+            scaled_problem = _device_scaled_problem(original_problem, engine, constraint_rescaling,
+                                                    variable_rescaling)
+            matrix_max_abs = engine.matrix_max_abs()
+        else:
+            scaled_problem, matrix_max_abs = _host_scaled_problem(params, original_problem)
+            engine = factory(scaled_problem.scaled_qp)
+        solve = _Solve(params, original_problem, scaled_problem, engine, matrix_max_abs)
+        policy = params.step_size_policy_params
+        solve.start(_constant_step_estimate(solve) if isinstance(policy, ConstantStepsizeParams) else None)
+        while True:
+            steps = solve.evaluate()
+            if steps == 0:
+                return solve.output
+            time_spent_doing_basic_algorithm_checkpoint = _time.time()
+            steps_taken = take_steps(policy, solve.state, steps, solve.is_lp)
+            solve.stepped(steps_taken, _time.time() - time_spent_doing_basic_algorithm_checkpoint)
+    finally:
+        if engine is not None and hasattr(engine, "close"):
+            engine.close()
 
 
 def _display_iteration_stats(stats):

@@ -147,3 +147,27 @@ def test_take_steps_host_loop_stops_on_numerical_error():
     assert take_steps(ConstantStepsizeParams(), st, 7) == 7 and Eng.calls == 7
     st.numerical_error = True
     assert take_steps(ConstantStepsizeParams(), st, 7) == 1
+
+
+def test_adaptive_step_rule_by_hand():
+    """adaptive_step_rule against pdhg.jl:691-729 worked by hand.  raw = [dx.dA'y, |dx|^2, |dy|^2, |dA'y|^2, 0.5 dx'Qdx];
+    interaction = |raw[0]| + |raw[4]|, movement = 0.5 w |dx|^2 + (0.5 / w) |dy|^2 (pdhg.jl:527-549).  Exponents 1 and
+    2 with total_number_iterations = 3 make the two factors exact: 1 - 4^-1 = 0.75 and 1 + 4^-2 = 1.0625."""
+    import math
+    from firstorderlp_jl_amd.primal_dual_hybrid_gradient import AdaptiveStepsizeParams, adaptive_step_rule
+    sp_ = AdaptiveStepsizeParams(1.0, 2.0)
+    # zero movement (:691-695): numerical error, nothing accepted, the step size stays
+    assert adaptive_step_rule([3.0, 0.0, 0.0, 1.0, 0.0], 2.0, 0.5, 3, sp_) == (False, True, 0.5)
+    # movement = 0.5 * 2 * 4 + 0.25 * 16 = 8, interaction = |-3| + 1 = 4: limit 2 < step 2.5 rejects (:703);
+    # next = min(0.75 * 2, 1.0625 * 2.5) = 1.5 (:714-728)
+    assert adaptive_step_rule([-3.0, 4.0, 16.0, 9.0, 1.0], 2.0, 2.5, 3, sp_) == (False, False, 1.5)
+    # the same sums at step 2 == limit: accepted (<=); next = min(1.5, 2.125) = 1.5
+    assert adaptive_step_rule([-3.0, 4.0, 16.0, 9.0, 1.0], 2.0, 2.0, 3, sp_) == (True, False, 1.5)
+    # interaction 0 (:697-701): limit Inf, accepted; next = min(0.75 * Inf, 1.0625 * 2.5) = 2.65625
+    assert adaptive_step_rule([0.0, 4.0, 16.0, 9.0, 0.0], 2.0, 2.5, 3, sp_) == (True, False, 2.65625)
+    # NaN sums: movement == 0.0 and interaction > 0 are both false, so the limit is Inf and the trial is accepted
+    accept, err, nxt = adaptive_step_rule([math.nan] * 5, 2.0, 2.5, 3, sp_)
+    assert (accept, err, nxt) == (True, False, 2.65625)
+    # NaN movement over a positive interaction: the limit is NaN, `step <= NaN` rejects and Julia's min gives NaN (:728)
+    accept, err, nxt = adaptive_step_rule([-3.0, math.nan, 16.0, 9.0, 1.0], 2.0, 2.5, 3, sp_)
+    assert (accept, err) == (False, False) and math.isnan(nxt)
