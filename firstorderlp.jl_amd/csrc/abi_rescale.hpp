@@ -73,7 +73,7 @@ static int apply_scaling(pdhg_handle *h, RescaleTmp &t) {
     // the column-chunk layouts of a shard group (dist.hpp) index their columns INTO THE CHUNK: the column factors in chunk
     // layout (xchunk is free between trials: the next trial packs xbar into it again)
     DistGroup &g = *h->grp;
-    int rc2 = launch_chunk_pack(g, h, t.inv_d, h->xchunk, 0, g.world, h->n, h->stream);
+    int rc2 = launch_chunk_pack(g, t.inv_d, h->xchunk, 0, g.world, h->n, h->stream);
     if (rc2) return rc2;
     const int64_t W = (int64_t)g.world * g.ag_sub;
     for (size_t c = 0; c < h->Achunk.size(); ++c) scale_one(h->Achunk[c], t.inv_e, h->xchunk + (int64_t)c * W, 0);

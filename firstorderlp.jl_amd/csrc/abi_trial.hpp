@@ -27,109 +27,154 @@ static int trial_dual_single(pdhg_handle *h, double step_size, double primal_wei
   return 0;
 }
 
-// One shard's whole trial, issued by that shard's own host thread (ShardPool): the same
-// launches, in the same order, as trial_dual_group issues for it from the calling thread.
+// ---- the trial of a row-partitioned group, launch by launch ----------------------------------------------------------
+// One text for both issuers (dist.hpp, "who issues"): the same launches, event calls and collectives in the same order
+// per stream, whether the calling thread walks all local shards or every shard's own pool thread issues its share.
 struct TrialArgs {
   double step_size, primal_weight, theta;
   bool primal;      // K1+K2 first (pdhg_trial_step); false: xbar only (pdhg_trial_dual)
 };
-static int trial_shard_mt(DistGroup &g, pdhg_handle *s, int i, const TrialArgs &a, double *t_issued) {
-  HIP_TRY(hipSetDevice(s->device));
+
+static int group_trial_primal(const Issue &I, const TrialArgs &a) {
   int rc;
-  if (a.primal) { if ((rc = launch_primal(s, a.step_size / a.primal_weight, a.theta, true))) return rc; }
-  else if ((rc = launch_xbar(s, a.theta))) return rc;
-  const double sigma = a.primal_weight * a.step_size;
-  if (g.ag_chunks > 1 && !s->has_q) {
-    // xbar chunk by chunk, A_p xbar as one pass per chunk (see trial_dual_group)
-    if (g.backend == COMM_RCCL) {
-      // the owned slice into the chunk layout, then one all-gather per chunk on the comm stream; ag_mode 2: the passes wait
-      // for the LAST chunk (one all-gather's worth of waiting: nothing overlapped, the same bits)
-      if ((rc = launch_chunk_pack(g, s, s->xbar, s->xchunk, s->rank, s->rank + 1, s->n_alloc, s->stream))) return rc;
-      HIP_TRY(hipEventRecord(s->ev_xbar, s->stream));
-      for (int c = 0; c < g.ag_chunks; ++c)
-        if ((rc = mt_all_gather_chunk(g, s, i, c))) return rc;
-      if (g.ag_mode != 1) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_ag[(size_t)g.ag_chunks - 1], 0));
-      if ((rc = launch_dual_chunked(s, sigma, g.ag_mode == 1))) return rc;
-    } else {
-      // peer back end: the ordinary all-gather, then the whole vector into the chunk layout
-      if ((rc = mt_all_gather(g, s, i, [](pdhg_handle *q) { return q->xbar; }, g.S))) return rc;
-      if ((rc = launch_chunk_pack(g, s, s->xbar, s->xchunk, 0, g.world, s->n_alloc, s->stream))) return rc;
-      if ((rc = launch_dual_chunked(s, sigma, false))) return rc;
-    }
-  } else {
-    if ((rc = mt_all_gather(g, s, i, [](pdhg_handle *q) { return q->xbar; }, g.S))) return rc;
-    if (s->has_q && (rc = mt_all_gather(g, s, i, [](pdhg_handle *q) { return q->x_next; }, g.S))) return rc;
-    if ((rc = launch_dual(s, sigma))) return rc;
+  FOR_ISSUED(I, s, i) {
+    if (a.primal) { if ((rc = launch_primal(s, a.step_size / a.primal_weight, a.theta, true))) return rc; }
+    else if ((rc = launch_xbar(s, a.theta))) return rc;
   }
-  if (!g.overlap) {
-    if ((rc = launch_aty_plain(s, s->y_next, s->aty_next))) return rc;
-    if ((rc = mt_reduce_scatter(g, s, i, [](pdhg_handle *q) { return q->aty_next; }, g.S))) return rc;
-  } else {
-    // see trial_dual_group: the product in residency rounds, slice k reduced as soon as its rows are complete
-    const char *rw_env = dev_env("PDHG_DIST_ROUND_WGS");
-    const int round_wgs = rw_env ? std::max(1, atoi(rw_env)) : 256 * 2;
-    const CsrDev &T = s->At;
-    int issued = 0, next_wg = 0;
-    for (int k = 0; k < g.world; ++k) {
-      const int64_t need = std::min<int64_t>(s->n, (int64_t)(k + 1) * g.S);
-      if (!T.tiled) {
-        if (!issued) { if ((rc = launch_aty_plain(s, s->y_next, s->aty_next))) return rc; issued = 1; }
-      } else {
-        while (next_wg < T.grid || !issued) {
-          const int g0 = next_wg;
-          const bool covered = g0 >= T.grid || (int64_t)T.wg_first_row[(size_t)g0] >= need;
-          if (covered && issued) break;
-          int g1 = std::min(T.grid, g0 + round_wgs);
-          if (T.grid - g1 < round_wgs / 2) g1 = T.grid;
-          if ((rc = launch_spmv_plain_part(s, T, s->y_next, s->aty_next, g0, g1, !issued))) return rc;
-          issued = 1;
-          next_wg = g1;
-        }
-      }
-      HIP_TRY(hipEventRecord(s->ev_part[(size_t)k], s->stream));
-      if ((rc = mt_reduce_slice_async(g, s, i, [](pdhg_handle *q) { return q->aty_next; }, g.S, k))) return rc;
-    }
-    if ((rc = mt_join_comm(g, s, i))) return rc;
-  }
-  {
-    const int64_t o = s->clo;
-    hipLaunchKernelGGL(interaction_kernel, dim3(ew_grid(s->cn)), dim3(TPB), 0, s->stream, (int)s->cn, s->x + o,
-                       s->x_next + o, s->aty + o, s->aty_next + o, s->pAt, s->pAt_stride);
-    HIP_TRY(hipGetLastError());
-  }
-  int qcount = 0;
-  if ((rc = launch_q_interaction(s, &qcount))) return rc;
-  {
-    const bool chunked = g.ag_chunks > 1 && !s->has_q;
-    if ((rc = launch_final(s, s->pAt, ew_grid(s->cn), s->pAt_stride, s->pA, chunked ? dual_chunk_slots(s) : s->A.slots(), qcount, false,
-                           chunked ? dual_chunk_slots(s) : -1))) return rc;
-  }
-  HIP_TRY(hipMemcpyAsync(s->scal_host, s->scal_dev, sizeof(double) * 5, hipMemcpyDeviceToHost, s->stream));
-  *t_issued = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  HIP_TRY(hipStreamSynchronize(s->stream));
   return 0;
 }
 
-static int trial_group_mt(const Shards &L, const TrialArgs &a, double out[5]) {
-  DistGroup &g = *L.g;
-  const double t0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  std::vector<double> issued((size_t)L.count, t0);
-  int rc = g.pool->run([&](int i) { return trial_shard_mt(g, L.p[i], i, a, &issued[(size_t)i]); });
-  if (rc) return rc;
-  const double t2 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  double t1 = t0;
-  for (double v : issued) t1 = std::max(t1, v);
-  g.t_issue += t1 - t0; g.t_wait += t2 - t1; g.n_trials += 1;
-  // the shards' scalars, added in rank order ([4], dx'Q dx, is replicated: maxed) -- as combine_scalars does
-  for (int q = 0; q < 5; ++q) {
-    double v = L.p[0]->scal_host[q];
-    for (int i = 1; i < L.count; ++i) {
-      const double t = L.p[i]->scal_host[q];
-      v = (q < 4) ? v + t : std::fmax(v, t);
+// t_p = A_p' y'_p in parts: a shard whose A_p' uses the tiled layout launches it one residency
+// round at a time (256 CUs x 2 workgroups: a smaller launch would idle CUs for the whole
+// sweep); as soon as the rows of slice k are complete, slice k is reduced to rank k on
+// the comm stream while the next round computes.  The sequence of collectives (slice
+// 0, 1, ..., P-1) is the same on every rank however the local product is cut: the reduction of slice k is called
+// once per slice by every issuer whatever its shard's layout (on the peer back end it holds a meeting point).
+static int group_aty_by_slices(const Issue &I) {
+  DistGroup &g = I.g;
+  const char *rw_env = dev_env("PDHG_DIST_ROUND_WGS");            // tests use a finer granule on small problems
+  const int round_wgs = rw_env ? std::max(1, atoi(rw_env)) : 256 * 2;
+  std::vector<int> next_wg(g.sh.size(), -1);                        // first workgroup not launched yet; -1: nothing issued yet
+  int rc;
+  for (int k = 0; k < g.world; ++k) {
+    FOR_ISSUED(I, s, i) {                                           // the shard advances until slice k is complete on it
+      const CsrDev &T = s->At;
+      int &nw = next_wg[(size_t)i];
+      const int64_t need = std::min<int64_t>(s->n, (int64_t)(k + 1) * g.S);   // rows [0, need) must be done
+      if (!T.tiled) {
+        if (nw < 0) { if ((rc = launch_aty_plain(s, s->y_next, s->aty_next))) return rc; nw = 0; }
+      } else {
+        // (the first round is launched whatever it covers: it clears the output, also when the grid is empty)
+        while (nw < 0 || (nw < T.grid && (int64_t)T.wg_first_row[(size_t)nw] < need)) {
+          const int g0 = std::max(nw, 0);
+          int g1 = std::min(T.grid, g0 + round_wgs);
+          if (T.grid - g1 < round_wgs / 2) g1 = T.grid;       // no runt round at the end
+          ProfScope ps(s, PDHG_K_SPMV_ATY);
+          if ((rc = launch_spmv_plain_part(s, T, s->y_next, s->aty_next, g0, g1, nw < 0))) return rc;
+          nw = g1;
+        }
+      }
+      HIP_TRY(hipEventRecord(s->ev_part[(size_t)k], s->stream));
     }
-    out[q] = v;
+    if ((rc = dist_reduce_slice_async(I, [](pdhg_handle *s) { return s->aty_next; }, g.S, k))) return rc;
   }
-  out[4] *= 0.5;
+  ProfScope ps(g.sh[(size_t)I.lo], PDHG_K_REDUCE_SCATTER);     // what is left of the exchange after the product
+  return dist_join_comm(I);
+}
+
+// The dual half: xbar's owned slices are ready; everything the trial queues on the issued shards from there up to the
+// second-stage reduction that leaves every shard's five sums in its scal_dev.
+static int group_trial_dual(const Issue &I, const TrialArgs &a) {
+  DistGroup &g = I.g;
+  pdhg_handle *lead = g.sh[(size_t)I.lo];
+  const double sigma = a.primal_weight * a.step_size;
+  int rc;
+  // The all-gather of xbar beside A_p xbar (DistGroup::ag_chunks; SURVEY 8e(ii), pdhg.jl:472-494): xbar travels in column
+  // chunks on the comm streams -- chunk c = sub-range c of every rank's slice, so that every link carries a part of every
+  // chunk -- and A_p xbar is one pass per chunk, pass c waiting for chunk c alone while chunk c + 1 is on the links.
+  // ag_mode 2 (and the peer back end): the same passes behind one all-gather -- the same bits, nothing overlapped.
+  const bool chunked = g.ag_chunks > 1 && !lead->has_q;
+  const bool chunks_on_comm = chunked && g.ag_mode == 1 && g.backend == COMM_RCCL;
+  {
+    ProfScope ps(lead, PDHG_K_ALLGATHER);
+    if (chunked && g.backend == COMM_RCCL) {
+      // the owned slices into the chunk layout (dist.hpp), then ONE ncclAllGather per chunk on the comm streams
+      FOR_ISSUED(I, s, i) {
+        if ((rc = launch_chunk_pack(g, s->xbar, s->xchunk, s->rank, s->rank + 1, s->n_alloc, s->stream))) return rc;
+        HIP_TRY(hipEventRecord(s->ev_xbar, s->stream));
+      }
+      for (int c = 0; c < g.ag_chunks; ++c)
+        if ((rc = dist_all_gather_chunk(I, c))) return rc;
+      if (!chunks_on_comm)       // ag_mode 2: every pass behind the whole all-gather (the last chunk's event)
+        FOR_ISSUED(I, s, i) { HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_ag[(size_t)g.ag_chunks - 1], 0)); }
+    } else {
+      if ((rc = dist_all_gather(I, [](pdhg_handle *s) { return s->xbar; }, g.S))) return rc;
+      // chunked on the peer back end: behind the ordinary all-gather, the whole vector into the chunk layout
+      if (chunked) FOR_ISSUED(I, s, i) { if ((rc = launch_chunk_pack(g, s->xbar, s->xchunk, 0, g.world, s->n_alloc, s->stream))) return rc; }
+      // QP: Q acts on full vectors, so x' is kept full as well (x becomes x' at accept)
+      if (lead->has_q && (rc = dist_all_gather(I, [](pdhg_handle *s) { return s->x_next; }, g.S))) return rc;
+    }
+  }
+  FOR_ISSUED(I, s, i) {
+    if ((rc = chunked ? launch_dual_chunked(s, sigma, chunks_on_comm) : launch_dual(s, sigma))) return rc;
+    if (!g.overlap && (rc = launch_aty_plain(s, s->y_next, s->aty_next))) return rc;      // t_p = A_p' y'_p, all n columns
+  }
+  if (!g.overlap) {
+    ProfScope ps(lead, PDHG_K_REDUCE_SCATTER);
+    if ((rc = dist_reduce_scatter(I, [](pdhg_handle *s) { return s->aty_next; }, g.S))) return rc;
+  } else if ((rc = group_aty_by_slices(I))) return rc;
+  FOR_ISSUED(I, s, i) {
+    {
+      ProfScope ps(s, PDHG_K_INTERACTION);
+      const int64_t o = s->clo;
+      hipLaunchKernelGGL(interaction_kernel, dim3(ew_grid(s->cn)), dim3(TPB), 0, s->stream, (int)s->cn, s->x + o,
+                         s->x_next + o, s->aty + o, s->aty_next + o, s->pAt, s->pAt_stride);
+      HIP_TRY(hipGetLastError());
+    }
+    int qcount = 0;
+    if ((rc = launch_q_interaction(s, &qcount))) return rc;   // replicated: identical on every shard
+    const int a_slots = chunked ? dual_chunk_slots(s) : s->A.slots();
+    if ((rc = launch_final(s, s->pAt, ew_grid(s->cn), s->pAt_stride, s->pA, a_slots, qcount, false, chunked ? a_slots : -1))) return rc;
+  }
+  return 0;
+}
+
+// The trial on the issuer the group has: the pool's threads, one per shard (thread 0 is the caller), unless the group has
+// none or is being profiled -- then the calling thread.  t_issue: until the last issuer's last launch call returned (on
+// the calling thread the clock starts behind the primal step, as it always has); t_wait: from then until the scalars
+// were on the host.
+static int group_trial(const Shards &L, const TrialArgs &a, double out[5]) {
+  DistGroup &g = *L.g;
+  auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  double t0, t1, r[5];
+  int rc;
+  if (g.pool && !L.p[0]->profile) {
+    t0 = t1 = now_s();
+    std::vector<double> issued((size_t)L.count, t0);
+    rc = g.pool->run([&](int i) -> int {
+      const Issue I(g, i);
+      int e;
+      if ((e = group_trial_primal(I, a)) || (e = group_trial_dual(I, a))) return e;
+      pdhg_handle *s = L.p[i];                 // (its device is current: the walks above made it so)
+      HIP_TRY(hipMemcpyAsync(s->scal_host, s->scal_dev, sizeof(double) * 5, hipMemcpyDeviceToHost, s->stream));
+      issued[(size_t)i] = now_s();
+      HIP_TRY(hipStreamSynchronize(s->stream));
+      return 0;
+    });
+    if (rc) return rc;
+    for (double v : issued) t1 = std::max(t1, v);
+    sum_scalars_in_rank_order(L, 5, 4, r);
+  } else {
+    if ((rc = group_trial_primal(g, a))) return rc;
+    t0 = now_s();
+    if ((rc = group_trial_dual(g, a))) return rc;
+    t1 = now_s();
+    if ((rc = combine_scalars(L, 5, 4, r))) return rc;
+  }
+  g.t_issue += t1 - t0; g.t_wait += now_s() - t1; g.n_trials += 1;
+  // [0..4) are added in rank order; [4] (dx'Q dx, replicated: the same value on every rank) is "maxed"
+  for (int q = 0; q < 4; ++q) out[q] = r[q];
+  out[4] = 0.5 * r[4];
   return 0;
 }
 
@@ -380,118 +425,6 @@ static int group_coop_trial(const Shards &L, const TrialArgs &ta, double out[5])
   return 0;
 }
 
-// Row-partitioned group: the dual half of a trial.  xbar's owned slices are ready.
-static int trial_dual_group(const Shards &L, double step_size, double primal_weight, double out[5]) {
-  DistGroup &g = *L.g;
-  pdhg_handle *lead = L.p[0];
-  int rc;
-  const auto t_begin = std::chrono::steady_clock::now();
-  // The all-gather of xbar beside A_p xbar (DistGroup::ag_chunks; SURVEY 8e(ii), pdhg.jl:472-494): xbar travels in column
-  // chunks on the comm streams -- chunk c = sub-range c of every rank's slice, so that every link carries a part of every
-  // chunk -- and A_p xbar is one pass per chunk, pass c waiting for chunk c alone while chunk c + 1 is on the links.
-  // ag_mode 2 (and the peer back end): the same passes behind one all-gather -- the same bits, nothing overlapped.
-  const bool chunked = g.ag_chunks > 1 && !lead->has_q;
-  const bool chunks_on_comm = chunked && g.ag_mode == 1 && g.backend == COMM_RCCL;
-  if (chunked && g.backend == COMM_RCCL) {
-    // the owned slices into the chunk layout (dist.hpp), then ONE ncclAllGather per chunk on the comm streams
-    ProfScope ps(lead, PDHG_K_ALLGATHER);
-    FOR_SHARDS(L, s) {
-      if ((rc = launch_chunk_pack(g, s, s->xbar, s->xchunk, s->rank, s->rank + 1, s->n_alloc, s->stream))) return rc;
-      HIP_TRY(hipEventRecord(s->ev_xbar, s->stream));
-    }
-    for (int c = 0; c < g.ag_chunks; ++c)
-      if ((rc = dist_all_gather_chunk(g, c))) return rc;
-    if (!chunks_on_comm)       // ag_mode 2: every pass behind the whole all-gather
-      FOR_SHARDS(L, s) { HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_ag[(size_t)g.ag_chunks - 1], 0)); }
-  } else if (chunked) {
-    // peer back end: the ordinary all-gather, then the whole vector into the chunk layout
-    ProfScope ps(lead, PDHG_K_ALLGATHER);
-    if ((rc = dist_all_gather(g, [](pdhg_handle *s) { return s->xbar; }, g.S))) return rc;
-    FOR_SHARDS(L, s) { if ((rc = launch_chunk_pack(g, s, s->xbar, s->xchunk, 0, g.world, s->n_alloc, s->stream))) return rc; }
-  } else {
-    ProfScope ps(lead, PDHG_K_ALLGATHER);
-    if ((rc = dist_all_gather(g, [](pdhg_handle *s) { return s->xbar; }, g.S))) return rc;
-    // QP: Q acts on full vectors, so x' is kept full as well (x becomes x' at accept)
-    if (lead->has_q && (rc = dist_all_gather(g, [](pdhg_handle *s) { return s->x_next; }, g.S))) return rc;
-  }
-  auto dual_of = [&](pdhg_handle *s) { return chunked ? launch_dual_chunked(s, primal_weight * step_size, chunks_on_comm)
-                                                      : launch_dual(s, primal_weight * step_size); };
-  if (!g.overlap) {
-    FOR_SHARDS(L, s) {
-      if ((rc = dual_of(s))) return rc;
-      if ((rc = launch_aty_plain(s, s->y_next, s->aty_next))) return rc;      // t_p = A_p' y'_p, all n columns
-    }
-    ProfScope ps(lead, PDHG_K_REDUCE_SCATTER);
-    if ((rc = dist_reduce_scatter(g, [](pdhg_handle *s) { return s->aty_next; }, g.S))) return rc;
-  } else {
-    // t_p in parts: a shard whose A_p' uses the tiled layout launches it one residency
-    // round at a time (256 CUs x 2 workgroups: a smaller launch would idle CUs for the whole
-    // sweep); as soon as the rows of slice k are complete, slice k is reduced to rank k on
-    // the comm stream while the next round computes.  The sequence of collectives (slice
-    // 0, 1, ..., P-1) is the same on every rank however the local product is cut.
-    FOR_SHARDS(L, s) { if ((rc = dual_of(s))) return rc; }
-    const char *rw_env = dev_env("PDHG_DIST_ROUND_WGS");            // tests use a finer granule on small problems
-    const int round_wgs = rw_env ? std::max(1, atoi(rw_env)) : 256 * 2;
-    std::vector<int> issued((size_t)L.count, 0), next_wg((size_t)L.count, 0);
-    int k_issued = 0;
-    while (k_issued < g.world) {
-      // every local shard advances until slice k_issued is complete on it
-      for (int i = 0; i < L.count; ++i) {
-        pdhg_handle *s = L.p[i];
-        HIP_TRY(hipSetDevice(s->device));
-        const CsrDev &T = s->At;
-        const int64_t need = std::min<int64_t>(s->n, (int64_t)(k_issued + 1) * g.S);   // rows [0, need) must be done
-        if (!T.tiled) {
-          if (issued[(size_t)i] == 0) {
-            if ((rc = launch_aty_plain(s, s->y_next, s->aty_next))) return rc;
-            issued[(size_t)i] = 1;
-          }
-        } else {
-          while (next_wg[(size_t)i] < T.grid || issued[(size_t)i] == 0) {
-            const int g0 = next_wg[(size_t)i];
-            const bool covered = g0 >= T.grid || (int64_t)T.wg_first_row[(size_t)g0] >= need;
-            if (covered && issued[(size_t)i] != 0) break;
-            int g1 = std::min(T.grid, g0 + round_wgs);
-            if (T.grid - g1 < round_wgs / 2) g1 = T.grid;       // no runt round at the end
-            ProfScope ps(s, PDHG_K_SPMV_ATY);
-            if ((rc = launch_spmv_plain_part(s, T, s->y_next, s->aty_next, g0, g1, issued[(size_t)i] == 0))) return rc;
-            issued[(size_t)i] = 1;
-            next_wg[(size_t)i] = g1;
-          }
-        }
-        HIP_TRY(hipEventRecord(s->ev_part[(size_t)k_issued], s->stream));
-      }
-      if ((rc = dist_reduce_slice_async(g, [](pdhg_handle *s) { return s->aty_next; }, g.S, k_issued))) return rc;
-      ++k_issued;
-    }
-    ProfScope ps(lead, PDHG_K_REDUCE_SCATTER);     // what is left of the exchange after the product
-    if ((rc = dist_join_comm(g))) return rc;
-  }
-  FOR_SHARDS(L, s) {
-    {
-      ProfScope ps(s, PDHG_K_INTERACTION);
-      const int64_t o = s->clo;
-      hipLaunchKernelGGL(interaction_kernel, dim3(ew_grid(s->cn)), dim3(TPB), 0, s->stream, (int)s->cn, s->x + o,
-                         s->x_next + o, s->aty + o, s->aty_next + o, s->pAt, s->pAt_stride);
-      HIP_TRY(hipGetLastError());
-    }
-    int qcount = 0;
-    if ((rc = launch_q_interaction(s, &qcount))) return rc;   // replicated: identical on every shard
-    if ((rc = launch_final(s, s->pAt, ew_grid(s->cn), s->pAt_stride, s->pA, chunked ? dual_chunk_slots(s) : s->A.slots(), qcount, false,
-                           chunked ? dual_chunk_slots(s) : -1))) return rc;
-  }
-  double r[5];
-  const auto t_issued = std::chrono::steady_clock::now();
-  // [0..4) are added in rank order; [4] (dx'Q dx, replicated: the same value on every rank) is "maxed"
-  if ((rc = combine_scalars(L, 5, 4, r))) return rc;
-  g.t_issue += std::chrono::duration<double>(t_issued - t_begin).count();
-  g.t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_issued).count();
-  g.n_trials += 1;
-  for (int q = 0; q < 4; ++q) out[q] = r[q];
-  out[4] = 0.5 * r[4];
-  return 0;
-}
-
 int pdhg_trial_primal(pdhg_handle *h, double step_size, double primal_weight) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -506,40 +439,31 @@ static bool trial_stays_off_member_streams(const pdhg_handle *h) {
   return h && h->grp && h->grp->coop_mode == 1 && !h->grp->sh.empty() && !h->grp->sh[0]->profile;
 }
 
-int pdhg_trial_dual(pdhg_handle *h, double step_size, double primal_weight, double theta, double out[5]) {
+// persistent kernel -> graph (a whole step only) -> single handle launch by launch; a group: group kernels -> launch by launch
+static int trial_dispatch(pdhg_handle *h, const TrialArgs &a, double out[5]) {
   int rc = check_handle(h, !trial_stays_off_member_streams(h));
   if (rc) return rc;
   if (!out) return fail(-1, "out == NULL");
   const Shards L = shards_of(h);
-  if (!L.g && coop_eligible(h)) {         // Malitsky-Pock retries: xbar + the dual half
-    if ((rc = coop_trial(h, step_size, primal_weight, theta, true, out)) != 1) return rc;    // 1: not run / timed out, repeat below
+  if (L.g) {
+    if (group_coop_eligible(L) && (rc = group_coop_trial(L, a, out)) != 1) return rc;       // 1: not run / timed out, repeat below
+    return group_trial(L, a, out);
   }
-  if (L.g && group_coop_eligible(L)) {
-    if ((rc = group_coop_trial(L, TrialArgs{step_size, primal_weight, theta, false}, out)) != 1) return rc;
-  }
-  if (L.g && L.g->pool && !L.p[0]->profile) return trial_group_mt(L, TrialArgs{step_size, primal_weight, theta, false}, out);
-  FOR_SHARDS(L, s) { if ((rc = launch_xbar(s, theta))) return rc; }
-  if (L.g) return trial_dual_group(L, step_size, primal_weight, out);
-  return trial_dual_single(h, step_size, primal_weight, out);
+  // (pdhg_trial_dual here: Malitsky-Pock retries, xbar + the dual half)
+  if (coop_eligible(h) && (rc = coop_trial(h, a.step_size, a.primal_weight, a.theta, !a.primal, out)) != 1) return rc;   // 1: as above
+  if (a.primal && graph_eligible(h)) return graph_trial(h, a.step_size, a.primal_weight, a.theta, out);
+  // (check_handle has made the handle's device current)
+  if ((rc = a.primal ? launch_primal(h, a.step_size / a.primal_weight, a.theta, true) : launch_xbar(h, a.theta))) return rc;
+  return trial_dual_single(h, a.step_size, a.primal_weight, out);
+}
+
+int pdhg_trial_dual(pdhg_handle *h, double step_size, double primal_weight, double theta, double out[5]) {
+  return trial_dispatch(h, TrialArgs{step_size, primal_weight, theta, false}, out);
 }
 
 int pdhg_trial_step(pdhg_handle *h, double step_size, double primal_weight, double theta, double out[5]) {
   RoctxRange roctx_range("pdhg_trial_step");
-  int rc = check_handle(h, !trial_stays_off_member_streams(h));
-  if (rc) return rc;
-  if (!out) return fail(-1, "out == NULL");
-  const Shards L = shards_of(h);
-  if (!L.g && coop_eligible(h)) {
-    if ((rc = coop_trial(h, step_size, primal_weight, theta, false, out)) != 1) return rc;   // 1: not run / timed out, repeat below
-  }
-  if (!L.g && graph_eligible(h)) return graph_trial(h, step_size, primal_weight, theta, out);
-  if (L.g && group_coop_eligible(L)) {
-    if ((rc = group_coop_trial(L, TrialArgs{step_size, primal_weight, theta, true}, out)) != 1) return rc;
-  }
-  if (L.g && L.g->pool && !L.p[0]->profile) return trial_group_mt(L, TrialArgs{step_size, primal_weight, theta, true}, out);
-  FOR_SHARDS(L, s) { if ((rc = launch_primal(s, step_size / primal_weight, theta, true))) return rc; }
-  if (L.g) return trial_dual_group(L, step_size, primal_weight, out);
-  return trial_dual_single(h, step_size, primal_weight, out);
+  return trial_dispatch(h, TrialArgs{step_size, primal_weight, theta, true}, out);
 }
 
 int pdhg_accept(pdhg_handle *h0, double avg_weight) {

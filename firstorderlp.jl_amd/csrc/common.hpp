@@ -32,6 +32,9 @@ inline int long_row_threshold_from_env() {
 }
 constexpr int NUM_XCD = 8;
 constexpr int EW_MAX_BLOCKS = 256 * 8;  // elementwise kernels: grid-stride above this
+inline int ew_grid(int64_t len) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>((len + TPB - 1) / TPB, EW_MAX_BLOCKS));
+}
 constexpr int FINAL_TPB = 1024;
 // tiled-sweep layout (SpMV v2)
 constexpr int TW_WPB = 8;              // waves per workgroup (512 threads), 2 workgroups per CU

@@ -157,7 +157,6 @@ struct DistGroup {
   int64_t S = 0;                        // slice stride: rank r owns columns [r*S, min(n, (r+1)*S))
   std::vector<int64_t> row_lo;          // [world+1] global row range of every rank
   std::vector<hipEvent_t> ev[2];        // cross-stream barrier of the peer back end
-  int flip = 0;
   // Exchange pattern of the trial's A_p'y_p: one reduce-scatter after the product, or P
   // per-slice reductions issued as the product's slices complete (on the comm streams,
   // overlapping the rest of the product).  Decided from (n, world, environment) only, so
@@ -252,41 +251,6 @@ __global__ __launch_bounds__(TPB) void p2p_reduce_kernel(PeerPtrs pp, int64_t of
   }
 }
 
-// every local stream waits for everything queued so far on every other local stream.
-// Up to 4 shards: all pairs (one hop, P^2 calls).  More: the first stream waits for all
-// the others and records "go", the others wait for "go" (two hops, 3P calls) -- measured
-// on 2 / 8 shards of one GPU: the hub form is 20 % slower at 2 and 6 % faster at 8.
-int p2p_barrier(DistGroup &g) {
-  const int k = (int)g.sh.size();
-  if (k <= 1) return 0;
-  g.flip ^= 1;
-  std::vector<hipEvent_t> &ev = g.ev[g.flip];
-  if (k <= 4) {
-    for (int i = 0; i < k; ++i) {
-      HIP_TRY(hipSetDevice(g.sh[i]->device));
-      HIP_TRY(hipEventRecord(ev[i], g.sh[i]->stream));
-    }
-    for (int i = 0; i < k; ++i) {
-      HIP_TRY(hipSetDevice(g.sh[i]->device));
-      for (int q = 0; q < k; ++q)
-        if (q != i) HIP_TRY(hipStreamWaitEvent(g.sh[i]->stream, ev[q], 0));
-    }
-    return 0;
-  }
-  for (int i = 1; i < k; ++i) {
-    HIP_TRY(hipSetDevice(g.sh[i]->device));
-    HIP_TRY(hipEventRecord(ev[i], g.sh[i]->stream));
-  }
-  HIP_TRY(hipSetDevice(g.sh[0]->device));
-  for (int q = 1; q < k; ++q) HIP_TRY(hipStreamWaitEvent(g.sh[0]->stream, ev[q], 0));
-  HIP_TRY(hipEventRecord(ev[0], g.sh[0]->stream));          // "go": everything queued anywhere so far is done
-  for (int i = 1; i < k; ++i) {
-    HIP_TRY(hipSetDevice(g.sh[i]->device));
-    HIP_TRY(hipStreamWaitEvent(g.sh[i]->stream, ev[0], 0));
-  }
-  return 0;
-}
-
 // own[q*S .. q*S+S) = peer q's slice, for every q != rank: the all-gather's pull as ONE kernel
 __global__ __launch_bounds__(TPB) void p2p_gather_kernel(PeerPtrs pp, int rank, int64_t S, double *own) {
   const int64_t stride = (int64_t)gridDim.x * TPB;
@@ -298,123 +262,177 @@ __global__ __launch_bounds__(TPB) void p2p_gather_kernel(PeerPtrs pp, int rank, 
   }
 }
 
-// A buffer selector: the same logical vector on every shard.
-typedef double *(*BufSel)(pdhg_handle *);
+// the same logical vector on every shard (`sel` picks it), by rank
+template <typename Sel>
+inline PeerPtrs peer_ptrs(DistGroup &g, Sel sel) {
+  PeerPtrs pp{};
+  pp.world = g.world;
+  for (pdhg_handle *q : g.sh) pp.p[q->rank] = sel(q);
+  return pp;
+}
+
+// ---- who issues ------------------------------------------------------------------------------------------------------
+// A group's work is issued either by the calling thread, which walks every local shard one after the other (one process
+// per GPU; PDHG_SHARD_THREADS=0; every profiled trial; every entry point other than the trial), or by the ShardPool, one
+// thread per shard.  Every exchange below is ONE text for both.  The issuers differ in three places, and nowhere else
+// does the code ask who issues:
+//  * the shards walked (FOR_ISSUED): all of g.sh, or shard i;
+//  * MEETING POINTS (meet()): where a shard's next call needs something EVERY local shard has queued (an event recorded),
+//    a pool thread waits for its siblings; the calling thread has nothing to do, it has just walked all of them.  There
+//    are three, all on the peer back end: inside stream_barrier (between its records and its waits), and at the head of
+//    dist_reduce_slice_async and of dist_join_comm's waits.  Every pool thread must reach the same sequence of them: a
+//    condition around a meeting point, or around a call that holds one, may depend on GROUP state only (backend, overlap,
+//    ag_chunks, has_q -- equal on all shards), never on a shard's own (At.tiled is chosen per shard from its own rows);
+//  * RCCL group calls: one thread driving several communicators brackets them with ncclGroupStart/End (with a single local
+//    shard as well: that is what the transports have seen); one thread per communicator does not.
+struct Issue {
+  DistGroup &g;
+  int lo, hi;                            // shards [lo, hi) of g.sh
+  Issue(DistGroup &g_) : g(g_), lo(0), hi((int)g_.sh.size()) {}                 // the calling thread: all local shards
+  Issue(DistGroup &g_, int i) : g(g_), lo(i), hi(i + 1) {}                      // shard i's own thread, one of g.pool's
+  bool threaded() const { return hi - lo < (int)g.sh.size(); }
+  int meet() const { return threaded() ? g.pool->barrier() : 0; }
+  int rccl_begin(const RcclApi *R) const { if (!threaded()) NCCL_TRY(R->GroupStart()); return 0; }
+  int rccl_end(const RcclApi *R) const { if (!threaded()) NCCL_TRY(R->GroupEnd()); return 0; }
+};
+// FOR_SHARDS over the issued shards; `i` is the shard's index in g.sh
+#define FOR_ISSUED(I, s, i)                                                     \
+  for (int i = (I).lo; i < (I).hi; ++i)                                         \
+    if (pdhg_handle *s = (I).g.sh[(size_t)i])                                   \
+      if (hipError_t _sde = hipSetDevice(s->device); _sde != hipSuccess)        \
+        return fail_hip(_sde, "hipSetDevice (shard loop)");                     \
+      else
+
+// every local stream waits for everything queued so far on every other local stream (peer back end): record my event,
+// meet, wait for the others' events.  The two event sets alternate (pdhg_handle::bar_flip: every barrier is taken for
+// every local shard, so the shards' counters agree), so that no event is recorded again while a sibling may still have
+// to wait for its last record.
+// All pairs (one hop, P^2 calls) -- except for one thread with more than 4 shards: the first stream waits for all the
+// others and records "go", the others wait for "go" (two hops, 3P calls) -- measured on 2 / 8 shards of one GPU: the hub
+// form is 20 % slower at 2 and 6 % faster at 8.
+int stream_barrier(const Issue &I) {
+  DistGroup &g = I.g;
+  const int k = (int)g.sh.size();
+  if (k <= 1) return 0;
+  const bool hub = !I.threaded() && k > 4;
+  FOR_ISSUED(I, s, i) {
+    s->bar_flip ^= 1;
+    if (!(hub && i == 0)) HIP_TRY(hipEventRecord(g.ev[s->bar_flip][(size_t)i], s->stream));
+  }
+  int rc = I.meet();                     // every local shard's event is recorded
+  if (rc) return rc;
+  if (hub) {
+    pdhg_handle *s0 = g.sh[0];
+    std::vector<hipEvent_t> &ev = g.ev[s0->bar_flip];
+    HIP_TRY(hipSetDevice(s0->device));
+    for (int q = 1; q < k; ++q) HIP_TRY(hipStreamWaitEvent(s0->stream, ev[(size_t)q], 0));
+    HIP_TRY(hipEventRecord(ev[0], s0->stream));          // "go": everything queued anywhere so far is done
+    FOR_ISSUED(I, s, i) { if (i > 0) HIP_TRY(hipStreamWaitEvent(s->stream, ev[0], 0)); }
+    return 0;
+  }
+  FOR_ISSUED(I, s, i) {
+    for (int q = 0; q < k; ++q)
+      if (q != i) HIP_TRY(hipStreamWaitEvent(s->stream, g.ev[s->bar_flip][(size_t)q], 0));
+  }
+  return 0;
+}
 
 // In-place all-gather: rank r contributes buf[r*S .. r*S+S), every rank ends with all of them.
 // The buffers hold world*S doubles.
 template <typename Sel>
-int dist_all_gather(DistGroup &g, Sel sel, int64_t S) {
+int dist_all_gather(const Issue &I, Sel sel, int64_t S) {
+  DistGroup &g = I.g;
   if (g.world == 1 && g.backend == COMM_P2P) return 0;
+  int rc;
   if (g.backend == COMM_RCCL) {
     RCCL_API(R);
-    NCCL_TRY(R->GroupStart());
-    for (size_t i = 0; i < g.sh.size(); ++i) {
-      pdhg_handle *s = g.sh[i];
-      HIP_TRY(hipSetDevice(s->device));
+    if ((rc = I.rccl_begin(R))) return rc;
+    FOR_ISSUED(I, s, i) {
       double *b = sel(s);
-      NCCL_TRY(R->AllGather(b + (int64_t)s->rank * S, b, (size_t)S, ncclDouble, g.comm[i], s->stream));
+      NCCL_TRY(R->AllGather(b + (int64_t)s->rank * S, b, (size_t)S, ncclDouble, g.comm[(size_t)i], s->stream));
     }
-    NCCL_TRY(R->GroupEnd());
-    return 0;
+    return I.rccl_end(R);
   }
-  int rc;
-  if ((rc = p2p_barrier(g))) return rc;
-  PeerPtrs pp{};
-  pp.world = g.world;
-  for (pdhg_handle *q : g.sh) pp.p[q->rank] = sel(q);
-  for (pdhg_handle *s : g.sh) {
-    HIP_TRY(hipSetDevice(s->device));
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((S + TPB - 1) / TPB, EW_MAX_BLOCKS));
-    hipLaunchKernelGGL(p2p_gather_kernel, dim3(grid), dim3(TPB), 0, s->stream, pp, s->rank, S, sel(s));
+  if ((rc = stream_barrier(I))) return rc;
+  const PeerPtrs pp = peer_ptrs(g, sel);
+  FOR_ISSUED(I, s, i) {
+    hipLaunchKernelGGL(p2p_gather_kernel, dim3(ew_grid(S)), dim3(TPB), 0, s->stream, pp, s->rank, S, sel(s));
     HIP_TRY(hipGetLastError());
   }
-  return p2p_barrier(g);
+  return stream_barrier(I);
 }
 
 // In-place reduce-scatter: rank r ends with op_q buf_q[r*S .. r*S+S) in ITS buf[r*S ..).
 template <typename Sel>
-int dist_reduce_scatter(DistGroup &g, Sel sel, int64_t S, bool maxop = false) {
+int dist_reduce_scatter(const Issue &I, Sel sel, int64_t S, bool maxop = false) {
+  DistGroup &g = I.g;
   if (g.world == 1 && g.backend == COMM_P2P) return 0;
+  int rc;
   if (g.backend == COMM_RCCL) {
     RCCL_API(R);
-    NCCL_TRY(R->GroupStart());
-    for (size_t i = 0; i < g.sh.size(); ++i) {
-      pdhg_handle *s = g.sh[i];
-      HIP_TRY(hipSetDevice(s->device));
+    if ((rc = I.rccl_begin(R))) return rc;
+    FOR_ISSUED(I, s, i) {
       double *b = sel(s);
       NCCL_TRY(R->ReduceScatter(b, b + (int64_t)s->rank * S, (size_t)S, ncclDouble, maxop ? ncclMax : ncclSum,
-                                 g.comm[i], s->stream));
+                                 g.comm[(size_t)i], s->stream));
     }
-    NCCL_TRY(R->GroupEnd());
-    return 0;
+    return I.rccl_end(R);
   }
-  int rc;
-  if ((rc = p2p_barrier(g))) return rc;
-  PeerPtrs pp{};
-  pp.world = g.world;
-  for (pdhg_handle *q : g.sh) pp.p[q->rank] = sel(q);
-  for (pdhg_handle *s : g.sh) {
-    HIP_TRY(hipSetDevice(s->device));
+  if ((rc = stream_barrier(I))) return rc;
+  const PeerPtrs pp = peer_ptrs(g, sel);
+  FOR_ISSUED(I, s, i) {
     const int64_t off = (int64_t)s->rank * S;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((S + TPB - 1) / TPB, EW_MAX_BLOCKS));
-    if (maxop) hipLaunchKernelGGL(p2p_reduce_kernel<true>, dim3(grid), dim3(TPB), 0, s->stream, pp, off, S, sel(s) + off);
-    else hipLaunchKernelGGL(p2p_reduce_kernel<false>, dim3(grid), dim3(TPB), 0, s->stream, pp, off, S, sel(s) + off);
+    if (maxop) hipLaunchKernelGGL(p2p_reduce_kernel<true>, dim3(ew_grid(S)), dim3(TPB), 0, s->stream, pp, off, S, sel(s) + off);
+    else hipLaunchKernelGGL(p2p_reduce_kernel<false>, dim3(ew_grid(S)), dim3(TPB), 0, s->stream, pp, off, S, sel(s) + off);
     HIP_TRY(hipGetLastError());
   }
-  return p2p_barrier(g);
+  return stream_barrier(I);
 }
 
 // Slice k of the partial vectors (S doubles at k*S) summed over ranks into its owner's
 // buffer, asynchronously on the comm streams, once every shard has recorded ev_part[k]
-// on its compute stream.  dist_join_comm() makes the compute streams wait for all of them.
+// on its compute stream (the caller did so for the issued shards just before).
+// dist_join_comm() makes the compute streams wait for all of them.
 template <typename Sel>
-int dist_reduce_slice_async(DistGroup &g, Sel sel, int64_t S, int k) {
+int dist_reduce_slice_async(const Issue &I, Sel sel, int64_t S, int k) {
+  DistGroup &g = I.g;
+  int rc;
   if (g.backend == COMM_RCCL) {
     RCCL_API(R);
-    for (pdhg_handle *s : g.sh) {
-      HIP_TRY(hipSetDevice(s->device));
-      HIP_TRY(hipStreamWaitEvent(s->comm_stream, s->ev_part[(size_t)k], 0));
-    }
-    NCCL_TRY(R->GroupStart());
-    for (size_t i = 0; i < g.sh.size(); ++i) {
-      pdhg_handle *s = g.sh[i];
-      HIP_TRY(hipSetDevice(s->device));
+    FOR_ISSUED(I, s, i) { HIP_TRY(hipStreamWaitEvent(s->comm_stream, s->ev_part[(size_t)k], 0)); }
+    if ((rc = I.rccl_begin(R))) return rc;
+    FOR_ISSUED(I, s, i) {
       double *b = sel(s) + (int64_t)k * S;
-      NCCL_TRY(R->Reduce(b, b, (size_t)S, ncclDouble, ncclSum, k, g.comm[i], s->comm_stream));
+      NCCL_TRY(R->Reduce(b, b, (size_t)S, ncclDouble, ncclSum, k, g.comm[(size_t)i], s->comm_stream));
     }
-    NCCL_TRY(R->GroupEnd());
-    return 0;
+    return I.rccl_end(R);
   }
-  pdhg_handle *owner = nullptr;
-  PeerPtrs pp{};
-  pp.world = g.world;
-  for (pdhg_handle *q : g.sh) { pp.p[q->rank] = sel(q); if (q->rank == k) owner = q; }
-  if (!owner) return fail(-1, "peer back end needs every rank in this process");
+  int owner_at = -1;
+  for (int i = 0; i < (int)g.sh.size(); ++i) if (g.sh[(size_t)i]->rank == k) owner_at = i;
+  if (owner_at < 0) return fail(-1, "peer back end needs every rank in this process");
+  if ((rc = I.meet())) return rc;           // everybody's ev_part[k] is recorded
+  if (owner_at < I.lo || owner_at >= I.hi) return 0;      // (the owner's issuer queues the reduction)
+  pdhg_handle *owner = g.sh[(size_t)owner_at];
   HIP_TRY(hipSetDevice(owner->device));
   for (pdhg_handle *q : g.sh) HIP_TRY(hipStreamWaitEvent(owner->comm_stream, q->ev_part[(size_t)k], 0));
   const int64_t off = (int64_t)k * S;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((S + TPB - 1) / TPB, EW_MAX_BLOCKS));
-  hipLaunchKernelGGL(p2p_reduce_kernel<false>, dim3(grid), dim3(TPB), 0, owner->comm_stream, pp, off, S, sel(owner) + off);
+  hipLaunchKernelGGL(p2p_reduce_kernel<false>, dim3(ew_grid(S)), dim3(TPB), 0, owner->comm_stream, peer_ptrs(g, sel), off, S, sel(owner) + off);
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
-int dist_join_comm(DistGroup &g) {
-  for (pdhg_handle *s : g.sh) {
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipEventRecord(s->ev_comm, s->comm_stream));
+int dist_join_comm(const Issue &I) {
+  DistGroup &g = I.g;
+  FOR_ISSUED(I, s, i) { HIP_TRY(hipEventRecord(s->ev_comm, s->comm_stream)); }
+  if (g.backend == COMM_RCCL) {
+    FOR_ISSUED(I, s, i) { HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_comm, 0)); }
+    return 0;
   }
-  for (pdhg_handle *s : g.sh) {
-    HIP_TRY(hipSetDevice(s->device));
-    if (g.backend == COMM_RCCL) {
-      HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_comm, 0));
-    } else {
-      // peer kernels read the OTHER shards' buffers: nobody may reuse its partial vector
-      // before every owner has finished reading
-      for (pdhg_handle *q : g.sh) HIP_TRY(hipStreamWaitEvent(s->stream, q->ev_comm, 0));
-    }
-  }
+  // peer kernels read the OTHER shards' buffers: nobody may reuse its partial vector
+  // before every owner has finished reading
+  int rc = I.meet();                        // every owner's ev_comm is recorded
+  if (rc) return rc;
+  FOR_ISSUED(I, s, i) { for (pdhg_handle *q : g.sh) HIP_TRY(hipStreamWaitEvent(s->stream, q->ev_comm, 0)); }
   return 0;
 }
 
@@ -434,138 +452,26 @@ __global__ __launch_bounds__(TPB) void chunk_pack_kernel(const double *__restric
       dst[c * W + (int64_t)q * sub + off] = j < src_len ? src[j] : 0.0;
     }
 }
-inline int launch_chunk_pack(DistGroup &g, pdhg_handle *s, const double *src, double *dst, int q0, int q1, int64_t src_len, hipStream_t stream) {
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((g.S + TPB - 1) / TPB, EW_MAX_BLOCKS));
-  hipLaunchKernelGGL(chunk_pack_kernel, dim3(grid), dim3(TPB), 0, stream, src, dst, g.S, g.ag_sub, g.ag_chunks, g.world, q0, q1, src_len);
+inline int launch_chunk_pack(DistGroup &g, const double *src, double *dst, int q0, int q1, int64_t src_len, hipStream_t stream) {
+  hipLaunchKernelGGL(chunk_pack_kernel, dim3(ew_grid(g.S)), dim3(TPB), 0, stream, src, dst, g.S, g.ag_sub, g.ag_chunks, g.world, q0, q1, src_len);
   HIP_TRY(hipGetLastError());
-  (void)s;
   return 0;
 }
-// Chunk c of every local shard's xchunk, on the COMM streams (which first wait for "the owned slice is packed": ev_xbar,
+// Chunk c of every issued shard's xchunk, on the COMM streams (which first wait for "the owned slice is packed": ev_xbar,
 // recorded by the caller on the compute streams); ev_ag[c] is recorded behind it.
-int dist_all_gather_chunk(DistGroup &g, int c) {
+int dist_all_gather_chunk(const Issue &I, int c) {
+  DistGroup &g = I.g;
   RCCL_API(R);
   const int64_t W = (int64_t)g.world * g.ag_sub;
-  if (c == 0)
-    for (pdhg_handle *s : g.sh) {
-      HIP_TRY(hipSetDevice(s->device));
-      HIP_TRY(hipStreamWaitEvent(s->comm_stream, s->ev_xbar, 0));
-    }
-  NCCL_TRY(R->GroupStart());
-  for (size_t i = 0; i < g.sh.size(); ++i) {
-    pdhg_handle *s = g.sh[i];
-    HIP_TRY(hipSetDevice(s->device));
+  int rc;
+  if (c == 0) FOR_ISSUED(I, s, i) { HIP_TRY(hipStreamWaitEvent(s->comm_stream, s->ev_xbar, 0)); }
+  if ((rc = I.rccl_begin(R))) return rc;
+  FOR_ISSUED(I, s, i) {
     double *b = s->xchunk + (int64_t)c * W;
-    NCCL_TRY(R->AllGather(b + (int64_t)s->rank * g.ag_sub, b, (size_t)g.ag_sub, ncclDouble, g.comm[i], s->comm_stream));
+    NCCL_TRY(R->AllGather(b + (int64_t)s->rank * g.ag_sub, b, (size_t)g.ag_sub, ncclDouble, g.comm[(size_t)i], s->comm_stream));
   }
-  NCCL_TRY(R->GroupEnd());
-  for (pdhg_handle *s : g.sh) {
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipEventRecord(s->ev_ag[(size_t)c], s->comm_stream));
-  }
-  return 0;
-}
-// the same for ONE shard, issued by its own host thread
-int mt_all_gather_chunk(DistGroup &g, pdhg_handle *s, int i, int c) {
-  RCCL_API(R);
-  const int64_t W = (int64_t)g.world * g.ag_sub;
-  if (c == 0) HIP_TRY(hipStreamWaitEvent(s->comm_stream, s->ev_xbar, 0));
-  double *b = s->xchunk + (int64_t)c * W;
-  NCCL_TRY(R->AllGather(b + (int64_t)s->rank * g.ag_sub, b, (size_t)g.ag_sub, ncclDouble, g.comm[(size_t)i], s->comm_stream));
-  HIP_TRY(hipEventRecord(s->ev_ag[(size_t)c], s->comm_stream));
-  return 0;
-}
-
-// ---- the same collectives issued PER SHARD, each by its own host thread (ShardPool) -------
-// `i` is the shard's index in g.sh, `s` the shard; every local shard's thread makes the same
-// sequence of calls.  RCCL: plain per-communicator calls (one thread per device needs no
-// group).  Peer back end: the cross-stream barrier becomes "record my event, meet the other
-// threads, wait for their events".
-
-int mt_stream_barrier(DistGroup &g, pdhg_handle *s, int i) {
-  const int k = (int)g.sh.size();
-  if (k <= 1) return 0;
-  s->mt_flip ^= 1;
-  std::vector<hipEvent_t> &ev = g.ev[s->mt_flip];
-  HIP_TRY(hipEventRecord(ev[(size_t)i], s->stream));
-  int rc = g.pool->barrier();
-  if (rc) return rc;
-  for (int q = 0; q < k; ++q)
-    if (q != i) HIP_TRY(hipStreamWaitEvent(s->stream, ev[(size_t)q], 0));
-  return 0;
-}
-
-inline PeerPtrs peer_ptrs(DistGroup &g, BufSel sel) {
-  PeerPtrs pp{};
-  pp.world = g.world;
-  for (pdhg_handle *q : g.sh) pp.p[q->rank] = sel(q);
-  return pp;
-}
-
-int mt_all_gather(DistGroup &g, pdhg_handle *s, int i, BufSel sel, int64_t S) {
-  if (g.world == 1 && g.backend == COMM_P2P) return 0;
-  if (g.backend == COMM_RCCL) {
-    RCCL_API(R);
-    double *b = sel(s);
-    NCCL_TRY(R->AllGather(b + (int64_t)s->rank * S, b, (size_t)S, ncclDouble, g.comm[(size_t)i], s->stream));
-    return 0;
-  }
-  int rc;
-  if ((rc = mt_stream_barrier(g, s, i))) return rc;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((S + TPB - 1) / TPB, EW_MAX_BLOCKS));
-  hipLaunchKernelGGL(p2p_gather_kernel, dim3(grid), dim3(TPB), 0, s->stream, peer_ptrs(g, sel), s->rank, S, sel(s));
-  HIP_TRY(hipGetLastError());
-  return mt_stream_barrier(g, s, i);
-}
-
-int mt_reduce_scatter(DistGroup &g, pdhg_handle *s, int i, BufSel sel, int64_t S) {
-  if (g.world == 1 && g.backend == COMM_P2P) return 0;
-  if (g.backend == COMM_RCCL) {
-    RCCL_API(R);
-    double *b = sel(s);
-    NCCL_TRY(R->ReduceScatter(b, b + (int64_t)s->rank * S, (size_t)S, ncclDouble, ncclSum, g.comm[(size_t)i], s->stream));
-    return 0;
-  }
-  int rc;
-  if ((rc = mt_stream_barrier(g, s, i))) return rc;
-  const int64_t off = (int64_t)s->rank * S;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((S + TPB - 1) / TPB, EW_MAX_BLOCKS));
-  hipLaunchKernelGGL(p2p_reduce_kernel<false>, dim3(grid), dim3(TPB), 0, s->stream, peer_ptrs(g, sel), off, S, sel(s) + off);
-  HIP_TRY(hipGetLastError());
-  return mt_stream_barrier(g, s, i);
-}
-
-// slice k of the partial vectors to its owner, on the comm streams, after every shard has
-// recorded ev_part[k] on its compute stream (the caller did so for `s` just before)
-int mt_reduce_slice_async(DistGroup &g, pdhg_handle *s, int i, BufSel sel, int64_t S, int k) {
-  if (g.backend == COMM_RCCL) {
-    RCCL_API(R);
-    HIP_TRY(hipStreamWaitEvent(s->comm_stream, s->ev_part[(size_t)k], 0));
-    double *b = sel(s) + (int64_t)k * S;
-    NCCL_TRY(R->Reduce(b, b, (size_t)S, ncclDouble, ncclSum, k, g.comm[(size_t)i], s->comm_stream));
-    return 0;
-  }
-  int rc = g.pool->barrier();            // everybody's ev_part[k] is recorded
-  if (rc) return rc;
-  if (s->rank != k) return 0;
-  for (pdhg_handle *q : g.sh) HIP_TRY(hipStreamWaitEvent(s->comm_stream, q->ev_part[(size_t)k], 0));
-  const int64_t off = (int64_t)k * S;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((S + TPB - 1) / TPB, EW_MAX_BLOCKS));
-  hipLaunchKernelGGL(p2p_reduce_kernel<false>, dim3(grid), dim3(TPB), 0, s->comm_stream, peer_ptrs(g, sel), off, S, sel(s) + off);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int mt_join_comm(DistGroup &g, pdhg_handle *s, int i) {
-  (void)i;
-  HIP_TRY(hipEventRecord(s->ev_comm, s->comm_stream));
-  if (g.backend == COMM_RCCL) {
-    HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_comm, 0));
-    return 0;
-  }
-  int rc = g.pool->barrier();            // every owner's ev_comm is recorded
-  if (rc) return rc;
-  for (pdhg_handle *q : g.sh) HIP_TRY(hipStreamWaitEvent(s->stream, q->ev_comm, 0));
+  if ((rc = I.rccl_end(R))) return rc;
+  FOR_ISSUED(I, s, i) { HIP_TRY(hipEventRecord(s->ev_ag[(size_t)c], s->comm_stream)); }
   return 0;
 }
 
@@ -600,7 +506,7 @@ int dist_all_gather_rows(DistGroup &g, Sel sel) {
     return 0;
   }
   int rc;
-  if ((rc = p2p_barrier(g))) return rc;
+  if ((rc = stream_barrier(g))) return rc;
   for (pdhg_handle *s : g.sh) {
     HIP_TRY(hipSetDevice(s->device));
     for (pdhg_handle *q : g.sh) {
@@ -610,7 +516,19 @@ int dist_all_gather_rows(DistGroup &g, Sel sel) {
                                hipMemcpyDeviceToDevice, s->stream));
     }
   }
-  return p2p_barrier(g);
+  return stream_barrier(g);
+}
+
+// the k scalars the local shards hold in scal_host, combined in rank order: [0, nsum) added, [nsum, k) maxed
+void sum_scalars_in_rank_order(const Shards &L, int k, int nsum, double *out) {
+  for (int q = 0; q < k; ++q) {
+    double v = L.p[0]->scal_host[q];
+    for (int i = 1; i < L.count; ++i) {
+      const double t = L.p[i]->scal_host[q];
+      v = (q < nsum) ? v + t : std::fmax(v, t);
+    }
+    out[q] = v;
+  }
 }
 
 // The k scalars every shard left in its scal_dev, combined over ALL ranks in
@@ -620,24 +538,9 @@ int combine_scalars(const Shards &L, int k, int nsum, double *out) {
   if (k > SCAL_MAX) return fail(-1, "too many scalars in one reduction");
   DistGroup *g = L.g;
   if (!g || g->all_local()) {
-    for (int i = 0; i < L.count; ++i) {
-      pdhg_handle *s = L.p[i];
-      HIP_TRY(hipSetDevice(s->device));
-      HIP_TRY(hipMemcpyAsync(s->scal_host, s->scal_dev, sizeof(double) * k, hipMemcpyDeviceToHost, s->stream));
-    }
-    for (int i = 0; i < L.count; ++i) {
-      pdhg_handle *s = L.p[i];
-      HIP_TRY(hipSetDevice(s->device));
-      HIP_TRY(hipStreamSynchronize(s->stream));
-    }
-    for (int q = 0; q < k; ++q) {
-      double v = L.p[0]->scal_host[q];
-      for (int i = 1; i < L.count; ++i) {
-        const double t = L.p[i]->scal_host[q];
-        v = (q < nsum) ? v + t : std::fmax(v, t);
-      }
-      out[q] = v;
-    }
+    FOR_SHARDS(L, s) { HIP_TRY(hipMemcpyAsync(s->scal_host, s->scal_dev, sizeof(double) * k, hipMemcpyDeviceToHost, s->stream)); }
+    FOR_SHARDS(L, s) { HIP_TRY(hipStreamSynchronize(s->stream)); }
+    sum_scalars_in_rank_order(L, k, nsum, out);
     return 0;
   }
   // one local shard per process: gather everybody's scalars through RCCL

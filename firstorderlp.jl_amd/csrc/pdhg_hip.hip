@@ -148,7 +148,7 @@ struct pdhg_handle {
   int64_t n_alloc = 0;             // length of the n-vectors that take part in collectives (world * S >= n)
   int64_t row_lo = 0;              // first GLOBAL row of this shard (m is the local row count)
   int64_t m_global = 0;
-  int mt_flip = 0;                     // event set of this shard's next threaded stream barrier
+  int bar_flip = 0;                    // event set (DistGroup::ev) of this shard's last stream barrier; toggled by whoever issues it
   hipStream_t comm_stream = nullptr;   // group: per-slice reductions run here, beside the product that feeds them
   std::vector<hipEvent_t> ev_part;     // [world] "slice k of A_p'y_p is complete" on `stream`
   hipEvent_t ev_comm = nullptr;        // "all of this shard's reductions are done" on `comm_stream`
@@ -224,11 +224,6 @@ struct pdhg_handle {
 namespace {
 
 void destroy_shard(pdhg_handle *h);
-
-int ew_grid(int64_t len) {
-  int64_t g = (len + TPB - 1) / TPB;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(g, EW_MAX_BLOCKS));
-}
 
 inline const char *prof_scope_name(int kid) {
   static const char *names[PDHG_K_COUNT] = {"pdhg:primal (K1+K2)", "pdhg:A*xbar + dual step (K3+K4)", "pdhg:A'*y' + interaction sums (K5+K6)",

@@ -334,22 +334,32 @@ def test_group_solve_matches_single_engine_solve(gpu_required):
 
 # ---- round 3: one issuing host thread per shard, rank-local ingest, RCCL binding --------------
 
-@pytest.mark.parametrize("overlap", ["0", "1"], ids=["reduce_scatter", "per_slice_reduce"])
+@pytest.mark.parametrize("exchange", [{"PDHG_DIST_OVERLAP": "0"}, {"PDHG_DIST_OVERLAP": "1"},
+                                      {"PDHG_DIST_OVERLAP": "0", "PDHG_DIST_AG_OVERLAP": "1"}],
+                         ids=["reduce_scatter", "per_slice_reduce", "chunked_all_gather"])
 @pytest.mark.parametrize("device_ids", [[0, 0], [0] * 8], ids=["2", "8"])
-def test_thread_per_shard_issue_is_bitwise_the_single_thread_issue(gpu_required, monkeypatch, device_ids, overlap):
+def test_thread_per_shard_issue_is_bitwise_the_single_thread_issue(gpu_required, monkeypatch, device_ids, exchange):
     """pdhg_create_multi issues every shard's trial from its own host thread (ShardPool);
     PDHG_SHARD_THREADS=0 issues all of them from the caller.  Same launches, same order per
     stream, rank-ordered sums: not a bit may differ.  (Peer-kernel back end here; the RCCL
-    back end takes the same route on >= 2 GPUs, tests/test_gpu_multi_device.py.)"""
-    monkeypatch.setenv("PDHG_DIST_OVERLAP", overlap)
+    back end takes the same route on >= 2 GPUs, tests/test_gpu_multi_device.py.)
+    PDHG_GROUP_COOP=0: left to itself this LP is one the persistent group kernels take on [0, 0]
+    (test_group_trial_kernels_are_bitwise_the_per_launch_group_path), and no issuing thread touches those -- the trials
+    have to reach the launch-by-launch path for the comparison to mean anything, hence group_coop_trials == 0.
+    chunked_all_gather: the column-chunk passes of A_p xbar behind one all-gather (DistGroup::ag_chunks, peer back end)."""
+    monkeypatch.setenv("PDHG_GROUP_COOP", "0")
+    for name, value in exchange.items():
+        monkeypatch.setenv(name, value)
     p = random_lp(30000, 20000, 6, seed=21)
     runs = {}
     for threads in ("1", "0"):
         monkeypatch.setenv("PDHG_SHARD_THREADS", threads)
         eng = HipPdhgEngine.from_problem(p, device_ids=device_ids)
+        assert ("all_gather" in eng.layout_describe()) == ("PDHG_DIST_AG_OVERLAP" in exchange)
         runs[threads] = _run(eng, p, 60, 25)
         trials, issue, wait = eng.host_issue_stats()
         assert trials >= 60 and issue > 0.0
+        assert eng.layout_info()["group_coop_trials"] == 0
         eng.close()
     for key, val in runs["1"].items():
         assert np.array_equal(np.asarray(val), np.asarray(runs["0"][key])), key
