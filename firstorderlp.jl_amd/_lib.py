@@ -39,6 +39,7 @@ EXPORTS = [
     "pdhg_measure_launch_overhead", "pdhg_selftest_wave_sums", "pdhg_layout_checksums",
     "pdhg_create_batch", "pdhg_batch_member", "pdhg_batch_trial_step", "pdhg_batch_accept",
     "pdhg_batch_take_steps_adaptive",
+    "pdhg_create_fleet", "pdhg_fleet_add", "pdhg_fleet_take_steps_adaptive", "pdhg_fleet_info",
 ]
 
 ABI_VERSION = 11
@@ -221,6 +222,14 @@ def lib():
     L.pdhg_batch_accept.argtypes = [_vp, _int_p, _dp]
     L.pdhg_batch_take_steps_adaptive.restype = i32
     L.pdhg_batch_take_steps_adaptive.argtypes = [_vp, i64, d, d, _dp, _dp, _ip, _dp, _int_p, _int_p, _ip]
+    L.pdhg_create_fleet.restype = i32
+    L.pdhg_create_fleet.argtypes = [ctypes.POINTER(_vp), i32, _vp]
+    L.pdhg_fleet_add.restype = i32
+    L.pdhg_fleet_add.argtypes = [_vp, i64, i64, i64, _ip, _ip, _dp, i32, _dp, _dp, _dp, _dp, i64, ctypes.POINTER(_vp)]
+    L.pdhg_fleet_take_steps_adaptive.restype = i32
+    L.pdhg_fleet_take_steps_adaptive.argtypes = [_vp, _ip, d, d, _dp, _dp, _ip, _dp, _int_p, _ip]
+    L.pdhg_fleet_info.restype = i32
+    L.pdhg_fleet_info.argtypes = [_vp, _ip]
     L.pdhg_kernel_name.restype = ctypes.c_char_p
     L.pdhg_kernel_name.argtypes = [_vp, i32]
     L.pdhg_layout_info.restype = i32

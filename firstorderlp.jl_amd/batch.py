@@ -21,8 +21,8 @@ from . import _lib
 from .engine import HipPdhgEngine, _d, _i, _pd, _pi
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams,
                                           MalitskyPockStepsizeParameters, _check_inputs, _constant_step_estimate,
-                                          _device_scaled_problem, _host_scaled_problem, _rescales_on_device, _Solve,
-                                          adaptive_step_rule)
+                                          _device_scaled_problem, _drive_solves, _host_scaled_problem, _rescales_on_device,
+                                          _Solve, adaptive_step_rule)
 
 MAX_BATCH = 32
 _int_p = ctypes.POINTER(ctypes.c_int)
@@ -281,21 +281,20 @@ def optimize_batch(params, problems, batch_factory=None):
         for mb in members:
             mb.start(estimate)
 
-        active = list(members)
-        while active:
-            requests = {}
-            for mb in active:
-                steps = mb.evaluate()
-                if steps > 0:
-                    requests.setdefault(steps, []).append(mb)
-            active = [mb for mb in active if mb.output is None]
-            for steps, group in sorted(requests.items()):
+        def step(requests):
+            # lockstep: the members that named the same step count step together, the smaller counts first
+            groups = {}
+            for mb, steps in requests:
+                groups.setdefault(steps, []).append(mb)
+            out = []
+            for steps, group in sorted(groups.items()):
                 t0 = _time.time()
                 done = _take_steps(batch, group, steps, policy)
                 dt = _time.time() - t0
-                for mb, d in zip(group, done):
-                    mb.stepped(d, dt)
-        return [mb.output for mb in members]
+                out.extend((mb, d, dt) for mb, d in zip(group, done))
+            return out
+
+        return _drive_solves(members, step)
     finally:
         if batch is not None and hasattr(batch, "close"):
             batch.close()

@@ -250,7 +250,9 @@ int pdhg_set_objective_matrix(pdhg_handle *h0, int64_t q_nnz, const int64_t *q_c
 void pdhg_destroy(pdhg_handle *h) {
   if (!h) return;
   if (h->owner) return;               // a batch member lives and dies with its batch
+  if (h->fleet_of) return;            // ... and a fleet member with its fleet
   if (h->bat) batch_release(h);
+  if (h->fleet) fleet_release(h);
   if (h->grp) destroy_group(h->grp);
   else destroy_shard(h);
 }

@@ -558,24 +558,19 @@ static bool device_loop_for(pdhg_handle *h) {
   return device_loop;
 }
 
-/* `n_steps` consecutive take_steps (the iterations optimize() runs between two termination
- * evaluations, pdhg.jl:862-1046: nothing but take_step happens there).  Stops after the step that
- * raised numerical_error, like the reference's loop does at the top of the next iteration. */
-int pdhg_take_steps_adaptive(pdhg_handle *h, int64_t n_steps, double reduction_exponent, double growth_exponent,
-                             double *step_size_io, double primal_weight, int64_t *total_number_iterations_io,
-                             double *cumulative_kkt_passes_io, int *numerical_error_out, int64_t *steps_done_out) {
-  RoctxRange roctx_range("pdhg_take_steps_adaptive");
-  if (!steps_done_out) return fail(-1, "null argument");
-  if (n_steps < 0) return fail(-2, "pdhg_take_steps_adaptive: n_steps < 0");
-  *steps_done_out = 0;
-  if (!h || !step_size_io || !total_number_iterations_io || !cumulative_kkt_passes_io || !numerical_error_out)
-    return fail(-1, "null argument");
-  *numerical_error_out = 0;
+// The per-handle loop of pdhg_take_steps_adaptive from a given place: `s` of the n_steps are taken already, and
+// `entry` != 0 says that a multi-step launch ended inside take_step s + 1 (its table of powers ran out), with `entry`
+// that take_step's step size on entry.  pdhg_take_steps_adaptive starts it at (0, 0.0); a fleet call (abi_fleet.hpp) at
+// whatever the shared launch left of a member, and at (0, 0.0) for the members it steps singly.
+static int take_steps_adaptive_resume(pdhg_handle *h, int64_t n_steps, int64_t s, double entry, double reduction_exponent,
+                                      double growth_exponent, double *step_size_io, double primal_weight,
+                                      int64_t *total_number_iterations_io, double *cumulative_kkt_passes_io,
+                                      int *numerical_error_out, int64_t *steps_done_out) {
   const bool device_loop = device_loop_for(h);
-  int64_t s = 0;
+  *steps_done_out = s;
   while (s < n_steps) {
-    double entry = 0.0;         // nonzero: a multi-step kernel ended inside a take_step (its table of powers ran out)
-    if (n_steps - s >= 2 && !h->grp && check_handle(h) == 0 && small_lp_eligible(h)) {
+    // entry nonzero: a multi-step kernel ended inside a take_step (its table of powers ran out)
+    if (entry == 0.0 && n_steps - s >= 2 && !h->grp && check_handle(h) == 0 && small_lp_eligible(h)) {
       // a small LP: the batch in one workgroup with the vectors in LDS (small_lp_kernel.hpp)
       int64_t k = 0;
       const int rc = small_lp_steps(h, n_steps - s, reduction_exponent, growth_exponent, step_size_io, primal_weight,
@@ -608,10 +603,28 @@ int pdhg_take_steps_adaptive(pdhg_handle *h, int64_t n_steps, double reduction_e
                                            entry != 0.0 ? entry : *step_size_io, primal_weight,
                                            total_number_iterations_io, cumulative_kkt_passes_io, numerical_error_out);
     if (rc) return rc;
+    entry = 0.0;
     *steps_done_out = ++s;
     if (*numerical_error_out) break;
   }
   return 0;
+}
+
+/* `n_steps` consecutive take_steps (the iterations optimize() runs between two termination
+ * evaluations, pdhg.jl:862-1046: nothing but take_step happens there).  Stops after the step that
+ * raised numerical_error, like the reference's loop does at the top of the next iteration. */
+int pdhg_take_steps_adaptive(pdhg_handle *h, int64_t n_steps, double reduction_exponent, double growth_exponent,
+                             double *step_size_io, double primal_weight, int64_t *total_number_iterations_io,
+                             double *cumulative_kkt_passes_io, int *numerical_error_out, int64_t *steps_done_out) {
+  RoctxRange roctx_range("pdhg_take_steps_adaptive");
+  if (!steps_done_out) return fail(-1, "null argument");
+  if (n_steps < 0) return fail(-2, "pdhg_take_steps_adaptive: n_steps < 0");
+  *steps_done_out = 0;
+  if (!h || !step_size_io || !total_number_iterations_io || !cumulative_kkt_passes_io || !numerical_error_out)
+    return fail(-1, "null argument");
+  *numerical_error_out = 0;
+  return take_steps_adaptive_resume(h, n_steps, 0, 0.0, reduction_exponent, growth_exponent, step_size_io, primal_weight,
+                                    total_number_iterations_io, cumulative_kkt_passes_io, numerical_error_out, steps_done_out);
 }
 
 int pdhg_add_current_primal_to_average(pdhg_handle *h0, double weight) {

@@ -1,0 +1,130 @@
+// host_fleet.hpp -- part of the single translation unit pdhg_hip.hip (included there, after host_small_lp.hpp).
+// MANY independent small LPs in one launch (small_lp_fleet_kernel, small_lp_kernel.hpp): the fleet's state and the shared
+// launch (host side).  A solo small-LP launch is dim3(1): one of 256 compute units works.  A fleet's launch carries one
+// workgroup per member; the members share nothing on the device, so each takes its steps exactly as its solo launch would.
+//
+// Per-member host work of a shared launch: one argument block written into a pinned table (uploaded whole, once), no
+// pow() of its own -- the members' tables of powers are windows into ONE pair indexed by the absolute
+// k1 = total_number_iterations + t + 2 -- and one wait on its own result words.
+
+struct FleetState {
+  std::vector<pdhg_handle *> mem;                               // in order of addition; owned
+  SmallLpArgs *args_dev = nullptr, *args_host = nullptr;        // the argument table: device copy, pinned staging
+  size_t args_cap = 0;
+  double *pow_dev = nullptr, *pow_host = nullptr;               // [2 * pow_cap]: k1^-reduction_exponent, then k1^-growth_exponent
+  size_t pow_cap = 0;
+  int64_t launches = 0, last_carried = 0, last_single = 0;
+};
+
+// one carried member of a call
+struct FleetCarry {
+  int k = 0;                   // index in FleetState::mem
+  int n = 0, max_trials = 0, table_len = 0;
+  int64_t k1_first = 0;        // k1 of its first trial
+  bool few = false;
+  unsigned long long seq = 0;
+};
+
+int fleet_reserve(pdhg_handle *f, size_t members, size_t span) {
+  FleetState &F = *f->fleet;
+  if (F.args_cap < members) {
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    if (F.args_dev) (void)hipFree(F.args_dev);
+    if (F.args_host) (void)hipHostFree(F.args_host);
+    F.args_dev = F.args_host = nullptr;
+    F.args_cap = 0;
+    const size_t cap = std::max<size_t>(2 * members, 64);
+    HIP_TRY(hipMalloc((void **)&F.args_dev, sizeof(SmallLpArgs) * cap));
+    HIP_TRY(hipHostMalloc((void **)&F.args_host, sizeof(SmallLpArgs) * cap, hipHostMallocDefault));
+    F.args_cap = cap;
+  }
+  if (F.pow_cap < span) {
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    if (F.pow_dev) (void)hipFree(F.pow_dev);
+    if (F.pow_host) (void)hipHostFree(F.pow_host);
+    F.pow_dev = F.pow_host = nullptr;
+    F.pow_cap = 0;
+    const size_t cap = std::max<size_t>(2 * span, 1024);
+    HIP_TRY(hipMalloc((void **)&F.pow_dev, sizeof(double) * 2 * cap));
+    HIP_TRY(hipHostMalloc((void **)&F.pow_host, sizeof(double) * 2 * cap, hipHostMallocDefault));
+    F.pow_cap = cap;
+  }
+  return 0;
+}
+
+// The shared launch of `carry` (every entry small_lp_eligible, n >= 2): at most two kernel launches back to back -- the
+// members of up to SMALL_FEW_ROWS rows and columns with 256 threads, the others with SMALL_TPB, the solo rule -- then one
+// wait per member.  On return steps_done[k] / entry[k] hold what small_lp_steps would have reported for member k.
+int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry, double reduction_exponent, double growth_exponent,
+                 double *step_size, const double *primal_weight, int64_t *total_number_iterations,
+                 double *cumulative_kkt_passes, int *numerical_error, int64_t *steps_done, double *entry) {
+  FleetState &F = *f->fleet;
+  if (carry.empty()) return 0;
+  HIP_TRY(hipSetDevice(f->device));
+  int rc;
+  // the tables of powers: one pair for the call, from the smallest to the largest k1 a member can reach
+  int64_t lo = INT64_MAX, hi = 0;
+  for (FleetCarry &c : carry) {
+    pdhg_handle *h = F.mem[(size_t)c.k];
+    if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
+    if ((rc = steps_result_words(h))) return rc;
+    steps_budget(c.n, &c.max_trials, &c.table_len);
+    c.k1_first = total_number_iterations[c.k] + 2;      // (steps_prepare: trial t of the launch uses k1 = total + t + 2)
+    c.few = small_lp_few_rows(h);
+    lo = std::min(lo, c.k1_first);
+    hi = std::max(hi, c.k1_first + c.table_len);          // one past the last
+  }
+  const size_t span = (size_t)(hi - lo);
+  if ((rc = fleet_reserve(f, carry.size(), span))) return rc;
+  {
+    // every entry a member can read is the host pow() steps_prepare computes; entries no member covers stay as they are
+    std::vector<std::pair<int64_t, int64_t>> iv;
+    for (const FleetCarry &c : carry) iv.emplace_back(c.k1_first, c.k1_first + c.table_len);
+    std::sort(iv.begin(), iv.end());
+    int64_t done_to = lo;
+    for (const auto &v : iv) {
+      for (int64_t k1 = std::max(done_to, v.first); k1 < v.second; ++k1) {
+        F.pow_host[(size_t)(k1 - lo)] = pow((double)k1, -reduction_exponent);
+        F.pow_host[span + (size_t)(k1 - lo)] = pow((double)k1, -growth_exponent);
+      }
+      done_to = std::max(done_to, v.second);
+    }
+    HIP_TRY(hipMemcpyAsync(F.pow_dev, F.pow_host, sizeof(double) * 2 * span, hipMemcpyHostToDevice, f->stream));
+  }
+  // launch order: the 256-thread members first, each part by descending nnz (the long members start first, the tail is short)
+  std::stable_sort(carry.begin(), carry.end(), [&](const FleetCarry &a, const FleetCarry &b) {
+    if (a.few != b.few) return a.few;
+    return F.mem[(size_t)a.k]->nnz > F.mem[(size_t)b.k]->nnz;
+  });
+  size_t n_few = 0, lds_few = 0, lds_big = 0;
+  for (size_t i = 0; i < carry.size(); ++i) {
+    FleetCarry &c = carry[i];
+    pdhg_handle *h = F.mem[(size_t)c.k];
+    const size_t off = (size_t)(c.k1_first - lo);
+    F.args_host[i] = small_lp_stage(h, c.n, c.max_trials, c.table_len, step_size[c.k], primal_weight[c.k], F.pow_dev + off,
+                                    F.pow_dev + span + off);
+    c.seq = F.args_host[i].seq;
+    if (c.few) { n_few += 1; lds_few = std::max(lds_few, small_lp_lds_bytes(h)); }
+    else lds_big = std::max(lds_big, small_lp_lds_bytes(h));
+  }
+  if ((rc = small_lp_lds_limit(f->device, 1, std::max(lds_few, lds_big)))) return rc;
+  HIP_TRY(hipMemcpyAsync(F.args_dev, F.args_host, sizeof(SmallLpArgs) * carry.size(), hipMemcpyHostToDevice, f->stream));
+  const size_t n_big = carry.size() - n_few;
+  if (n_few > 0) {
+    hipLaunchKernelGGL(small_lp_fleet_kernel<256>, dim3((unsigned)n_few), dim3(256), lds_few, f->stream,
+                       (const SmallLpArgs *)F.args_dev, (int)n_few);
+    F.launches += 1;
+  }
+  if (n_big > 0) {
+    hipLaunchKernelGGL(small_lp_fleet_kernel<SMALL_TPB>, dim3((unsigned)n_big), dim3(SMALL_TPB), lds_big, f->stream,
+                       (const SmallLpArgs *)(F.args_dev + n_few), (int)n_big);
+    F.launches += 1;
+  }
+  HIP_TRY(hipGetLastError());
+  for (const FleetCarry &c : carry) {
+    if ((rc = small_lp_collect(F.mem[(size_t)c.k], c.seq, &step_size[c.k], &total_number_iterations[c.k], &cumulative_kkt_passes[c.k],
+                               &numerical_error[c.k], &steps_done[c.k], &entry[c.k])))
+      return rc;
+  }
+  return 0;
+}

@@ -16,6 +16,73 @@ bool small_lp_eligible(pdhg_handle *h) {
   return h->small_lp_mode == 1 && !h->profile;
 }
 
+// The opt-in for the launch's dynamic LDS (beyond 64 KiB), per device and kernel instance; it only ever grows
+// (ensure_lds_limit's reasoning).  `which`: 0 the solo instantiations, 1 the fleet's.
+int small_lp_lds_limit(int device, int which, size_t lds) {
+  static size_t limit[64][2] = {};
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  size_t &cur = limit[device & 63][which];
+  if (cur < lds) {
+    if (which == 0) {
+      HIP_TRY(hipFuncSetAttribute((const void *)small_lp_steps_kernel<SMALL_TPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      HIP_TRY(hipFuncSetAttribute((const void *)small_lp_steps_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    } else {
+      HIP_TRY(hipFuncSetAttribute((const void *)small_lp_fleet_kernel<SMALL_TPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      HIP_TRY(hipFuncSetAttribute((const void *)small_lp_fleet_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    cur = lds;
+  }
+  return 0;
+}
+
+size_t small_lp_lds_bytes(const pdhg_handle *h) { return sizeof(double) * (9 * (size_t)h->n + 4 * (size_t)h->m); }
+
+// 256 threads up to this many rows / columns, SMALL_TPB beyond (small_lp_kernel.hpp)
+bool small_lp_few_rows(const pdhg_handle *h) {
+  static const int few_env = dev_env("PDHG_SMALL_FEW_ROWS") ? atoi(dev_env("PDHG_SMALL_FEW_ROWS")) : SMALL_FEW_ROWS;   // dev knob
+  return std::max(h->n, h->m) <= few_env;
+}
+
+// The argument block of a launch of up to n take_steps of h (solo, or as one entry of a fleet's table): takes the next
+// sequence number of the handle's result words and hands the deferred average update to the launch.
+SmallLpArgs small_lp_stage(pdhg_handle *h, int n, int max_trials, int table_len, double step_size, double primal_weight,
+                           const double *pow_red, const double *pow_growth) {
+  SmallLpArgs a{};
+  a.n = (int)h->n; a.m = (int)h->m; a.num_eq = (int)h->num_eq;
+  a.A = h->A.view(); a.T = h->At.view();
+  a.x = h->x; a.y = h->y; a.aty = h->aty; a.sum_x = h->sum_x; a.sum_y = h->sum_y;
+  a.c = h->c; a.lb = h->lb; a.ub = h->ub; a.b = h->b;
+  a.primal_weight = primal_weight; a.step_size = step_size;
+  a.n_steps = n; a.max_trials = max_trials; a.table_len = table_len;
+  a.pend = h->pend_x ? 1 : 0; a.pend_w = h->pend_w;
+  a.wsum_x = h->sum_x_weights; a.wsum_y = h->sum_y_weights;
+  a.pow_red = pow_red; a.pow_growth = pow_growth;
+  a.res_host = h->steps_res;
+  a.seq = ++h->steps_seq;
+  h->pend_x = h->pend_y = false;             // the launch applies it
+  return a;
+}
+
+// Wait for launch `seq` of h and take its results into the handle's bookkeeping and the caller's scalars.
+int small_lp_collect(pdhg_handle *h, unsigned long long seq, double *step_size_io, int64_t *total_number_iterations_io,
+                     double *cumulative_kkt_passes_io, int *numerical_error_out, int64_t *steps_done, double *unfinished_entry) {
+  double r[13], r14 = 0.0;
+  if (int rc = steps_wait(h, seq, r, &r14)) return rc;
+  const int64_t steps = (int64_t)r[1], trials = (int64_t)r[2];
+  h->small_lp_launches += 1; h->n_graph_trials += trials;
+  h->sum_x_count += steps; h->sum_y_count += steps;
+  h->sum_x_weights = r[6]; h->sum_y_weights = r[7];
+  h->state_version += 1;
+  *step_size_io = r[0];
+  *total_number_iterations_io += trials;
+  *cumulative_kkt_passes_io += (double)trials;
+  *steps_done = steps;
+  *unfinished_entry = r14;
+  if (r[8] != 0.0) { *numerical_error_out = 1; *steps_done = steps + 1; }
+  return 0;
+}
+
 // returns 1 when not eligible (nothing launched)
 int small_lp_steps(pdhg_handle *h, int64_t n_steps, double reduction_exponent, double growth_exponent, double *step_size_io,
                    double primal_weight, int64_t *total_number_iterations_io, double *cumulative_kkt_passes_io,
@@ -29,52 +96,18 @@ int small_lp_steps(pdhg_handle *h, int64_t n_steps, double reduction_exponent, d
   const int n = (int)std::min<int64_t>(n_steps, 1 << 20);
   int max_trials = 0, table_len = 0;
   if ((rc = steps_prepare(h, n, *total_number_iterations_io, reduction_exponent, growth_exponent, &max_trials, &table_len))) return rc;
-  const size_t lds = sizeof(double) * (9 * (size_t)h->n + 4 * (size_t)h->m);
-  {
-    static size_t limit[64] = {};
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    size_t &cur = limit[h->device & 63];
-    if (cur < lds) {
-      HIP_TRY(hipFuncSetAttribute((const void *)small_lp_steps_kernel<SMALL_TPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      HIP_TRY(hipFuncSetAttribute((const void *)small_lp_steps_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      cur = lds;
-    }
-  }
-
-  SmallLpArgs a{};
-  a.n = (int)h->n; a.m = (int)h->m; a.num_eq = (int)h->num_eq;
-  a.A = h->A.view(); a.T = h->At.view();
-  a.x = h->x; a.y = h->y; a.aty = h->aty; a.sum_x = h->sum_x; a.sum_y = h->sum_y;
-  a.c = h->c; a.lb = h->lb; a.ub = h->ub; a.b = h->b;
-  a.primal_weight = primal_weight; a.step_size = *step_size_io;
-  a.n_steps = n; a.max_trials = max_trials; a.table_len = table_len;
-  a.pend = h->pend_x ? 1 : 0; a.pend_w = h->pend_w;
-  a.wsum_x = h->sum_x_weights; a.wsum_y = h->sum_y_weights;
-  a.pow_red = h->steps_pow_dev; a.pow_growth = h->steps_pow_dev + table_len;
-  a.res_host = h->steps_res;
-  a.seq = ++h->steps_seq;
-  h->pend_x = h->pend_y = false;             // the launch applies it
+  const size_t lds = small_lp_lds_bytes(h);
+  if ((rc = small_lp_lds_limit(h->device, 0, lds))) return rc;
+  const SmallLpArgs a = small_lp_stage(h, n, max_trials, table_len, *step_size_io, primal_weight, h->steps_pow_dev,
+                                       h->steps_pow_dev + table_len);
   const auto c1 = std::chrono::steady_clock::now();
-  static const int few_env = dev_env("PDHG_SMALL_FEW_ROWS") ? atoi(dev_env("PDHG_SMALL_FEW_ROWS")) : SMALL_FEW_ROWS;   // dev knob
-  if (std::max(h->n, h->m) <= few_env) hipLaunchKernelGGL(small_lp_steps_kernel<256>, dim3(1), dim3(256), lds, h->stream, a);
+  if (small_lp_few_rows(h)) hipLaunchKernelGGL(small_lp_steps_kernel<256>, dim3(1), dim3(256), lds, h->stream, a);
   else hipLaunchKernelGGL(small_lp_steps_kernel<SMALL_TPB>, dim3(1), dim3(SMALL_TPB), lds, h->stream, a);
   HIP_TRY(hipGetLastError());
   const auto c2 = std::chrono::steady_clock::now();
   h->t_launch += std::chrono::duration<double>(c2 - c1).count();
-  double r[13], r14 = 0.0;
-  if ((rc = steps_wait(h, a.seq, r, &r14))) return rc;
+  rc = small_lp_collect(h, a.seq, step_size_io, total_number_iterations_io, cumulative_kkt_passes_io, numerical_error_out,
+                        steps_done, unfinished_entry);
   h->t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - c2).count();
-  const int64_t steps = (int64_t)r[1], trials = (int64_t)r[2];
-  h->small_lp_launches += 1; h->n_graph_trials += trials;
-  h->sum_x_count += steps; h->sum_y_count += steps;
-  h->sum_x_weights = r[6]; h->sum_y_weights = r[7];
-  h->state_version += 1;
-  *step_size_io = r[0];
-  *total_number_iterations_io += trials;
-  *cumulative_kkt_passes_io += (double)trials;
-  *steps_done = steps;
-  *unfinished_entry = r14;
-  if (r[8] != 0.0) { *numerical_error_out = 1; *steps_done = steps + 1; }
-  return 0;
+  return rc;
 }

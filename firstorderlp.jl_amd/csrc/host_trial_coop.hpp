@@ -190,14 +190,26 @@ int coop_trial(pdhg_handle *h, double step_size, double primal_weight, double th
 // uploaded), the pinned result words.  Budget: the steps asked for plus room for rejections (a launch that runs out
 // returns at a take_step boundary and the caller launches again); 64 more table entries for finishing the take_step
 // the budget ends in.  The tables cost two pow() per entry on the host: sized to the batch, not to the worst case.
-static int steps_prepare(pdhg_handle *h, int n, int64_t total_number_iterations, double reduction_exponent,
-                         double growth_exponent, int *max_trials_out, int *table_len_out) {
+// (steps_budget: the budget alone; steps_result_words: the pinned result words alone -- a many-LP launch, host_fleet.hpp,
+//  takes both per member and builds ONE pair of tables for all of them)
+static void steps_budget(int n, int *max_trials_out, int *table_len_out) {
   int max_trials = n + n / 8 + 16, table_len = max_trials + 64;
   if (const char *tv = dev_env("PDHG_STEPS_TEST_TABLE")) max_trials = table_len = std::max(1, atoi(tv));   // test knob: launches end inside take_steps
+  *max_trials_out = max_trials;
+  *table_len_out = table_len;
+}
+static int steps_result_words(pdhg_handle *h) {
   if (!h->steps_res) {
     HIP_TRY(hipHostMalloc((void **)&h->steps_res, STEPS_RES_WORDS * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
     memset(h->steps_res, 0, STEPS_RES_WORDS * sizeof(double));
   }
+  return 0;
+}
+static int steps_prepare(pdhg_handle *h, int n, int64_t total_number_iterations, double reduction_exponent,
+                         double growth_exponent, int *max_trials_out, int *table_len_out) {
+  int max_trials = 0, table_len = 0;
+  steps_budget(n, &max_trials, &table_len);
+  if (int rc = steps_result_words(h)) return rc;
   if (h->steps_pow_cap < table_len) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (h->steps_pow_dev) (void)hipFree(h->steps_pow_dev);

@@ -308,6 +308,7 @@ int graph_trial(pdhg_handle *h, double step_size, double primal_weight, double t
 // queues_work: the entry point may put work on the shards' own streams (everything but a trial step and a lazy accept)
 int check_handle(pdhg_handle *h, bool queues_work = true, bool batch_ok = false) {
   if (!h) return fail(-1, "null handle");
+  if (h->fleet) return fail(-1, "a fleet handle runs no iterations of its own: call this on a member (pdhg_fleet_add)");
   if (h->bat && !batch_ok) return fail(-1, "a batch handle holds the shared matrix only: call this on a member (pdhg_batch_member)");
   if (queues_work && h->grp && !h->grp->coop_dev.empty()) {
     DistGroup &g = *h->grp;

@@ -51,7 +51,7 @@
 #include "tr_coop_kernel.hpp"
 #include "batch_kernels.hpp"
 
-namespace { struct DistGroup; }
+namespace { struct DistGroup; struct FleetState; }
 struct BatchState;
 
 struct pdhg_handle {
@@ -216,6 +216,12 @@ struct pdhg_handle {
   // vectors); a member's A / At are the batch's layouts, borrowed (`owner` = the batch): it is freed with the batch.
   BatchState *bat = nullptr;
   pdhg_handle *owner = nullptr;
+
+  // ---- fleets of independent small LPs (abi_fleet.hpp).  A fleet handle owns `fleet` (its members, the argument table
+  // and the shared tables of powers of a many-LP launch) and runs no iterations of its own; a member is a complete
+  // handle of its own -- matrix included -- on the fleet's device and stream (`fleet_of` = the fleet, which frees it).
+  FleetState *fleet = nullptr;
+  pdhg_handle *fleet_of = nullptr;
 };
 
 #include "dist.hpp"
@@ -595,6 +601,7 @@ int launch_final(pdhg_handle *h, const double *p_int, int n_int, int stride_int,
 #include "host_trial_graph.hpp"
 #include "host_trial_coop.hpp"
 #include "host_small_lp.hpp"
+#include "host_fleet.hpp"
 #include "host_trial_graph_build.hpp"
 #include "host_shards.hpp"
 }  // namespace
@@ -742,6 +749,7 @@ int pdhg_create(pdhg_handle **out, int64_t m, int64_t n, int64_t nnz,
 }
 
 static void batch_release(pdhg_handle *h);
+static void fleet_release(pdhg_handle *h);
 static int batch_scale_members(pdhg_handle *h, const double *dv, const double *ev);
 
 #include "abi_dist.hpp"
@@ -750,4 +758,5 @@ static int batch_scale_members(pdhg_handle *h, const double *dv, const double *e
 #include "abi_rescale.hpp"
 #include "abi_measure.hpp"
 #include "abi_batch.hpp"
+#include "abi_fleet.hpp"
 }  // extern "C"

@@ -56,8 +56,10 @@ __device__ __forceinline__ double small_row_sum(const CsrView &M, int r, const d
   return s;
 }
 
+// The whole launch of one LP: what a workgroup does with one argument block, whoever handed it over -- the solo kernel
+// (the block by value) or the fleet kernel (its entry of a table in device memory).
 template <int THREADS>
-__global__ __launch_bounds__(THREADS) void small_lp_steps_kernel(SmallLpArgs a) {
+__device__ __forceinline__ void small_lp_steps_body(const SmallLpArgs &a) {
   extern __shared__ double lds[];
   __shared__ double red[6][THREADS / WAVE];
   __shared__ double s_dec[3];
@@ -172,6 +174,23 @@ __global__ __launch_bounds__(THREADS) void small_lp_steps_kernel(SmallLpArgs a) 
     a.res_host[13] = __longlong_as_double((long long)ck);
     a.res_host[15] = (double)a.seq;
   }
+}
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void small_lp_steps_kernel(SmallLpArgs a) {
+  small_lp_steps_body<THREADS>(a);
+}
+
+// MANY small LPs in one launch (host_fleet.hpp): workgroup b runs entry b of `table` to the end of ITS n_steps, exactly
+// as a solo launch would -- its own accepts and rejections, its own tables of powers (pointers into the call's shared
+// pair), its own pinned result words.  The workgroups share nothing, so up to one per compute unit they run side by side;
+// beyond that the dispatcher hands out the rest as compute units fall free (the table is ordered longest first).  The
+// dynamic LDS of the launch is the largest member's; a smaller member uses the front of it.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void small_lp_fleet_kernel(const SmallLpArgs *__restrict__ table, int count) {
+  if ((int)blockIdx.x >= count) return;
+  const SmallLpArgs a = table[blockIdx.x];          // (uniform, read before any store: scalar loads)
+  small_lp_steps_body<THREADS>(a);
 }
 
 }  // namespace

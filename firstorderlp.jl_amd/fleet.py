@@ -1,0 +1,196 @@
+"""Many independent small LPs at once, one workgroup per LP.
+
+``optimize_many(params, problems)`` returns what ``optimize(params, problems[k])`` returns, for every k.  The problems
+share nothing -- any mix of shapes, LPs and QPs.  What they share is the launch: an LP small enough for the solo
+small-LP path (csrc/small_lp_kernel.hpp: every vector in one workgroup's LDS) takes its steps between two evaluations in
+one workgroup, and ``pdhg_fleet_take_steps_adaptive`` carries one such workgroup per problem in one launch instead of one
+launch per problem on one of 256 compute units.  The members do not run in lockstep: each accepts, rejects, restarts and
+terminates on its own, at the iterations ``optimize`` would.  Both drivers run the same per-problem solve object
+(``primal_dual_hybrid_gradient._Solve``); the evaluations between the steps stay per member and serial.
+
+``HipPdhgFleet`` is the device side: one fleet handle that owns K ordinary member handles on one stream (``.members``:
+``HipPdhgEngine`` views -- every single-LP method works on them, ``rescale`` included: a member's matrix is its own).
+"""
+import ctypes
+import os
+import time as _time
+
+import numpy as np
+
+from . import _lib
+from .engine import HipPdhgEngine, _d, _i, _pd, _pi
+from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams, _check_inputs,
+                                          _constant_step_estimate, _device_scaled_problem, _drive_solves,
+                                          _host_scaled_problem, _rescales_on_device, _Solve, take_steps)
+
+_int_p = ctypes.POINTER(ctypes.c_int)
+
+
+class _MemberEngine(HipPdhgEngine):
+    """A non-owning view of a member: the fleet frees it (``close`` only forgets the handle)."""
+
+    def close(self):
+        self._h = None
+
+
+class HipPdhgFleet:
+    """K independent problems on one GPU and one stream (``pdhg_create_fleet`` / ``pdhg_fleet_add``)."""
+
+    takes_original_problem = True
+
+    def __init__(self, device_id=-1, stream=None):
+        self._L = _lib.lib()
+        h = ctypes.c_void_p()
+        _lib.check(self._L.pdhg_create_fleet(ctypes.byref(h), int(device_id), ctypes.c_void_p(stream) if stream else None))
+        self._h = h
+        self.members = []
+
+    @property
+    def K(self):
+        return len(self.members)
+
+    def add(self, problem):
+        """A new member from a problem (``pdhg_fleet_add``; a QP's objective matrix is uploaded to the member)."""
+        A = problem.constraint_matrix.tocsc()
+        m, n = int(A.shape[0]), int(A.shape[1])
+        colptr, rowval, nzval = _i(A.indptr), _i(A.indices), _d(A.data)
+        c, b = _d(problem.objective_vector), _d(problem.right_hand_side)
+        lb, ub = _d(problem.variable_lower_bound), _d(problem.variable_upper_bound)
+        if c.shape != (n,) or lb.shape != (n,) or ub.shape != (n,) or b.shape != (m,):
+            raise ValueError("vector lengths do not match the constraint matrix")
+        mh = ctypes.c_void_p()
+        _lib.check(self._L.pdhg_fleet_add(self._h, m, n, len(nzval), _pi(colptr), _pi(rowval), _pd(nzval), 0, _pd(c),
+                                          _pd(b), _pd(lb), _pd(ub), int(problem.num_equalities), ctypes.byref(mh)))
+        eng = _MemberEngine._wrap(self._L, mh, m, n)
+        self.members.append(eng)
+        eng._upload_objective_matrix(problem.objective_matrix)
+        return eng
+
+    @classmethod
+    def from_problems(cls, problems, device_id=-1, stream=None):
+        problems = list(problems)
+        if not problems:
+            raise ValueError("a fleet needs at least one problem")
+        fleet = cls(device_id=device_id, stream=stream)
+        try:
+            for p in problems:
+                fleet.add(p)
+        except Exception:
+            fleet.close()
+            raise
+        return fleet
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for eng in self.members:
+                eng._h = None
+            self._L.pdhg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def take_steps_adaptive(self, n_steps, reduction_exponent, growth_exponent, step_sizes, primal_weights,
+                            total_number_iterations, cumulative_kkt_passes):
+        """``n_steps[k]`` take_steps of member k, for every k (0: the member is left alone); the small LPs among them in
+        one launch.  Returns arrays (step_sizes, total_number_iterations, cumulative_kkt_passes, numerical_error,
+        steps_done)."""
+        K = self.K
+        ns = np.array(np.broadcast_to(n_steps, (K,)), dtype=np.int64)
+        ss = _d(np.array(np.broadcast_to(step_sizes, (K,)), dtype=np.float64))
+        pw = _d(np.array(np.broadcast_to(primal_weights, (K,)), dtype=np.float64))
+        it = np.array(np.broadcast_to(total_number_iterations, (K,)), dtype=np.int64)
+        kkt = _d(np.array(np.broadcast_to(cumulative_kkt_passes, (K,)), dtype=np.float64))
+        err = np.zeros(K, dtype=np.int32)
+        done = np.zeros(K, dtype=np.int64)
+        _lib.check(self._L.pdhg_fleet_take_steps_adaptive(
+            self._h, _pi(ns), float(reduction_exponent), float(growth_exponent), _pd(ss), _pd(pw), _pi(it), _pd(kkt),
+            err.ctypes.data_as(_int_p), _pi(done)))
+        return ss, it, kkt, err.astype(bool), done
+
+    def info(self):
+        """dict(members, shared_launches, carried, single): the last two describe the last ``take_steps_adaptive``."""
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(self._L.pdhg_fleet_info(self._h, _pi(info)))
+        return dict(zip(["members", "shared_launches", "carried", "single"], info[:4].tolist()))
+
+
+def _default_fleet_factory(problems):
+    return HipPdhgFleet.from_problems(problems)
+
+
+_default_fleet_factory.takes_original_problem = True
+
+
+def _step_fleet(fleet, solves, policy, requests):
+    """The steps the members named at this round: one ``take_steps_adaptive`` of the fleet for all of them under the
+    adaptive policy, else (another policy, PDHG_PY_TAKE_STEP=1, a fleet without the native call) member by member
+    through ``take_steps``.  Returns (solve, steps taken, seconds) per request."""
+    if (isinstance(policy, AdaptiveStepsizeParams) and hasattr(fleet, "take_steps_adaptive")
+            and os.environ.get("PDHG_PY_TAKE_STEP", "0") != "1"):
+        K = len(solves)
+        slot = {id(mb): k for k, mb in enumerate(solves)}
+        ns, it = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+        ss, pw, kkt = np.ones(K), np.ones(K), np.zeros(K)
+        for mb, steps in requests:
+            k = slot[id(mb)]
+            ns[k] = steps
+            ss[k], pw[k] = mb.state.step_size, mb.state.primal_weight
+            it[k], kkt[k] = mb.state.total_number_iterations, mb.state.cumulative_kkt_passes
+        t0 = _time.time()
+        ss, it, kkt, err, done = fleet.take_steps_adaptive(ns, policy.reduction_exponent, policy.growth_exponent, ss, pw,
+                                                           it, kkt)
+        dt = _time.time() - t0
+        out = []
+        for mb, _ in requests:
+            k = slot[id(mb)]
+            mb.state.step_size, mb.state.total_number_iterations = float(ss[k]), int(it[k])
+            mb.state.cumulative_kkt_passes = float(kkt[k])
+            if err[k]:
+                mb.state.numerical_error = True
+            out.append((mb, int(done[k]), dt))
+        return out
+    out = []
+    for mb, steps in requests:
+        t0 = _time.time()
+        done = take_steps(policy, mb.state, steps, mb.is_lp)
+        out.append((mb, done, _time.time() - t0))
+    return out
+
+
+def optimize_many(params, problems, fleet_factory=None):
+    """``optimize(params, problems[k])`` for every k, side by side: a list of ``SaddlePointOutput`` in input order.
+
+    Anything ``optimize`` accepts: any mix of shapes, LPs and QPs, every step-size policy, any number of problems (an
+    empty list raises ``ValueError`` before any device work).  ``fleet_factory(problems) -> fleet`` builds the device
+    side (default ``HipPdhgFleet``): an object with ``.members`` (one engine per problem, in order), ``close()`` and,
+    optionally, ``take_steps_adaptive``; a factory whose ``takes_original_problem`` is true receives the original
+    problems and every member rescales on the device, any other one receives the host-rescaled problems."""
+    problems = list(problems)
+    if not problems:
+        raise ValueError("optimize_many needs at least one problem")
+    _check_inputs(params, problems)
+    policy = params.step_size_policy_params
+    factory = fleet_factory or _default_fleet_factory
+    fleet = None
+    try:
+        if _rescales_on_device(factory):
+            fleet = factory(problems)
+            scaled, max_abs = [], []
+            for p, eng in zip(problems, fleet.members):
+                E, D = eng.rescale(params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
+                scaled.append(_device_scaled_problem(p, eng, E, D))
+                max_abs.append(eng.matrix_max_abs())
+        else:
+            scaled, max_abs = zip(*[_host_scaled_problem(params, p) for p in problems])
+            fleet = factory([s.scaled_qp for s in scaled])
+        solves = [_Solve(params, p, s, eng, a) for p, s, eng, a in zip(problems, scaled, fleet.members, max_abs)]
+        for mb in solves:
+            mb.start(_constant_step_estimate(mb) if isinstance(policy, ConstantStepsizeParams) else None)
+        return _drive_solves(solves, lambda requests: _step_fleet(fleet, solves, policy, requests))
+    finally:
+        if fleet is not None and hasattr(fleet, "close"):
+            fleet.close()

@@ -534,6 +534,25 @@ class _Solve:
         self.time_spent_doing_basic_algorithm += seconds
 
 
+def _drive_solves(solves, step):
+    """The outer loop of several solves side by side (``batch.optimize_batch``, ``fleet.optimize_many``): at each
+    round every active solve evaluates and names its step count, a solve that terminated leaves, and
+    ``step(requests)`` -- ``requests`` = [(solve, steps)] in the solves' order -- takes those steps and returns
+    (solve, steps taken, seconds) for each.  Returns the outputs in the solves' order."""
+    active = list(solves)
+    while active:
+        requests = []
+        for mb in active:
+            steps = mb.evaluate()
+            if steps > 0:
+                requests.append((mb, steps))
+        active = [mb for mb in active if mb.output is None]
+        if requests:
+            for mb, done, seconds in step(requests):
+                mb.stepped(done, seconds)
+    return [mb.output for mb in solves]
+
+
 def optimize(params, original_problem, engine_factory=None):
     """``optimize(params::PdhgParameters, original_problem)`` -- pdhg.jl:782-1049.
 

@@ -524,6 +524,45 @@ int pdhg_batch_take_steps_adaptive(pdhg_handle *batch, int64_t n_steps, double r
                                    double *cumulative_kkt_passes, int *numerical_error,
                                    const int *active, int64_t *steps_done);
 
+/*
+ * ---- fleets: many independent small LPs stepped by one launch ---------------------------------
+ * No reference counterpart (the reference solves one LP per call); every member runs the reference's
+ * take_step (src/primal_dual_hybrid_gradient.jl:653-731) on its own LP.  Unlike a batch, the members
+ * share NOTHING: each has its own matrix, shape and vectors.  What they share is the launch: an LP
+ * whose vectors fit one workgroup's LDS takes a run of take_steps in one workgroup (the solo small-LP
+ * path, launched on one of 256 compute units); a fleet's launch carries one such workgroup per member.
+ *
+ * pdhg_create_fleet: an empty fleet on `device_id` (< 0: the current device) and `stream` (NULL: a
+ * stream of its own).  The fleet handle runs no iterations: every single-LP entry point refuses it
+ * with -1.  pdhg_destroy frees the fleet and its members.
+ */
+int pdhg_create_fleet(pdhg_handle **out, int device_id, void *stream);
+/* A new member: what pdhg_create makes of the same arguments, on the fleet's device and stream.  Every
+ * single-LP entry point works on it, pdhg_rescale and pdhg_set_objective_matrix included (its matrix is
+ * its own).  The fleet owns it: pdhg_destroy on a member does nothing.  Members keep the order they
+ * were added in; that order indexes the arrays of the calls below. */
+int pdhg_fleet_add(pdhg_handle *fleet, int64_t m, int64_t n, int64_t nnz, const int64_t *colptr,
+                   const int64_t *rowval, const double *nzval, int index_base, const double *c,
+                   const double *b, const double *lb, const double *ub, int64_t num_equalities,
+                   pdhg_handle **member);
+/* pdhg_take_steps_adaptive(member k, n_steps[k], ..., &step_size[k], primal_weight[k], ...) for every
+ * member k -- the same results bit for bit -- with all arrays one entry per member.  n_steps[k] == 0:
+ * member k and its entries are neither read nor written.  The members do NOT run in lockstep: each
+ * accepts and rejects on its own.  Members that take the solo small-LP path (an LP with 9n + 4m
+ * doubles <= 144 KB and rows of <= 256 entries) and ask for >= 2 steps are carried by one shared
+ * launch (two when shapes up to and beyond 256 rows are mixed); every other member (a QP, longer rows,
+ * a single step) and whatever the launch left of a carried one is stepped in turn, inside this call.
+ * Null arrays return -1, a handle that is not a fleet -1, n_steps[k] < 0 returns -2: nothing is
+ * launched. */
+int pdhg_fleet_take_steps_adaptive(pdhg_handle *fleet, const int64_t *n_steps, double reduction_exponent,
+                                   double growth_exponent, double *step_size,
+                                   const double *primal_weight, int64_t *total_number_iterations,
+                                   double *cumulative_kkt_passes, int *numerical_error,
+                                   int64_t *steps_done);
+/* info[0] members, info[1] shared launches so far, info[2] members carried by the shared launch of the
+ * last pdhg_fleet_take_steps_adaptive, info[3] members that call stepped singly, info[4..7] 0. */
+int pdhg_fleet_info(pdhg_handle *fleet, int64_t info[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1037,4 +1037,51 @@ function batch_take_steps_adaptive(batch::Ptr{Cvoid}, n_steps::Integer, reductio
   return numerical_error, steps_done
 end
 
+# ---- fleets: many independent small LPs stepped by one launch (include/pdhg_hip.h) --------------------------
+"""Problems of any shapes as a fleet (`pdhg_create_fleet`, `pdhg_fleet_add`): returns (fleet handle, member handles).
+Every single-LP call above works on a member (wrap one in a `HipSolverState`-like holder without a finalizer:
+`pdhg_destroy` on a member does nothing, `destroy_fleet` frees the fleet and its members)."""
+function create_fleet(problems::Vector{FirstOrderLp.QuadraticProgrammingProblem}; device_id::Integer = -1)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ccall((:pdhg_create_fleet, LIB), Cint, (Ref{Ptr{Cvoid}}, Cint, Ptr{Cvoid}), h, device_id, C_NULL))
+  members = Ptr{Cvoid}[]
+  for p in problems
+    A = p.constraint_matrix
+    m, n = size(A)
+    mh = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pdhg_fleet_add, LIB), Cint,
+      (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint,
+       Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Ptr{Cvoid}}),
+      h[], m, n, length(A.nzval), A.colptr, A.rowval, A.nzval, 1, p.objective_vector, p.right_hand_side,
+      p.variable_lower_bound, p.variable_upper_bound, p.num_equalities, mh))
+    push!(members, mh[])
+  end
+  return h[], members
+end
+
+destroy_fleet(fleet::Ptr{Cvoid}) = ccall((:pdhg_destroy, LIB), Cvoid, (Ptr{Cvoid},), fleet)
+
+"`n_steps[k]` adaptive take_steps of member k, for every k, the small LPs in one launch (`pdhg_fleet_take_steps_adaptive`); the vectors are updated in place."
+function fleet_take_steps_adaptive(fleet::Ptr{Cvoid}, n_steps::Vector{Int64}, reduction_exponent::Float64,
+                                   growth_exponent::Float64, step_size::Vector{Float64},
+                                   primal_weight::Vector{Float64}, total_number_iterations::Vector{Int64},
+                                   cumulative_kkt_passes::Vector{Float64})
+  K = length(n_steps)
+  numerical_error = zeros(Cint, K)
+  steps_done = zeros(Int64, K)
+  check(ccall((:pdhg_fleet_take_steps_adaptive, LIB), Cint,
+    (Ptr{Cvoid}, Ptr{Int64}, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Cint},
+     Ptr{Int64}),
+    fleet, n_steps, reduction_exponent, growth_exponent, step_size, primal_weight, total_number_iterations,
+    cumulative_kkt_passes, numerical_error, steps_done))
+  return numerical_error, steps_done
+end
+
+"(members, shared launches so far, members carried by the last call, members it stepped singly) (`pdhg_fleet_info`)."
+function fleet_info(fleet::Ptr{Cvoid})
+  info = zeros(Int64, 8)
+  check(ccall((:pdhg_fleet_info, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), fleet, info))
+  return info[1], info[2], info[3], info[4]
+end
+
 end # module
