@@ -18,27 +18,21 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _lib
-from .engine import HipPdhgEngine, _d, _i, _pd, _pi
+from .engine import _MemberEngine, _MemberOwner, _d, _i, _int_p, _pd, _pi
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams,
                                           MalitskyPockStepsizeParameters, _check_inputs, _constant_step_estimate,
-                                          _device_scaled_problem, _drive_solves, _host_scaled_problem, _rescales_on_device,
-                                          _Solve, adaptive_step_rule)
+                                          _device_scaled_problem, _drive_solves, _host_scaled_problem, _pack_step_states,
+                                          _rescales_on_device, _Solve, _unpack_step_states, adaptive_step_rule)
 
 MAX_BATCH = 32
-_int_p = ctypes.POINTER(ctypes.c_int)
 
 
-class _MemberEngine(HipPdhgEngine):
-    """A non-owning view of member k: the batch frees it (``close`` only forgets the handle)."""
-
-    def close(self):
-        self._h = None
-
+class _BatchMember(_MemberEngine):
     def rescale(self, *args, **kw):
         raise ValueError("a batch member shares its batch's matrix: rescale the batch")
 
 
-class HipPdhgBatch:
+class HipPdhgBatch(_MemberOwner):
     """K LPs with one constraint matrix on one GPU (``pdhg_create_batch``)."""
 
     def __init__(self, constraint_matrix, objective_vectors, right_hand_sides, variable_lower_bounds,
@@ -67,7 +61,7 @@ class HipPdhgBatch:
         for k in range(K):
             mh = ctypes.c_void_p()
             _lib.check(self._L.pdhg_batch_member(self._h, k, ctypes.byref(mh)))
-            self.members.append(_MemberEngine._wrap(self._L, mh, self.m, self.n))
+            self.members.append(_BatchMember._wrap(self._L, mh, self.m, self.n))
 
     @classmethod
     def from_problems(cls, problems, **kw):
@@ -78,19 +72,6 @@ class HipPdhgBatch:
                    [p.variable_upper_bound for p in problems], p0.num_equalities, **kw)
 
     takes_original_problem = True
-
-    def close(self):
-        if getattr(self, "_h", None):
-            for eng in self.members:
-                eng._h = None
-            self._L.pdhg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _mask(self, active):
         a = np.ones(self.K, dtype=np.int32) if active is None else np.asarray(active, dtype=np.int32).copy()
@@ -127,16 +108,9 @@ class HipPdhgBatch:
         """``n_steps`` take_steps of every active member in lockstep.  Returns arrays (step_sizes,
         total_number_iterations, cumulative_kkt_passes, numerical_error, steps_done)."""
         a = self._mask(active)
-        ss = _d(np.array(step_sizes, dtype=np.float64))
-        pw = _d(np.array(primal_weights, dtype=np.float64))
-        it = np.array(total_number_iterations, dtype=np.int64)
-        kkt = _d(np.array(cumulative_kkt_passes, dtype=np.float64))
-        err = np.zeros(self.K, dtype=np.int32)
-        done = np.zeros(self.K, dtype=np.int64)
-        _lib.check(self._L.pdhg_batch_take_steps_adaptive(
-            self._h, int(n_steps), float(reduction_exponent), float(growth_exponent), _pd(ss), _pd(pw), _pi(it),
-            _pd(kkt), err.ctypes.data_as(_int_p), a.ctypes.data_as(_int_p), _pi(done)))
-        return ss, it, kkt, err.astype(bool), done
+        return self._take_steps_adaptive(self._L.pdhg_batch_take_steps_adaptive, int(n_steps), reduction_exponent,
+                                         growth_exponent, step_sizes, primal_weights, total_number_iterations,
+                                         cumulative_kkt_passes, a.ctypes.data_as(_int_p))
 
 
 def check_batch(problems, params=None):
@@ -229,23 +203,11 @@ def _take_steps(batch, members, n_steps, policy):
     """``n_steps`` take_steps of every member in ``members`` (lockstep); returns the steps each took."""
     if (isinstance(policy, AdaptiveStepsizeParams) and isinstance(batch, HipPdhgBatch)
             and os.environ.get("PDHG_PY_TAKE_STEP", "0") != "1"):
-        K = batch.K
-        slot = [_slot(batch, mb) for mb in members]
-        mask = np.zeros(K, dtype=np.int32)
-        ss, pw, kkt = np.ones(K), np.ones(K), np.zeros(K)
-        it = np.zeros(K, dtype=np.int64)
-        for k, mb in zip(slot, members):
-            mask[k] = 1
-            ss[k], pw[k] = mb.state.step_size, mb.state.primal_weight
-            it[k], kkt[k] = mb.state.total_number_iterations, mb.state.cumulative_kkt_passes
-        ss, it, kkt, err, done = batch.take_steps_adaptive(n_steps, policy.reduction_exponent,
-                                                           policy.growth_exponent, ss, pw, it, kkt, mask)
-        for k, mb in zip(slot, members):
-            mb.state.step_size, mb.state.total_number_iterations = float(ss[k]), int(it[k])
-            mb.state.cumulative_kkt_passes = float(kkt[k])
-            if err[k]:
-                mb.state.numerical_error = True
-        return [int(done[k]) for k in slot]
+        placed = [(_slot(batch, mb), mb.state) for mb in members]
+        mask = np.zeros(batch.K, dtype=np.int32)
+        mask[[k for k, _ in placed]] = 1
+        return _unpack_step_states(placed, *batch.take_steps_adaptive(
+            n_steps, policy.reduction_exponent, policy.growth_exponent, *_pack_step_states(batch.K, placed), mask))
     return _take_steps_python(batch, members, n_steps, policy)
 
 

@@ -294,23 +294,15 @@ int pdhg_batch_take_steps_adaptive(pdhg_handle *batch, int64_t n_steps, double r
       if (rc) return rc;
       for (int k = 0; k < K; ++k) {
         if (!need[k]) continue;
-        cumulative_kkt_passes[k] += 1;
-        const double k1 = (double)(total_number_iterations[k] + 1);
-        const StepRule rule = adaptive_step_rule(raw + 5 * k, primal_weight[k], step_size[k], pow(k1, -reduction_exponent),
-                                                 pow(k1, -growth_exponent));
-        if (rule.numerical_error) {
-          numerical_error[k] = 1;
+        StepIO io{step_size[k], total_number_iterations[k], cumulative_kkt_passes[k], numerical_error[k], steps_done[k],
+                  primal_weight[k], reduction_exponent, growth_exponent};
+        const StepRule rule = step_after_trial(io, raw + 5 * k);
+        if (rule.numerical_error) live[k] = 0;
+        else acc[k] = rule.accept;
+        if (rule.numerical_error || rule.accept) {       // the take_step is over (a failing one counts as taken)
           need[k] = 0;
-          live[k] = 0;
-          steps_done[k] += 1;
-          continue;
+          io.steps_done += 1;
         }
-        if (rule.accept) {
-          acc[k] = 1;
-          need[k] = 0;
-          steps_done[k] += 1;
-        }
-        step_size[k] = rule.next_step;
       }
       if ((rc = pdhg_batch_accept(batch, acc, entry))) return rc;
     }

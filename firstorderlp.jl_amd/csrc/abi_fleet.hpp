@@ -84,44 +84,33 @@ int pdhg_fleet_take_steps_adaptive(pdhg_handle *fleet, const int64_t *n_steps, d
   const int K = (int)F.mem.size();
   for (int k = 0; k < K; ++k)
     if (n_steps[k] < 0) return fail(-2, "pdhg_fleet_take_steps_adaptive: n_steps[" + std::to_string(k) + "] < 0");
-  std::vector<FleetCarry> carry;
-  std::vector<int> single;
+  std::vector<StepIO> io;                       // one per member that steps in this call (reserved: the carries point into it)
+  io.reserve((size_t)K);
+  std::vector<FleetCarry> carry, single;
   for (int k = 0; k < K; ++k) {
     if (n_steps[k] == 0) continue;              // neither read nor written
     numerical_error[k] = 0;
     steps_done[k] = 0;
+    io.push_back(StepIO{step_size[k], total_number_iterations[k], cumulative_kkt_passes[k], numerical_error[k], steps_done[k],
+                        primal_weight[k], reduction_exponent, growth_exponent});
     pdhg_handle *h = F.mem[(size_t)k];
-    if (n_steps[k] >= 2 && check_handle(h) == 0 && small_lp_eligible(h)) {
-      FleetCarry c;
-      c.k = k;
-      c.n = (int)std::min<int64_t>(n_steps[k], 1 << 20);
-      carry.push_back(c);
-    } else {
-      single.push_back(k);
-    }
+    FleetCarry c;
+    c.k = k;
+    c.io = &io.back();
+    c.n = (int)std::min<int64_t>(n_steps[k], 1 << 20);
+    (n_steps[k] >= 2 && check_handle(h) == 0 && small_lp_eligible(h) ? carry : single).push_back(c);
   }
   F.last_carried = (int64_t)carry.size();
   F.last_single = (int64_t)single.size();
-  std::vector<double> entry((size_t)K, 0.0);
-  int rc = fleet_launch(fleet, carry, reduction_exponent, growth_exponent, step_size, primal_weight, total_number_iterations,
-                        cumulative_kkt_passes, numerical_error, steps_done, entry.data());
+  int rc = fleet_launch(fleet, carry);
   if (rc) return rc;
   // what the shared launch left of a carried member, from where it stopped (the step size on entry of a take_step it
-  // ended inside goes to that take_step's accept, as in pdhg_take_steps_adaptive)
-  for (const FleetCarry &c : carry) {
-    const int k = c.k;
-    if (numerical_error[k] || steps_done[k] >= n_steps[k]) continue;
-    if ((rc = take_steps_adaptive_resume(F.mem[(size_t)k], n_steps[k], steps_done[k], entry[(size_t)k], reduction_exponent,
-                                         growth_exponent, &step_size[k], primal_weight[k], &total_number_iterations[k],
-                                         &cumulative_kkt_passes[k], &numerical_error[k], &steps_done[k])))
-      return rc;
-  }
-  for (int k : single) {
-    if ((rc = take_steps_adaptive_resume(F.mem[(size_t)k], n_steps[k], 0, 0.0, reduction_exponent, growth_exponent,
-                                         &step_size[k], primal_weight[k], &total_number_iterations[k],
-                                         &cumulative_kkt_passes[k], &numerical_error[k], &steps_done[k])))
-      return rc;
-  }
+  // ended inside goes to that take_step's accept, as in pdhg_take_steps_adaptive); the others from the start
+  for (const std::vector<FleetCarry> *part : {&carry, &single})
+    for (const FleetCarry &c : *part) {
+      if (c.io->numerical_error || c.io->steps_done >= n_steps[c.k]) continue;
+      if ((rc = take_steps_adaptive_resume(F.mem[(size_t)c.k], n_steps[c.k], *c.io))) return rc;
+    }
   return 0;
 }
 

@@ -16,10 +16,10 @@ static int trial_dual_single(pdhg_handle *h, double step_size, double primal_wei
   static const bool host_word = !(dev_env("PDHG_TRIAL_HOST_WORD") && dev_env("PDHG_TRIAL_HOST_WORD")[0] == '0');
   if (host_word && !h->profile) {
     if ((rc = ensure_result_word(h))) return rc;
-    if ((rc = launch_final(h, h->pAt, h->At.slots(), h->pAt_stride, h->pA, h->A.slots(), qcount, true))) return rc;
+    if ((rc = launch_final(h, h->At.slots(), h->A.slots(), qcount, true))) return rc;
     return wait_result_word(h, out);
   }
-  if ((rc = launch_final(h, h->pAt, h->At.slots(), h->pAt_stride, h->pA, h->A.slots(), qcount))) return rc;
+  if ((rc = launch_final(h, h->At.slots(), h->A.slots(), qcount))) return rc;
   HIP_TRY(hipMemcpyAsync(h->scal_host, h->scal_dev, 5 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   for (int q = 0; q < 5; ++q) out[q] = h->scal_host[q];
@@ -30,11 +30,6 @@ static int trial_dual_single(pdhg_handle *h, double step_size, double primal_wei
 // ---- the trial of a row-partitioned group, launch by launch ----------------------------------------------------------
 // One text for both issuers (dist.hpp, "who issues"): the same launches, event calls and collectives in the same order
 // per stream, whether the calling thread walks all local shards or every shard's own pool thread issues its share.
-struct TrialArgs {
-  double step_size, primal_weight, theta;
-  bool primal;      // K1+K2 first (pdhg_trial_step); false: xbar only (pdhg_trial_dual)
-};
-
 static int group_trial_primal(const Issue &I, const TrialArgs &a) {
   int rc;
   FOR_ISSUED(I, s, i) {
@@ -134,7 +129,7 @@ static int group_trial_dual(const Issue &I, const TrialArgs &a) {
     int qcount = 0;
     if ((rc = launch_q_interaction(s, &qcount))) return rc;   // replicated: identical on every shard
     const int a_slots = chunked ? dual_chunk_slots(s) : s->A.slots();
-    if ((rc = launch_final(s, s->pAt, ew_grid(s->cn), s->pAt_stride, s->pA, a_slots, qcount, false, chunked ? a_slots : -1))) return rc;
+    if ((rc = launch_final(s, ew_grid(s->cn), a_slots, qcount, false, chunked ? a_slots : -1))) return rc;
   }
   return 0;
 }
@@ -263,11 +258,8 @@ static int group_coop_prepare(const Shards &L) {
     HIP_TRY(hipStreamSynchronize(D.stream));
     for (size_t k = 0; k < k_n; ++k) {
       pdhg_handle *s = L.p[D.members[k]];
-      GridSync host;
-      HIP_TRY(hipMemcpy(&host, s->gsync, sizeof(GridSync), hipMemcpyDeviceToHost));
       unsigned long long seen = 0;
-      s->coop_nxcd = 0;
-      for (int x = 0; x < 8; ++x) { seen += host.xcd_count[x][0]; s->coop_nxcd += host.xcd_count[x][0] > 0; s->coop_xcd_cnt[x] = (unsigned)host.xcd_count[x][0]; }
+      if (int rc = census_read(D.stream, s->gsync, &seen, &s->coop_nxcd, s->coop_xcd_cnt)) return rc;
       if (seen != (unsigned long long)grid[k] || s->coop_nxcd == 0) return fail(996, "group trial kernel: workgroup census does not add up");
     }
   }
@@ -340,25 +332,13 @@ static int group_coop_trial(const Shards &L, const TrialArgs &ta, double out[5])
         a.xbar_peer[L.p[q]->rank] = L.p[q]->xbar;
         a.part_peer[L.p[q]->rank] = L.p[q]->aty_next;
       }
-      EpiArgs de{};
-      de.y = s->y; de.b = s->b; de.y_next = s->y_next; de.sigma = sigma; de.num_eq = (int)s->num_eq;
-      de.partials = s->pA; de.stride = s->A.slots(); de.lo_offset = s->A.slots();
-      if (s->pend_y) { de.sum_y = s->sum_y; de.avg_w = s->pend_w; }
-      a.A = trial_product(s, s->A, s->xbar, de);
+      a.A = trial_product(s, s->A, s->xbar, dual_epilogue(s, sigma));
       EpiArgs te{};
       te.out = s->aty_next;
       a.T = trial_product(s, s->At, s->y_next, te);
       a.off = o; a.aty_next = s->aty_next;
       a.pAt = s->pAt; a.pAt_stride = s->pAt_stride;
-      a.sp.ptr[0] = s->pAt;                         a.sp.count[0] = s->coop_grid;
-      a.sp.ptr[1] = s->pAt + s->pAt_stride;         a.sp.count[1] = s->coop_grid;
-      a.sp.ptr[2] = s->pA;                          a.sp.count[2] = s->A.slots();
-      a.sp.ptr[3] = s->pAt + 2 * s->pAt_stride;     a.sp.count[3] = s->coop_grid;
-      a.sp.ptr[4] = s->pQ;                          a.sp.count[4] = 0;
-      for (int q : {0, 1, 3}) a.sp.ptr_lo[q] = a.sp.ptr[q] + 3 * s->pAt_stride;
-      a.sp.ptr_lo[2] = s->pA + s->A.slots();
-      a.sp.ptr_lo[4] = s->pQ + s->ew_grid_n;
-      a.sp.out = nullptr;
+      a.sp = trial_final_spec(s, s->coop_grid, s->A.slots(), 0, s->A.slots(), nullptr);      // (one interaction partial per workgroup)
       a.sync = s->gsync; a.gsync = g.gsync;
       a.epoch = s->coop_epoch; s->coop_epoch += 3;
       a.xepoch = g.xepoch;
@@ -450,8 +430,8 @@ static int trial_dispatch(pdhg_handle *h, const TrialArgs &a, double out[5]) {
     return group_trial(L, a, out);
   }
   // (pdhg_trial_dual here: Malitsky-Pock retries, xbar + the dual half)
-  if (coop_eligible(h) && (rc = coop_trial(h, a.step_size, a.primal_weight, a.theta, !a.primal, out)) != 1) return rc;   // 1: as above
-  if (a.primal && graph_eligible(h)) return graph_trial(h, a.step_size, a.primal_weight, a.theta, out);
+  if (coop_eligible(h) && (rc = coop_trial(h, a, out)) != 1) return rc;   // 1: as above
+  if (a.primal && graph_eligible(h)) return graph_trial(h, a, out);
   // (check_handle has made the handle's device current)
   if ((rc = a.primal ? launch_primal(h, a.step_size / a.primal_weight, a.theta, true) : launch_xbar(h, a.theta))) return rc;
   return trial_dual_single(h, a.step_size, a.primal_weight, out);
@@ -500,112 +480,68 @@ int pdhg_accept(pdhg_handle *h0, double avg_weight) {
  * statements as primal_dual_hybrid_gradient.py::take_step_adaptive (bitwise equal
  * results; tests/test_gpu_native_take_step.py); what it removes is the host
  * language's per-call overhead between the trial and the accept. */
-// step_on_entry: the step size the take_step was entered with (the average's weight, pdhg.jl:512) -- equal to
-// *step_size_io except when a multi-step kernel handed back a take_step it had begun (some trials already rejected)
-static int take_step_adaptive_from(pdhg_handle *h, double reduction_exponent, double growth_exponent,
-                                   double *step_size_io, double step_on_entry, double primal_weight,
-                                   int64_t *total_number_iterations_io, double *cumulative_kkt_passes_io,
-                                   int *numerical_error_out);
+// The weight of the accept is the step size the take_step was entered with (pdhg.jl:512): io.step_size, except when a
+// multi-step kernel handed back a take_step it had begun (some trials already rejected) -- then io.entry, which this
+// take_step uses up.
+static int take_step_adaptive_from(pdhg_handle *h, StepIO &io) {
+  const double step_in = io.step_size, step_on_entry = io.entry != 0.0 ? io.entry : step_in;
+  auto failed = [&](int rc) { io.step_size = step_in; return rc; };     // an error return leaves the caller's step size as it came
+  io.numerical_error = 0;
+  for (bool done = false; !done;) {
+    io.iterations += 1;
+    double raw[5];
+    int rc = pdhg_trial_step(h, io.step_size, io.primal_weight, 1.0, raw);
+    if (rc) return failed(rc);
+    const StepRule rule = step_after_trial(io, raw);
+    if (rule.numerical_error) break;
+    if (rule.accept) {
+      if ((rc = pdhg_accept(h, step_on_entry))) return failed(rc);
+      done = true;
+    }
+  }
+  io.entry = 0.0;
+  return 0;
+}
 int pdhg_take_step_adaptive(pdhg_handle *h, double reduction_exponent, double growth_exponent,
                             double *step_size_io, double primal_weight, int64_t *total_number_iterations_io,
                             double *cumulative_kkt_passes_io, int *numerical_error_out) {
   if (!h || !step_size_io || !total_number_iterations_io || !cumulative_kkt_passes_io || !numerical_error_out)
     return fail(-1, "null argument");
-  return take_step_adaptive_from(h, reduction_exponent, growth_exponent, step_size_io, *step_size_io, primal_weight,
-                                 total_number_iterations_io, cumulative_kkt_passes_io, numerical_error_out);
-}
-static int take_step_adaptive_from(pdhg_handle *h, double reduction_exponent, double growth_exponent,
-                                   double *step_size_io, double step_on_entry, double primal_weight,
-                                   int64_t *total_number_iterations_io, double *cumulative_kkt_passes_io,
-                                   int *numerical_error_out) {
-  double step_size = *step_size_io;
-  *numerical_error_out = 0;
-  bool done = false;
-  while (!done) {
-    *total_number_iterations_io += 1;
-    double raw[5];
-    int rc = pdhg_trial_step(h, step_size, primal_weight, 1.0, raw);
-    if (rc) return rc;
-    *cumulative_kkt_passes_io += 1;
-    const double k1 = (double)(*total_number_iterations_io + 1);
-    const StepRule rule = adaptive_step_rule(raw, primal_weight, step_size, pow(k1, -reduction_exponent), pow(k1, -growth_exponent));
-    if (rule.numerical_error) {
-      *numerical_error_out = 1;
-      break;
-    }
-    if (rule.accept) {
-      if ((rc = pdhg_accept(h, step_on_entry))) return rc;   // weight = step size on entry (pdhg.jl:512)
-      done = true;
-    }
-    step_size = rule.next_step;
-  }
-  *step_size_io = step_size;
-  return 0;
+  int64_t steps_done = 0;
+  StepIO io{*step_size_io, *total_number_iterations_io, *cumulative_kkt_passes_io, *numerical_error_out, steps_done,
+            primal_weight, reduction_exponent, growth_exponent};
+  return take_step_adaptive_from(h, io);
 }
 
-// Does pdhg_take_steps_adaptive take this handle's batches with the multi-step kernel (steps_kernel)?
-static bool device_loop_for(pdhg_handle *h) {
-  // Several take_steps per launch (steps_kernel: the rule on the device; stream-layout LPs on one handle).  Bitwise the
-  // per-trial launches (tests/test_gpu_device_loop.py) and faster on every grid measured but one tie: L1-SVM 19.7k ->
-  // 23.4k it/s, random 100K 22.5k -> 28.6k, 3000 x 2500 32.7k -> 52.7k (trial_kernel.hpp, profiles/r03_trial_kernel.txt).
-  // PDHG_DEVICE_LOOP=0 / 1: never / whenever eligible; PDHG_DEVICE_LOOP_MAX_WGS: largest grid it is the default for.
-  const char *dl_env = getenv("PDHG_DEVICE_LOOP");
-  bool device_loop = dl_env && dl_env[0] == '1';
-  if (!dl_env && !h->grp && !h->profile && !h->has_q && check_handle(h) == 0 && coop_eligible(h)) {
-    static const int max_wgs = dev_env("PDHG_DEVICE_LOOP_MAX_WGS") ? atoi(dev_env("PDHG_DEVICE_LOOP_MAX_WGS")) : (1 << 30);
-    device_loop = h->coop_grid <= max_wgs;
-  }
-  return device_loop;
-}
-
-// The per-handle loop of pdhg_take_steps_adaptive from a given place: `s` of the n_steps are taken already, and
-// `entry` != 0 says that a multi-step launch ended inside take_step s + 1 (its table of powers ran out), with `entry`
-// that take_step's step size on entry.  pdhg_take_steps_adaptive starts it at (0, 0.0); a fleet call (abi_fleet.hpp) at
-// whatever the shared launch left of a member, and at (0, 0.0) for the members it steps singly.
-static int take_steps_adaptive_resume(pdhg_handle *h, int64_t n_steps, int64_t s, double entry, double reduction_exponent,
-                                      double growth_exponent, double *step_size_io, double primal_weight,
-                                      int64_t *total_number_iterations_io, double *cumulative_kkt_passes_io,
-                                      int *numerical_error_out, int64_t *steps_done_out) {
-  const bool device_loop = device_loop_for(h);
-  *steps_done_out = s;
-  while (s < n_steps) {
-    // entry nonzero: a multi-step kernel ended inside a take_step (its table of powers ran out)
-    if (entry == 0.0 && n_steps - s >= 2 && !h->grp && check_handle(h) == 0 && small_lp_eligible(h)) {
-      // a small LP: the batch in one workgroup with the vectors in LDS (small_lp_kernel.hpp)
-      int64_t k = 0;
-      const int rc = small_lp_steps(h, n_steps - s, reduction_exponent, growth_exponent, step_size_io, primal_weight,
-                                    total_number_iterations_io, cumulative_kkt_passes_io, numerical_error_out, &k, &entry);
+// The per-handle loop of pdhg_take_steps_adaptive from a given place: io.steps_done of the n_steps are taken already,
+// and io.entry != 0 says that a multi-step launch ended inside the next take_step.  pdhg_take_steps_adaptive starts it
+// at (0, 0.0); a fleet call (abi_fleet.hpp) at whatever the shared launch left of a member, and at (0, 0.0) for the
+// members it steps singly.
+static int take_steps_adaptive_resume(pdhg_handle *h, int64_t n_steps, StepIO &io) {
+  // the multi-step launchers in the order they are offered a batch: a small LP in one workgroup with the vectors in
+  // LDS (small_lp_kernel.hpp), then the persistent multi-step kernel (steps_kernel); each answers 1 for "not taken"
+  int (*const launchers[])(pdhg_handle *, int64_t, StepIO &) = {small_lp_steps, coop_steps};
+  while (io.steps_done < n_steps) {
+    bool go_on = false;       // a launch took whole take_steps: offer the rest again
+    for (auto launch : launchers) {
+      // (entry != 0: a launch ended inside a take_step -- its step size on entry must reach the accept of THAT
+      //  take_step, so it is finished launch by launch below, never handed to a fresh multi-step launch)
+      if (io.entry != 0.0 || n_steps - io.steps_done < 2 || h->grp || check_handle(h) != 0) break;
+      const int64_t before = io.steps_done;
+      const int rc = launch(h, n_steps - before, io);
       if (rc != 0 && rc != 1) return rc;
-      if (rc == 0) {
-        s += k;
-        *steps_done_out = s;
-        if (*numerical_error_out) break;
-        if (k > 0 && entry == 0.0) continue;
-      }
+      if (rc == 1) continue;
+      if (io.numerical_error) return 0;
+      // (nothing taken: trial budget spent on rejections, or a time-out -- the next launcher, or the next step singly)
+      go_on = io.steps_done > before && io.entry == 0.0;
+      if (go_on) break;
     }
-    // (entry != 0: the small-LP launch above ended inside a take_step -- its step size on entry must reach the accept
-    //  of THAT take_step, so it is finished launch by launch below, never handed to a fresh multi-step launch)
-    if (entry == 0.0 && device_loop && n_steps - s >= 2 && !h->grp && !h->profile && check_handle(h) == 0) {
-      int64_t k = 0;
-      const int rc = coop_steps(h, n_steps - s, reduction_exponent, growth_exponent, step_size_io, primal_weight,
-                                total_number_iterations_io, cumulative_kkt_passes_io, numerical_error_out, &k, &entry);
-      if (rc != 0 && rc != 1) return rc;
-      if (rc == 0) {
-        s += k;
-        *steps_done_out = s;
-        if (*numerical_error_out) break;
-        if (k > 0 && entry == 0.0) continue;   // (k == 0: trial budget spent on rejections, or a time-out: take the next step singly)
-      }
-    }
-    if (s >= n_steps) break;
-    // one take_step, launch by launch -- or the rest of one that a multi-step kernel began (entry: its step size on entry)
-    const int rc = take_step_adaptive_from(h, reduction_exponent, growth_exponent, step_size_io,
-                                           entry != 0.0 ? entry : *step_size_io, primal_weight,
-                                           total_number_iterations_io, cumulative_kkt_passes_io, numerical_error_out);
-    if (rc) return rc;
-    entry = 0.0;
-    *steps_done_out = ++s;
-    if (*numerical_error_out) break;
+    if (go_on) continue;
+    if (io.steps_done >= n_steps) break;
+    // one take_step, launch by launch -- or the rest of one that a multi-step kernel began (io.entry)
+    if (int rc = take_step_adaptive_from(h, io)) return rc;
+    io.steps_done += 1;
+    if (io.numerical_error) break;
   }
   return 0;
 }
@@ -623,8 +559,9 @@ int pdhg_take_steps_adaptive(pdhg_handle *h, int64_t n_steps, double reduction_e
   if (!h || !step_size_io || !total_number_iterations_io || !cumulative_kkt_passes_io || !numerical_error_out)
     return fail(-1, "null argument");
   *numerical_error_out = 0;
-  return take_steps_adaptive_resume(h, n_steps, 0, 0.0, reduction_exponent, growth_exponent, step_size_io, primal_weight,
-                                    total_number_iterations_io, cumulative_kkt_passes_io, numerical_error_out, steps_done_out);
+  StepIO io{*step_size_io, *total_number_iterations_io, *cumulative_kkt_passes_io, *numerical_error_out, *steps_done_out,
+            primal_weight, reduction_exponent, growth_exponent};
+  return take_steps_adaptive_resume(h, n_steps, io);
 }
 
 int pdhg_add_current_primal_to_average(pdhg_handle *h0, double weight) {

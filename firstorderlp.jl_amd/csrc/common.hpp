@@ -188,6 +188,36 @@ __host__ __device__ inline StepRule adaptive_step_rule(const double raw[5], doub
   return r;
 }
 
+// The adaptive policy's scalars of one solve on the host side of stepping.  What the caller reads afterwards is BOUND
+// by reference (the C ABI's pointers, or elements of its arrays: every update lands in the caller's storage at once,
+// nothing is copied back at the end of a call); what it only passes in is held by value.
+struct StepIO {
+  double &step_size;
+  int64_t &iterations;          // total_number_iterations: trials so far
+  double &kkt_passes;           // cumulative_kkt_passes
+  int &numerical_error;
+  int64_t &steps_done;          // take_steps taken in this call so far
+  double primal_weight, reduction_exponent, growth_exponent;
+  // the step size on entry of a take_step that a multi-step launch ended inside (its table of powers ran out); 0: none.
+  // It is the weight of THAT take_step's accept (pdhg.jl:512), so the take_step is finished launch by launch and the
+  // value is never handed to a fresh multi-step launch.
+  double entry = 0.0;
+  // does steps_kernel take this call's batches?  -1: not asked yet (device_loop_for reads the environment: once per call)
+  int device_loop = -1;
+};
+
+// take_step(::AdaptiveStepsizeParams) after one trial whose sums are raw[5] (io.iterations counts the trial): the KKT
+// pass, the rule with the HOST's pow, and its outcome in the step state -- numerical_error raised, or the next step size.
+inline StepRule step_after_trial(StepIO &io, const double raw[5]) {
+  io.kkt_passes += 1;
+  const double k1 = (double)(io.iterations + 1);
+  const StepRule rule = adaptive_step_rule(raw, io.primal_weight, io.step_size, pow(k1, -io.reduction_exponent),
+                                           pow(k1, -io.growth_exponent));
+  if (rule.numerical_error) io.numerical_error = 1;
+  else io.step_size = rule.next_step;
+  return rule;
+}
+
 // A load that cannot be served by a stale line of this CU's L1: agent scope (sc1), served by the L2.  The
 // multi-step trial kernel re-reads vectors that OTHER compute units rewrote since this CU last read them, and a
 // per-workgroup L1 invalidate costs ~50 ns per workgroup and XCD, serialised (tools/grid_barrier_probe).  Relaxed:

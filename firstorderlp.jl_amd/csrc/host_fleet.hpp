@@ -19,6 +19,7 @@ struct FleetState {
 // one carried member of a call
 struct FleetCarry {
   int k = 0;                   // index in FleetState::mem
+  StepIO *io = nullptr;        // its step state (bound to the caller's arrays at k)
   int n = 0, max_trials = 0, table_len = 0;
   int64_t k1_first = 0;        // k1 of its first trial
   bool few = false;
@@ -54,12 +55,11 @@ int fleet_reserve(pdhg_handle *f, size_t members, size_t span) {
 
 // The shared launch of `carry` (every entry small_lp_eligible, n >= 2): at most two kernel launches back to back -- the
 // members of up to SMALL_FEW_ROWS rows and columns with 256 threads, the others with SMALL_TPB, the solo rule -- then one
-// wait per member.  On return steps_done[k] / entry[k] hold what small_lp_steps would have reported for member k.
-int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry, double reduction_exponent, double growth_exponent,
-                 double *step_size, const double *primal_weight, int64_t *total_number_iterations,
-                 double *cumulative_kkt_passes, int *numerical_error, int64_t *steps_done, double *entry) {
+// wait per member.  On return every member's step state holds what small_lp_steps would have left in it.
+int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry) {
   FleetState &F = *f->fleet;
   if (carry.empty()) return 0;
+  const double reduction_exponent = carry[0].io->reduction_exponent, growth_exponent = carry[0].io->growth_exponent;   // the call's
   HIP_TRY(hipSetDevice(f->device));
   int rc;
   // the tables of powers: one pair for the call, from the smallest to the largest k1 a member can reach
@@ -69,7 +69,7 @@ int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry, double reductio
     if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
     if ((rc = steps_result_words(h))) return rc;
     steps_budget(c.n, &c.max_trials, &c.table_len);
-    c.k1_first = total_number_iterations[c.k] + 2;      // (steps_prepare: trial t of the launch uses k1 = total + t + 2)
+    c.k1_first = c.io->iterations + 2;      // (steps_prepare: trial t of the launch uses k1 = total + t + 2)
     c.few = small_lp_few_rows(h);
     lo = std::min(lo, c.k1_first);
     hi = std::max(hi, c.k1_first + c.table_len);          // one past the last
@@ -101,7 +101,7 @@ int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry, double reductio
     FleetCarry &c = carry[i];
     pdhg_handle *h = F.mem[(size_t)c.k];
     const size_t off = (size_t)(c.k1_first - lo);
-    F.args_host[i] = small_lp_stage(h, c.n, c.max_trials, c.table_len, step_size[c.k], primal_weight[c.k], F.pow_dev + off,
+    F.args_host[i] = small_lp_stage(h, c.n, c.max_trials, c.table_len, c.io->step_size, c.io->primal_weight, F.pow_dev + off,
                                     F.pow_dev + span + off);
     c.seq = F.args_host[i].seq;
     if (c.few) { n_few += 1; lds_few = std::max(lds_few, small_lp_lds_bytes(h)); }
@@ -121,10 +121,7 @@ int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry, double reductio
     F.launches += 1;
   }
   HIP_TRY(hipGetLastError());
-  for (const FleetCarry &c : carry) {
-    if ((rc = small_lp_collect(F.mem[(size_t)c.k], c.seq, &step_size[c.k], &total_number_iterations[c.k], &cumulative_kkt_passes[c.k],
-                               &numerical_error[c.k], &steps_done[c.k], &entry[c.k])))
-      return rc;
-  }
+  for (const FleetCarry &c : carry)
+    if ((rc = small_lp_collect(F.mem[(size_t)c.k], c.seq, *c.io))) return rc;
   return 0;
 }

@@ -64,41 +64,27 @@ SmallLpArgs small_lp_stage(pdhg_handle *h, int n, int max_trials, int table_len,
   return a;
 }
 
-// Wait for launch `seq` of h and take its results into the handle's bookkeeping and the caller's scalars.
-int small_lp_collect(pdhg_handle *h, unsigned long long seq, double *step_size_io, int64_t *total_number_iterations_io,
-                     double *cumulative_kkt_passes_io, int *numerical_error_out, int64_t *steps_done, double *unfinished_entry) {
-  double r[13], r14 = 0.0;
-  if (int rc = steps_wait(h, seq, r, &r14)) return rc;
-  const int64_t steps = (int64_t)r[1], trials = (int64_t)r[2];
-  h->small_lp_launches += 1; h->n_graph_trials += trials;
-  h->sum_x_count += steps; h->sum_y_count += steps;
-  h->sum_x_weights = r[6]; h->sum_y_weights = r[7];
+// Wait for launch `seq` of h and take its results into the handle's bookkeeping and the step state (steps_collect).
+int small_lp_collect(pdhg_handle *h, unsigned long long seq, StepIO &io) {
+  double r[13];
+  if (int rc = steps_collect(h, seq, io, r)) return rc;
+  h->small_lp_launches += 1;
   h->state_version += 1;
-  *step_size_io = r[0];
-  *total_number_iterations_io += trials;
-  *cumulative_kkt_passes_io += (double)trials;
-  *steps_done = steps;
-  *unfinished_entry = r14;
-  if (r[8] != 0.0) { *numerical_error_out = 1; *steps_done = steps + 1; }
   return 0;
 }
 
-// returns 1 when not eligible (nothing launched)
-int small_lp_steps(pdhg_handle *h, int64_t n_steps, double reduction_exponent, double growth_exponent, double *step_size_io,
-                   double primal_weight, int64_t *total_number_iterations_io, double *cumulative_kkt_passes_io,
-                   int *numerical_error_out, int64_t *steps_done, double *unfinished_entry) {
-  *steps_done = 0;
-  *unfinished_entry = 0.0;
+// Up to n_steps take_steps from the step state `io` on, as coop_steps; returns 1 when not eligible (nothing launched)
+int small_lp_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   if (!small_lp_eligible(h)) return 1;
   HIP_TRY(hipSetDevice(h->device));
   int rc;
   if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
   const int n = (int)std::min<int64_t>(n_steps, 1 << 20);
   int max_trials = 0, table_len = 0;
-  if ((rc = steps_prepare(h, n, *total_number_iterations_io, reduction_exponent, growth_exponent, &max_trials, &table_len))) return rc;
+  if ((rc = steps_prepare(h, n, io, &max_trials, &table_len))) return rc;
   const size_t lds = small_lp_lds_bytes(h);
   if ((rc = small_lp_lds_limit(h->device, 0, lds))) return rc;
-  const SmallLpArgs a = small_lp_stage(h, n, max_trials, table_len, *step_size_io, primal_weight, h->steps_pow_dev,
+  const SmallLpArgs a = small_lp_stage(h, n, max_trials, table_len, io.step_size, io.primal_weight, h->steps_pow_dev,
                                        h->steps_pow_dev + table_len);
   const auto c1 = std::chrono::steady_clock::now();
   if (small_lp_few_rows(h)) hipLaunchKernelGGL(small_lp_steps_kernel<256>, dim3(1), dim3(256), lds, h->stream, a);
@@ -106,8 +92,7 @@ int small_lp_steps(pdhg_handle *h, int64_t n_steps, double reduction_exponent, d
   HIP_TRY(hipGetLastError());
   const auto c2 = std::chrono::steady_clock::now();
   h->t_launch += std::chrono::duration<double>(c2 - c1).count();
-  rc = small_lp_collect(h, a.seq, step_size_io, total_number_iterations_io, cumulative_kkt_passes_io, numerical_error_out,
-                        steps_done, unfinished_entry);
+  rc = small_lp_collect(h, a.seq, io);
   h->t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - c2).count();
   return rc;
 }

@@ -21,6 +21,25 @@ bool coop_eligible(pdhg_handle *h) {
   return h->coop_mode == 1 && !h->profile;
 }
 
+// The census of a persistent launch shape: how many of its workgroups the dispatcher places on each XCD (the barriers
+// count arrivals per XCD).  census_read: `sync` back from the device once `stream` has drained -- the total, the XCDs
+// that hold any, and the count of each; xcd_census: a launch of `grid` registering workgroups first.  What a caller
+// makes of a census that does not add up is its own affair.
+int census_read(hipStream_t stream, const GridSync *sync, unsigned long long *total, unsigned *nxcd, unsigned cnt[8]) {
+  GridSync host;
+  HIP_TRY(hipMemcpyAsync(&host, sync, sizeof(GridSync), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  *total = 0;
+  *nxcd = 0;
+  for (int x = 0; x < 8; ++x) { *total += host.xcd_count[x][0]; *nxcd += host.xcd_count[x][0] > 0; cnt[x] = (unsigned)host.xcd_count[x][0]; }
+  return 0;
+}
+int xcd_census(hipStream_t stream, int grid, GridSync *sync, unsigned long long *total, unsigned *nxcd, unsigned cnt[8]) {
+  hipLaunchKernelGGL(xcd_register_kernel, dim3(grid), dim3(TPB), 0, stream, sync);
+  HIP_TRY(hipGetLastError());
+  return census_read(stream, sync, total, nxcd, cnt);
+}
+
 // grid of the persistent launch + the census of workgroups per XCD (once per handle)
 // cap_limit: at most this many workgroups (several shards share a device); several_items: accept more items than
 // workgroups (the phases then walk several row blocks per workgroup)
@@ -56,14 +75,8 @@ int coop_prepare(pdhg_handle *h, int cap_limit, bool several_items) {
     HIP_TRY(hipMalloc((void **)&h->coop_trace, sizeof(unsigned long long) * 8 * (size_t)h->coop_grid));
     HIP_TRY(hipMemsetAsync(h->coop_trace, 0, sizeof(unsigned long long) * 8 * (size_t)h->coop_grid, h->stream));
   }
-  hipLaunchKernelGGL(xcd_register_kernel, dim3(h->coop_grid), dim3(TPB), 0, h->stream, h->gsync);
-  HIP_TRY(hipGetLastError());
-  GridSync host;
-  HIP_TRY(hipMemcpyAsync(&host, h->gsync, sizeof(GridSync), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
   unsigned long long total = 0;
-  h->coop_nxcd = 0;
-  for (int x = 0; x < 8; ++x) { total += host.xcd_count[x][0]; h->coop_nxcd += host.xcd_count[x][0] > 0; h->coop_xcd_cnt[x] = (unsigned)host.xcd_count[x][0]; }
+  if ((rc = xcd_census(h->stream, h->coop_grid, h->gsync, &total, &h->coop_nxcd, h->coop_xcd_cnt))) return rc;
   if (total != (unsigned long long)h->coop_grid || h->coop_nxcd == 0) {
     h->coop_mode = 0;
     return fail(996, "one-launch trial: workgroup census does not add up");
@@ -96,41 +109,26 @@ std::mutex &coop_device_mutex(int device) {
   return mu[device & 63];
 }
 
-int coop_trial(pdhg_handle *h, double step_size, double primal_weight, double theta, bool xbar_only, double out[5]) {
+int coop_trial(pdhg_handle *h, const TrialArgs &ta, double out[5]) {
   int rc = coop_prepare(h);
   if (rc) return rc;
+  const bool xbar_only = !ta.primal;
   std::lock_guard<std::mutex> one_at_a_time(coop_device_mutex(h->device));
   const auto c0 = std::chrono::steady_clock::now();
   TrialKernelArgs a{};
   a.n = (int)h->n; a.xbar_only = xbar_only ? 1 : 0;
   a.x = h->x; a.c = h->c; a.aty = h->aty; a.lb = h->lb; a.ub = h->ub;
-  a.tau = step_size / primal_weight; a.theta = theta;
+  a.tau = ta.step_size / ta.primal_weight; a.theta = ta.theta;
   a.x_next = h->x_next; a.xbar = h->xbar;
   a.avg_w = h->pend_w; a.sum_x = (h->pend_x && !xbar_only) ? h->sum_x : nullptr;
-  EpiArgs de{};
-  de.y = h->y; de.b = h->b; de.y_next = h->y_next; de.sigma = primal_weight * step_size; de.num_eq = (int)h->num_eq;
-  de.partials = h->pA; de.stride = h->A.slots(); de.lo_offset = h->A.slots();
-  if (h->pend_y) { de.sum_y = h->sum_y; de.avg_w = h->pend_w; }
-  a.A = trial_product(h, h->A, h->xbar, de);
-  EpiArgs te{};
-  te.x = h->x; te.x_next = h->x_next; te.aty = h->aty; te.aty_next = h->aty_next;
-  te.partials = h->pAt; te.stride = h->pAt_stride; te.lo_offset = 3 * h->pAt_stride;
-  a.T = trial_product(h, h->At, h->y_next, te);
-  a.sp.ptr[0] = h->pAt;                       a.sp.count[0] = h->At.slots();
-  a.sp.ptr[1] = h->pAt + h->pAt_stride;       a.sp.count[1] = h->At.slots();
-  a.sp.ptr[2] = h->pA;                        a.sp.count[2] = h->A.slots();
-  a.sp.ptr[3] = h->pAt + 2 * h->pAt_stride;   a.sp.count[3] = h->At.slots();
-  a.sp.ptr[4] = h->pQ;                        a.sp.count[4] = 0;
-  for (int q : {0, 1, 3}) a.sp.ptr_lo[q] = a.sp.ptr[q] + 3 * h->pAt_stride;
-  a.sp.ptr_lo[2] = h->pA + h->A.slots();
-  a.sp.ptr_lo[4] = h->pQ + h->ew_grid_n;
-  a.sp.out = nullptr;
+  a.A = trial_product(h, h->A, h->xbar, dual_epilogue(h, ta.primal_weight * ta.step_size));
+  a.T = trial_product(h, h->At, h->y_next, aty_epilogue(h));
+  a.sp = trial_final_spec(h, h->At.slots(), h->A.slots(), h->has_q ? h->ew_grid_n : 0, h->A.slots(), nullptr);
   a.has_q = h->has_q ? 1 : 0;
   a.epoch = h->coop_epoch;
   h->coop_epoch += 2;
   if (h->has_q) {
     a.q_blocks = h->ew_grid_n;
-    a.sp.count[4] = h->ew_grid_n;
     a.qx = h->qx; a.dx = h->tmp_n; a.qtdx = h->tmp_n2; a.pq = h->pQ;
     EpiArgs qe{};
     qe.out = h->tmp_n2;
@@ -205,8 +203,7 @@ static int steps_result_words(pdhg_handle *h) {
   }
   return 0;
 }
-static int steps_prepare(pdhg_handle *h, int n, int64_t total_number_iterations, double reduction_exponent,
-                         double growth_exponent, int *max_trials_out, int *table_len_out) {
+static int steps_prepare(pdhg_handle *h, int n, const StepIO &io, int *max_trials_out, int *table_len_out) {
   int max_trials = 0, table_len = 0;
   steps_budget(n, &max_trials, &table_len);
   if (int rc = steps_result_words(h)) return rc;
@@ -222,9 +219,9 @@ static int steps_prepare(pdhg_handle *h, int n, int64_t total_number_iterations,
   }
   // the t-th trial of the launch runs with total_number_iterations = total + t + 1 and uses k1 = that + 1 (pdhg.jl:713-714)
   for (int t = 0; t < table_len; ++t) {
-    const double k1 = (double)(total_number_iterations + t + 2);
-    h->steps_pow_host[t] = pow(k1, -reduction_exponent);
-    h->steps_pow_host[table_len + t] = pow(k1, -growth_exponent);
+    const double k1 = (double)(io.iterations + t + 2);
+    h->steps_pow_host[t] = pow(k1, -io.reduction_exponent);
+    h->steps_pow_host[table_len + t] = pow(k1, -io.growth_exponent);
   }
   HIP_TRY(hipMemcpyAsync(h->steps_pow_dev, h->steps_pow_host, sizeof(double) * 2 * (size_t)table_len, hipMemcpyHostToDevice, h->stream));
   *max_trials_out = max_trials;
@@ -259,9 +256,27 @@ static int steps_wait(pdhg_handle *h, unsigned long long seq, double r[13], doub
   return fail(998, "multi-step kernel finished without publishing its results");
 }
 
-// Up to n_steps adaptive take_steps in ONE launch (steps_kernel, trial_kernel.hpp).  On return *steps_done take_steps
-// have been taken (fewer when the launch ran out of its trial budget, met numerical_error, or a barrier timed out: the
-// caller goes on from the state left).  Returns 1 when nothing could be launched (not eligible).
+// Wait for launch `seq` of h and take its result words into the handle's bookkeeping and the step state: steps and
+// trials, the average's counts and weight sums, step size, iterations, KKT passes, steps done, `entry`.  r[13]: the words,
+// for what only one launcher reads.
+static int steps_collect(pdhg_handle *h, unsigned long long seq, StepIO &io, double r[13]) {
+  double r14 = 0.0;
+  if (int rc = steps_wait(h, seq, r, &r14)) return rc;
+  const int64_t steps = (int64_t)r[1], trials = (int64_t)r[2];
+  h->n_graph_trials += trials;
+  h->sum_x_count += steps; h->sum_y_count += steps;
+  h->sum_x_weights = r[6]; h->sum_y_weights = r[7];
+  io.step_size = r[0];
+  io.iterations += trials;
+  io.kkt_passes += (double)trials;
+  io.steps_done += steps;
+  // (also after a barrier time-out: the launch may have aborted inside a take_step whose earlier trials were rejected,
+  //  and the word is written by the same thread as the other result words)
+  io.entry = r14;
+  if (r[8] != 0.0) { io.numerical_error = 1; io.steps_done += 1; }   // the failing take_step counts as taken (it is not repeated)
+  return 0;
+}
+
 // The multi-step kernel's XCD-local mode: LPs whose products are at most PDHG_COOP_LOCAL_MAX (default 32: one per compute
 // unit of an XCD) items.  8 x coop_grid workgroups are launched, the dispatcher deals them round the XCDs, those on XCD 0
 // work -- the census must find exactly coop_grid of them there.  Own barrier words and epoch (the single-trial kernel
@@ -275,12 +290,10 @@ static int steps_local_prepare(pdhg_handle *h) {
   if (h->coop_grid <= 0 || h->coop_grid > cap || dev_env("PDHG_COOP_TEST_PRETEND_WGS")) return 1;
   HIP_TRY(hipMalloc((void **)&h->lsync, sizeof(GridSync)));
   HIP_TRY(hipMemsetAsync(h->lsync, 0, sizeof(GridSync), h->stream));
-  hipLaunchKernelGGL(xcd_register_kernel, dim3(8 * h->coop_grid), dim3(TPB), 0, h->stream, h->lsync);
-  HIP_TRY(hipGetLastError());
-  GridSync host;
-  HIP_TRY(hipMemcpyAsync(&host, h->lsync, sizeof(GridSync), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (host.xcd_count[0][0] != (unsigned long long)h->coop_grid) return 1;      // the dispatcher dealt them otherwise: all-XCD mode
+  unsigned long long total = 0;
+  unsigned nxcd = 0, cnt[8];
+  if (int rc = xcd_census(h->stream, 8 * h->coop_grid, h->lsync, &total, &nxcd, cnt)) return rc;
+  if (cnt[0] != (unsigned)h->coop_grid) return 1;      // the dispatcher dealt them otherwise: all-XCD mode
   h->local_epoch = 0;
   h->local_mode = 1;
   if (getenv("PDHG_VERBOSE"))
@@ -288,12 +301,29 @@ static int steps_local_prepare(pdhg_handle *h) {
   return 0;
 }
 
-int coop_steps(pdhg_handle *h, int64_t n_steps, double reduction_exponent, double growth_exponent, double *step_size_io,
-               double primal_weight, int64_t *total_number_iterations_io, double *cumulative_kkt_passes_io,
-               int *numerical_error_out, int64_t *steps_done, double *unfinished_entry) {
-  *steps_done = 0;
-  *unfinished_entry = 0.0;
-  if (!coop_eligible(h) || h->has_q || !h->lazy_accept || h->pend_x != h->pend_y) return 1;
+// Does pdhg_take_steps_adaptive take this handle's batches with the multi-step kernel (steps_kernel)?  (The caller has
+// checked the handle: a single one, its device current.)
+static bool device_loop_for(pdhg_handle *h) {
+  // Several take_steps per launch (steps_kernel: the rule on the device; stream-layout LPs on one handle).  Bitwise the
+  // per-trial launches (tests/test_gpu_device_loop.py) and faster on every grid measured but one tie: L1-SVM 19.7k ->
+  // 23.4k it/s, random 100K 22.5k -> 28.6k, 3000 x 2500 32.7k -> 52.7k (trial_kernel.hpp, profiles/r03_trial_kernel.txt).
+  // PDHG_DEVICE_LOOP=0 / 1: never / whenever eligible; PDHG_DEVICE_LOOP_MAX_WGS: largest grid it is the default for.
+  const char *dl_env = getenv("PDHG_DEVICE_LOOP");
+  bool device_loop = dl_env && dl_env[0] == '1';
+  if (!dl_env && !h->profile && !h->has_q && coop_eligible(h)) {
+    static const int max_wgs = dev_env("PDHG_DEVICE_LOOP_MAX_WGS") ? atoi(dev_env("PDHG_DEVICE_LOOP_MAX_WGS")) : (1 << 30);
+    device_loop = h->coop_grid <= max_wgs;
+  }
+  return device_loop;
+}
+
+// Up to n_steps adaptive take_steps in ONE launch (steps_kernel, trial_kernel.hpp), from the step state `io` on.  On
+// return io counts the take_steps taken (fewer than n_steps when the launch ran out of its trial budget, met
+// numerical_error, or a barrier timed out: the caller goes on from the state left).  Returns 1 when nothing was
+// launched (the multi-step kernel is not wanted for this call, or the handle does not suit it).
+int coop_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
+  if (io.device_loop < 0) io.device_loop = device_loop_for(h) ? 1 : 0;
+  if (!io.device_loop || h->profile || !coop_eligible(h) || h->has_q || !h->lazy_accept || h->pend_x != h->pend_y) return 1;
   int rc = coop_prepare(h);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
@@ -304,7 +334,7 @@ int coop_steps(pdhg_handle *h, int64_t n_steps, double reduction_exponent, doubl
     HIP_TRY(hipMemsetAsync(h->steps_ctl, 0, sizeof(StepsCtl), h->stream));
   }
   std::lock_guard<std::mutex> one_at_a_time(coop_device_mutex(h->device));
-  if ((rc = steps_prepare(h, n, *total_number_iterations_io, reduction_exponent, growth_exponent, &max_trials, &table_len))) return rc;
+  if ((rc = steps_prepare(h, n, io, &max_trials, &table_len))) return rc;
   StepsKernelArgs a{};
   a.n = (int)h->n; a.num_eq = (int)h->num_eq;
   a.xa = h->x; a.xb = h->x_next; a.ya = h->y; a.yb = h->y_next; a.atya = h->aty; a.atyb = h->aty_next;
@@ -316,19 +346,10 @@ int coop_steps(pdhg_handle *h, int64_t n_steps, double reduction_exponent, doubl
   h->A.coop_uses -= 1; h->At.coop_uses -= 1;       // (trial_product counted one use: the launch's own count comes back with the results)
   a.uses_a = a.A.uses; a.uses_t = a.T.uses;
   a.pA = h->pA; a.pAt = h->pAt; a.pA_slots = h->A.slots(); a.pAt_stride = h->pAt_stride;
-  FinalSpec sp{};
-  sp.ptr[0] = h->pAt;                       sp.count[0] = h->At.slots();
-  sp.ptr[1] = h->pAt + h->pAt_stride;       sp.count[1] = h->At.slots();
-  sp.ptr[2] = h->pA;                        sp.count[2] = h->A.slots();
-  sp.ptr[3] = h->pAt + 2 * h->pAt_stride;   sp.count[3] = h->At.slots();
-  sp.ptr[4] = h->pQ;                        sp.count[4] = 0;
-  for (int q : {0, 1, 3}) sp.ptr_lo[q] = sp.ptr[q] + 3 * h->pAt_stride;
-  sp.ptr_lo[2] = h->pA + h->A.slots();
-  sp.ptr_lo[4] = h->pQ + h->ew_grid_n;
-  sp.out = nullptr;
+  const FinalSpec sp = trial_final_spec(h, h->At.slots(), h->A.slots(), 0, h->A.slots(), nullptr);
   memcpy(h->steps_pow_host + 2 * (size_t)table_len, &sp, sizeof sp);        // staged behind the pow tables (pinned)
   HIP_TRY(hipMemcpyAsync(&h->steps_ctl->sp, h->steps_pow_host + 2 * (size_t)table_len, sizeof sp, hipMemcpyHostToDevice, h->stream));
-  a.primal_weight = primal_weight; a.step_size = *step_size_io;
+  a.primal_weight = io.primal_weight; a.step_size = io.step_size;
   a.n_steps = n; a.max_trials = max_trials; a.table_len = table_len;
   a.pend = h->pend_x ? 1 : 0; a.pend_w = h->pend_w;
   a.wsum_x = h->sum_x_weights; a.wsum_y = h->sum_y_weights;
@@ -357,12 +378,12 @@ int coop_steps(pdhg_handle *h, int64_t n_steps, double reduction_exponent, doubl
   HIP_TRY(hipGetLastError());
   const auto c2 = std::chrono::steady_clock::now();
   h->t_launch += std::chrono::duration<double>(c2 - c1).count();
-  double r[13], r14 = 0.0;
-  if ((rc = steps_wait(h, a.seq, r, &r14))) return rc;
+  double r[13];
+  if ((rc = steps_collect(h, a.seq, io, r))) return rc;
   h->t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - c2).count();
-  const int64_t steps = (int64_t)r[1], trials = (int64_t)r[2];
+  const int64_t trials = (int64_t)r[2];
   const bool flip = r[3] != 0.0, aborted = r[9] != 0.0 || r[11] != 0.0;
-  h->steps_launches += 1; h->steps_trials += trials; h->n_graph_trials += trials;
+  h->steps_launches += 1; h->steps_trials += trials;
   if (local) { h->local_epoch = (unsigned long long)r[10]; h->local_launches += 1; }
   else h->coop_epoch = (unsigned long long)r[10];
   h->A.coop_uses += (unsigned long long)trials + (aborted ? 1ull : 0ull);
@@ -370,17 +391,7 @@ int coop_steps(pdhg_handle *h, int64_t n_steps, double reduction_exponent, doubl
   if (flip) { std::swap(h->x, h->x_next); std::swap(h->y, h->y_next); std::swap(h->aty, h->aty_next); }
   h->pend_x = h->pend_y = r[4] != 0.0;
   h->pend_w = r[5];
-  h->sum_x_count += steps; h->sum_y_count += steps;
-  h->sum_x_weights = r[6]; h->sum_y_weights = r[7];
   if (trials > 0 || aborted) h->state_version += 1;     // (bump_version of a single handle)
-  *step_size_io = r[0];
-  *total_number_iterations_io += trials;
-  *cumulative_kkt_passes_io += (double)trials;
-  *steps_done = steps;
-  // (also after a barrier time-out: the launch may have aborted inside a take_step whose earlier trials were rejected,
-  //  and the word is written by the same thread as the other result words)
-  *unfinished_entry = r14;
-  if (r[8] != 0.0) { *numerical_error_out = 1; *steps_done = steps + 1; }   // the failing take_step counts as taken (it is not repeated)
   if (aborted && local) {
     // the XCD-local form failed (a workgroup of the launch was not where the census saw it): the all-XCD form from here on
     h->local_mode = 0;

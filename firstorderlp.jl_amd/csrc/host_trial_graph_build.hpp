@@ -29,10 +29,7 @@ struct GraphArgs {
   dim3 primal_grid;
   EpiArgs dual_epi;
   GraphArgs(pdhg_handle *h_, double sigma) : h(h_), n((int)h_->n), primal_grid(ew_grid((h_->n + 1) / 2)) {
-    dual_epi = EpiArgs{};
-    dual_epi.y = h->y; dual_epi.b = h->b; dual_epi.y_next = h->y_next; dual_epi.sigma = sigma;
-    dual_epi.num_eq = (int)h->num_eq; dual_epi.partials = h->pA; dual_epi.stride = h->A.slots(); dual_epi.lo_offset = h->A.slots();
-    if (h->pend_y) { dual_epi.sum_y = h->sum_y; dual_epi.avg_w = h->pend_w; }
+    dual_epi = dual_epilogue(h, sigma);
   }
 };
 
@@ -229,25 +226,13 @@ int graph_build(pdhg_handle *h, pdhg_handle::TrialGraph &G, double tau, double t
   if (dual_done.empty()) dual_done.push_back(G.n_primal);
   const CsrDev &A = h->A;
   const CsrDev &T = h->At;
-  EpiArgs te{};
-  te.x = h->x; te.x_next = h->x_next; te.aty = h->aty; te.aty_next = h->aty_next;
-  te.partials = h->pAt; te.stride = h->pAt_stride; te.lo_offset = 3 * h->pAt_stride;
   {
-    int rc = graph_add_spmv<MODE_ATY, 1>(h, G.graph, T, h->y_next, te, dual_done, aty_done, nullptr, nullptr);
+    int rc = graph_add_spmv<MODE_ATY, 1>(h, G.graph, T, h->y_next, aty_epilogue(h), dual_done, aty_done, nullptr, nullptr);
     if (rc) return rc;
   }
   if (aty_done.empty()) aty_done = dual_done;
   // K6b -> pinned host memory + sequence number
-  FinalSpec sp{};
-  sp.ptr[0] = h->pAt;                       sp.count[0] = T.slots();
-  sp.ptr[1] = h->pAt + h->pAt_stride;       sp.count[1] = T.slots();
-  sp.ptr[2] = h->pA;                        sp.count[2] = A.slots();
-  sp.ptr[3] = h->pAt + 2 * h->pAt_stride;   sp.count[3] = T.slots();
-  sp.ptr[4] = h->pQ;                        sp.count[4] = 0;
-  for (int q : {0, 1, 3}) sp.ptr_lo[q] = sp.ptr[q] + 3 * h->pAt_stride;
-  sp.ptr_lo[2] = h->pA + A.slots();
-  sp.ptr_lo[4] = h->pQ + h->ew_grid_n;
-  sp.out = nullptr;
+  const FinalSpec sp = trial_final_spec(h, T.slots(), A.slots(), 0, A.slots(), nullptr);
   hipGraphNode_t fin = nullptr;
   HIP_TRY(graph_add_kernel(G.graph, &fin, aty_done, (const void *)final_reduce_host_kernel, dim3(1), dim3(FINAL_TPB), sp,
                            h->seq_dev, h->res_host));
@@ -259,8 +244,8 @@ int graph_build(pdhg_handle *h, pdhg_handle::TrialGraph &G, double tau, double t
   return 0;
 }
 
-int graph_trial(pdhg_handle *h, double step_size, double primal_weight, double theta, double out[5]) {
-  const double tau = step_size / primal_weight, sigma = primal_weight * step_size;
+int graph_trial(pdhg_handle *h, const TrialArgs &ta, double out[5]) {
+  const double tau = ta.step_size / ta.primal_weight, sigma = ta.primal_weight * ta.step_size, theta = ta.theta;
   pdhg_handle::TrialGraph *G = nullptr;
   for (int k = 0; k < 2; ++k)
     if (h->tgraph[k].exec && h->tgraph[k].x == h->x && h->tgraph[k].y == h->y && h->tgraph[k].aty == h->aty)

@@ -486,13 +486,50 @@ int launch_xbar(pdhg_handle *h, double theta) {
   return 0;
 }
 
-int launch_dual(pdhg_handle *h, double sigma) {
-  ProfScope ps(h, PDHG_K_SPMV_DUAL);
+// ---- what every path that stages a trial fills the same way (separate launches, graph, one-launch kernels, group kernel) ----
+struct TrialArgs {
+  double step_size, primal_weight, theta;
+  bool primal;      // K1+K2 first (pdhg_trial_step); false: xbar only (pdhg_trial_dual)
+};
+
+// the dual step fused into A xbar (K3+K4), with the deferred sum_y update when one is pending; the dy^2 block partials
+// go to pA, one slot per block of A (column-chunk passes override the two strides with their last layout's slots)
+EpiArgs dual_epilogue(const pdhg_handle *h, double sigma) {
   EpiArgs e{};
   e.y = h->y; e.b = h->b; e.y_next = h->y_next; e.sigma = sigma; e.num_eq = (int)h->num_eq;
   e.partials = h->pA; e.stride = h->A.slots(); e.lo_offset = h->A.slots();
   if (h->pend_y) { e.sum_y = h->sum_y; e.avg_w = h->pend_w; }
-  const int rc = launch_spmv<MODE_DUAL, 0>(h, h->A, h->xbar, e);
+  return e;
+}
+
+// the interaction sums fused into A'y' (K5+K6): three quantities in pAt, their low parts behind them
+EpiArgs aty_epilogue(const pdhg_handle *h) {
+  EpiArgs e{};
+  e.x = h->x; e.x_next = h->x_next; e.aty = h->aty; e.aty_next = h->aty_next;
+  e.partials = h->pAt; e.stride = h->pAt_stride; e.lo_offset = 3 * h->pAt_stride;
+  return e;
+}
+
+// The second-stage reduction of a trial's block partials: n_int interaction partials per quantity in pAt, n_dy dy^2
+// partials in pA with their low parts dy_lo further on, q_count partials of the QP dot in pQ; out: where the five
+// sums go on the device (nullptr for the kernels that publish them to the host themselves).
+FinalSpec trial_final_spec(const pdhg_handle *h, int n_int, int n_dy, int q_count, int dy_lo, double *out) {
+  FinalSpec sp{};
+  sp.ptr[0] = h->pAt;                       sp.count[0] = n_int;
+  sp.ptr[1] = h->pAt + h->pAt_stride;       sp.count[1] = n_int;
+  sp.ptr[2] = h->pA;                        sp.count[2] = n_dy;
+  sp.ptr[3] = h->pAt + 2 * h->pAt_stride;   sp.count[3] = n_int;
+  sp.ptr[4] = h->pQ;                        sp.count[4] = q_count;
+  for (int q : {0, 1, 3}) sp.ptr_lo[q] = sp.ptr[q] + 3 * h->pAt_stride;
+  sp.ptr_lo[2] = h->pA + dy_lo;
+  sp.ptr_lo[4] = h->pQ + h->ew_grid_n;
+  sp.out = out;
+  return sp;
+}
+
+int launch_dual(pdhg_handle *h, double sigma) {
+  ProfScope ps(h, PDHG_K_SPMV_DUAL);
+  const int rc = launch_spmv<MODE_DUAL, 0>(h, h->A, h->xbar, dual_epilogue(h, sigma));
   if (!rc) h->pend_y = false;
   return rc;
 }
@@ -514,10 +551,8 @@ int launch_dual_chunked(pdhg_handle *h, double sigma, bool wait_events) {
       e.out = h->chunk_carry;
       rc = launch_spmv<MODE_PLAIN, 0>(h, h->Achunk[(size_t)c], h->xchunk + (size_t)c * h->Achunk[(size_t)c].cols, e, init);
     } else {
-      EpiArgs e{};
-      e.y = h->y; e.b = h->b; e.y_next = h->y_next; e.sigma = sigma; e.num_eq = (int)h->num_eq;
-      e.partials = h->pA; e.stride = dual_chunk_slots(h); e.lo_offset = dual_chunk_slots(h);
-      if (h->pend_y) { e.sum_y = h->sum_y; e.avg_w = h->pend_w; }
+      EpiArgs e = dual_epilogue(h, sigma);
+      e.stride = e.lo_offset = dual_chunk_slots(h);
       rc = launch_spmv<MODE_DUAL, 0>(h, h->Achunk[(size_t)c], h->xchunk + (size_t)c * h->Achunk[(size_t)c].cols, e, init);
       if (!rc) h->pend_y = false;
     }
@@ -527,10 +562,7 @@ int launch_dual_chunked(pdhg_handle *h, double sigma, bool wait_events) {
 
 int launch_aty_fused(pdhg_handle *h) {
   ProfScope ps(h, PDHG_K_SPMV_ATY);
-  EpiArgs e{};
-  e.x = h->x; e.x_next = h->x_next; e.aty = h->aty; e.aty_next = h->aty_next;
-  e.partials = h->pAt; e.stride = h->pAt_stride; e.lo_offset = 3 * h->pAt_stride;
-  return launch_spmv<MODE_ATY, 1>(h, h->At, h->y_next, e);
+  return launch_spmv<MODE_ATY, 1>(h, h->At, h->y_next, aty_epilogue(h));
 }
 
 int launch_aty_plain(pdhg_handle *h, const double *yin, double *out) {
@@ -574,20 +606,10 @@ __global__ __launch_bounds__(FINAL_TPB) void final_reduce_host_kernel(FinalSpec 
 }
 
 // second-stage reduction of the trial's block partials into scal_dev[0..5)
-// (dy_lo: where the low parts of the dy^2 partials start behind p_dy; < 0: the handle's own A.slots())
-int launch_final(pdhg_handle *h, const double *p_int, int n_int, int stride_int, const double *p_dy, int n_dy,
-                 int q_count, bool to_host = false, int dy_lo = -1) {
+// (dy_lo: where the low parts of the dy^2 partials start behind pA; < 0: the handle's own A.slots())
+int launch_final(pdhg_handle *h, int n_int, int n_dy, int q_count, bool to_host = false, int dy_lo = -1) {
   ProfScope ps(h, PDHG_K_FINAL);
-  FinalSpec sp{};
-  sp.ptr[0] = p_int;                  sp.count[0] = n_int;
-  sp.ptr[1] = p_int + stride_int;     sp.count[1] = n_int;
-  sp.ptr[2] = p_dy;                   sp.count[2] = n_dy;
-  sp.ptr[3] = p_int + 2 * stride_int; sp.count[3] = n_int;
-  sp.ptr[4] = h->pQ;                  sp.count[4] = q_count;
-  for (int q : {0, 1, 3}) sp.ptr_lo[q] = sp.ptr[q] + 3 * stride_int;
-  sp.ptr_lo[2] = p_dy + (dy_lo >= 0 ? dy_lo : h->A.slots());
-  sp.ptr_lo[4] = h->pQ + h->ew_grid_n;
-  sp.out = h->scal_dev;
+  const FinalSpec sp = trial_final_spec(h, n_int, n_dy, q_count, dy_lo >= 0 ? dy_lo : h->A.slots(), h->scal_dev);
   if (to_host) {       // results straight into the pinned result word (the caller polls it: wait_result_word)
     hipLaunchKernelGGL(final_reduce_host_kernel, dim3(1), dim3(FINAL_TPB), 0, h->stream, sp, h->seq_dev, h->res_host);
     h->seq_expected += 1;

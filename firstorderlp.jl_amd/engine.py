@@ -17,6 +17,7 @@ from . import _lib
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int64)
+_int_p = ctypes.POINTER(ctypes.c_int)
 
 
 def _d(a):
@@ -475,3 +476,44 @@ class HipPdhgEngine:
         for k in ("A", "At"):    # width in bits of an entry's column field
             out[k + "_tile_shift"] = max(1, (out[k + "_tile_cols"] - 1).bit_length()) if out[k + "_tile_cols"] else 0
         return out
+
+
+class _MemberEngine(HipPdhgEngine):
+    """A non-owning view of one member of a batch or a fleet: its owner frees it (``close`` only forgets the handle)."""
+
+    def close(self):
+        self._h = None
+
+
+class _MemberOwner:
+    """What ``HipPdhgBatch`` and ``HipPdhgFleet`` share: the library ``_L``, the owning handle ``_h``, ``members``
+    (``_MemberEngine`` views, freed with the handle) and the marshalling of their ``take_steps_adaptive``."""
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for eng in self.members:
+                eng._h = None
+            self._L.pdhg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _take_steps_adaptive(self, call, n_steps, reduction_exponent, growth_exponent, step_sizes, primal_weights,
+                             total_number_iterations, cumulative_kkt_passes, *active):
+        """``call(handle, n_steps, exponents, the members' four scalar arrays, numerical_error, *active, steps_done)``
+        with one array entry per member.  Returns arrays (step_sizes, total_number_iterations, cumulative_kkt_passes,
+        numerical_error, steps_done)."""
+        K = len(self.members)
+        ss = _d(np.array(np.broadcast_to(step_sizes, (K,)), dtype=np.float64))
+        pw = _d(np.array(np.broadcast_to(primal_weights, (K,)), dtype=np.float64))
+        it = np.array(np.broadcast_to(total_number_iterations, (K,)), dtype=np.int64)
+        kkt = _d(np.array(np.broadcast_to(cumulative_kkt_passes, (K,)), dtype=np.float64))
+        err = np.zeros(K, dtype=np.int32)
+        done = np.zeros(K, dtype=np.int64)
+        _lib.check(call(self._h, n_steps, float(reduction_exponent), float(growth_exponent), _pd(ss), _pd(pw), _pi(it),
+                        _pd(kkt), err.ctypes.data_as(_int_p), *active, _pi(done)))
+        return ss, it, kkt, err.astype(bool), done

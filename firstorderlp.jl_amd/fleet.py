@@ -18,22 +18,14 @@ import time as _time
 import numpy as np
 
 from . import _lib
-from .engine import HipPdhgEngine, _d, _i, _pd, _pi
+from .engine import _MemberEngine, _MemberOwner, _d, _i, _pd, _pi
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams, _check_inputs,
                                           _constant_step_estimate, _device_scaled_problem, _drive_solves,
-                                          _host_scaled_problem, _rescales_on_device, _Solve, take_steps)
-
-_int_p = ctypes.POINTER(ctypes.c_int)
-
-
-class _MemberEngine(HipPdhgEngine):
-    """A non-owning view of a member: the fleet frees it (``close`` only forgets the handle)."""
-
-    def close(self):
-        self._h = None
+                                          _host_scaled_problem, _pack_step_states, _rescales_on_device, _Solve,
+                                          _unpack_step_states, take_steps)
 
 
-class HipPdhgFleet:
+class HipPdhgFleet(_MemberOwner):
     """K independent problems on one GPU and one stream (``pdhg_create_fleet`` / ``pdhg_fleet_add``)."""
 
     takes_original_problem = True
@@ -80,36 +72,15 @@ class HipPdhgFleet:
             raise
         return fleet
 
-    def close(self):
-        if getattr(self, "_h", None):
-            for eng in self.members:
-                eng._h = None
-            self._L.pdhg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def take_steps_adaptive(self, n_steps, reduction_exponent, growth_exponent, step_sizes, primal_weights,
                             total_number_iterations, cumulative_kkt_passes):
         """``n_steps[k]`` take_steps of member k, for every k (0: the member is left alone); the small LPs among them in
         one launch.  Returns arrays (step_sizes, total_number_iterations, cumulative_kkt_passes, numerical_error,
         steps_done)."""
-        K = self.K
-        ns = np.array(np.broadcast_to(n_steps, (K,)), dtype=np.int64)
-        ss = _d(np.array(np.broadcast_to(step_sizes, (K,)), dtype=np.float64))
-        pw = _d(np.array(np.broadcast_to(primal_weights, (K,)), dtype=np.float64))
-        it = np.array(np.broadcast_to(total_number_iterations, (K,)), dtype=np.int64)
-        kkt = _d(np.array(np.broadcast_to(cumulative_kkt_passes, (K,)), dtype=np.float64))
-        err = np.zeros(K, dtype=np.int32)
-        done = np.zeros(K, dtype=np.int64)
-        _lib.check(self._L.pdhg_fleet_take_steps_adaptive(
-            self._h, _pi(ns), float(reduction_exponent), float(growth_exponent), _pd(ss), _pd(pw), _pi(it), _pd(kkt),
-            err.ctypes.data_as(_int_p), _pi(done)))
-        return ss, it, kkt, err.astype(bool), done
+        ns = np.array(np.broadcast_to(n_steps, (self.K,)), dtype=np.int64)
+        return self._take_steps_adaptive(self._L.pdhg_fleet_take_steps_adaptive, _pi(ns), reduction_exponent,
+                                         growth_exponent, step_sizes, primal_weights, total_number_iterations,
+                                         cumulative_kkt_passes)
 
     def info(self):
         """dict(members, shared_launches, carried, single): the last two describe the last ``take_steps_adaptive``."""
@@ -133,26 +104,15 @@ def _step_fleet(fleet, solves, policy, requests):
             and os.environ.get("PDHG_PY_TAKE_STEP", "0") != "1"):
         K = len(solves)
         slot = {id(mb): k for k, mb in enumerate(solves)}
-        ns, it = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
-        ss, pw, kkt = np.ones(K), np.ones(K), np.zeros(K)
+        placed = [(slot[id(mb)], mb.state) for mb, _ in requests]
+        ns = np.zeros(K, dtype=np.int64)
         for mb, steps in requests:
-            k = slot[id(mb)]
-            ns[k] = steps
-            ss[k], pw[k] = mb.state.step_size, mb.state.primal_weight
-            it[k], kkt[k] = mb.state.total_number_iterations, mb.state.cumulative_kkt_passes
+            ns[slot[id(mb)]] = steps
+        packed = _pack_step_states(K, placed)
         t0 = _time.time()
-        ss, it, kkt, err, done = fleet.take_steps_adaptive(ns, policy.reduction_exponent, policy.growth_exponent, ss, pw,
-                                                           it, kkt)
+        results = fleet.take_steps_adaptive(ns, policy.reduction_exponent, policy.growth_exponent, *packed)
         dt = _time.time() - t0
-        out = []
-        for mb, _ in requests:
-            k = slot[id(mb)]
-            mb.state.step_size, mb.state.total_number_iterations = float(ss[k]), int(it[k])
-            mb.state.cumulative_kkt_passes = float(kkt[k])
-            if err[k]:
-                mb.state.numerical_error = True
-            out.append((mb, int(done[k]), dt))
-        return out
+        return [(mb, d, dt) for (mb, _), d in zip(requests, _unpack_step_states(placed, *results))]
     out = []
     for mb, steps in requests:
         t0 = _time.time()

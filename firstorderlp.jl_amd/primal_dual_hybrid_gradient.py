@@ -122,6 +122,39 @@ def adaptive_step_rule(raw, primal_weight, step_size, total_number_iterations, s
     return step_size <= step_size_limit, False, julia_min(first_term, second_term)
 
 
+# ---- the adaptive policy's scalars to and from the library's take_step(s) calls: one engine, or the members of a batch
+# / a fleet side by side (``placed``: (slot, solver_state) pairs, the slot indexing the call's arrays of K entries)
+
+def _native_step_args(step_params, solver_state):
+    return (step_params.reduction_exponent, step_params.growth_exponent, solver_state.step_size,
+            solver_state.primal_weight, solver_state.total_number_iterations, solver_state.cumulative_kkt_passes)
+
+
+def _store_step_state(solver_state, step_size, total_number_iterations, cumulative_kkt_passes, numerical_error):
+    solver_state.step_size = float(step_size)
+    solver_state.total_number_iterations = int(total_number_iterations)
+    solver_state.cumulative_kkt_passes = float(cumulative_kkt_passes)
+    if numerical_error:
+        solver_state.numerical_error = True
+
+
+def _pack_step_states(K, placed):
+    """(step_sizes, primal_weights, total_number_iterations, cumulative_kkt_passes) of a K-member call; the slots that
+    ``placed`` does not name hold harmless values."""
+    ss, pw, kkt = np.ones(K), np.ones(K), np.zeros(K)
+    it = np.zeros(K, dtype=np.int64)
+    for k, st in placed:
+        ss[k], pw[k], it[k], kkt[k] = st.step_size, st.primal_weight, st.total_number_iterations, st.cumulative_kkt_passes
+    return ss, pw, it, kkt
+
+
+def _unpack_step_states(placed, step_sizes, total_number_iterations, cumulative_kkt_passes, numerical_error, steps_done):
+    """What a K-member call returned, back into the states of ``placed``; the steps each of them took."""
+    for k, st in placed:
+        _store_step_state(st, step_sizes[k], total_number_iterations[k], cumulative_kkt_passes[k], numerical_error[k])
+    return [int(steps_done[k]) for k, _ in placed]
+
+
 def take_step_adaptive(step_params, solver_state):
     """take_step(::AdaptiveStepsizeParams, ...)  pdhg.jl:653-731.
 
@@ -131,13 +164,7 @@ def take_step_adaptive(step_params, solver_state):
     the loop below, which is also what every other engine uses."""
     eng = solver_state.engine
     if hasattr(eng, "take_step_adaptive") and os.environ.get("PDHG_PY_TAKE_STEP", "0") != "1":
-        (solver_state.step_size, solver_state.total_number_iterations,
-         solver_state.cumulative_kkt_passes, err) = eng.take_step_adaptive(
-            step_params.reduction_exponent, step_params.growth_exponent, solver_state.step_size,
-            solver_state.primal_weight, solver_state.total_number_iterations,
-            solver_state.cumulative_kkt_passes)
-        if err:
-            solver_state.numerical_error = True
+        _store_step_state(solver_state, *eng.take_step_adaptive(*_native_step_args(step_params, solver_state)))
         return
     step_size = solver_state.step_size
     done = False
@@ -224,13 +251,8 @@ def take_steps(step_params, solver_state, n_steps, is_lp=True):
     eng = solver_state.engine
     if (isinstance(step_params, AdaptiveStepsizeParams) and hasattr(eng, "take_steps_adaptive")
             and os.environ.get("PDHG_PY_TAKE_STEP", "0") != "1"):
-        (solver_state.step_size, solver_state.total_number_iterations,
-         solver_state.cumulative_kkt_passes, err, done) = eng.take_steps_adaptive(
-            n_steps, step_params.reduction_exponent, step_params.growth_exponent,
-            solver_state.step_size, solver_state.primal_weight,
-            solver_state.total_number_iterations, solver_state.cumulative_kkt_passes)
-        if err:
-            solver_state.numerical_error = True
+        *results, done = eng.take_steps_adaptive(n_steps, *_native_step_args(step_params, solver_state))
+        _store_step_state(solver_state, *results)
         return done
     done = 0
     while done < n_steps:
