@@ -39,23 +39,8 @@ static int ev_ensure_host(pdhg_handle *h) {
   return 0;
 }
 static int ev_wait_host(pdhg_handle *h, int k, unsigned long long seq, double *out) {
-  const volatile unsigned long long *bits = reinterpret_cast<const volatile unsigned long long *>(h->ev_host);
-  auto ready = [&]() -> bool {
-    if (bits[EV_HOST_SEQ] != seq) return false;
-    unsigned long long w[EV_HOST_SLOTS];
-    unsigned long long ck = EV_CHECK_SALT ^ seq ^ ((unsigned long long)k << 56);
-    for (int q = 0; q < k; ++q) { w[q] = bits[q]; ck ^= w[q] * (2ull * (unsigned long long)q + 1ull); }
-    if (ck != bits[EV_HOST_CK]) return false;
-    for (int q = 0; q < k; ++q) memcpy(&out[q], &w[q], 8);
-    return true;
-  };
-  for (long spin = 0; spin < 40000000L; ++spin) {
-    if (ready()) return 0;
-    if ((spin & 0xFFFFF) == 0xFFFFF && hipStreamQuery(h->stream) != hipErrorNotReady) break;
-  }
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (ready()) return 0;
-  return fail(998, "evaluation reduction finished without publishing its results");
+  return wait_words(h->stream, h->ev_host, EV_HOST_SLOTS, k, seq, out, 40000000L,
+                    "evaluation reduction finished without publishing its results");
 }
 
 // The evaluation reductions publish into pinned host memory (one handle) unless PDHG_EVAL_HOST_WORD=0 (dev): decided in

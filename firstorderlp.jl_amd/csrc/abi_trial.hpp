@@ -382,7 +382,7 @@ static int group_coop_trial(const Shards &L, const TrialArgs &ta, double out[5])
     pdhg_handle *s = L.p[i];
     HIP_TRY(hipSetDevice(s->device));
     double r[5];
-    const int rc = wait_result_word(s, r, true);
+    const int rc = wait_result_word(s, r);
     if (rc) return rc;
     failed = failed || s->res_error != 0.0;
     for (int q = 0; q < 4; ++q) sums[q] = (i == 0) ? r[q] : sums[q] + r[q];      // rank order (L.p is ascending in rank)

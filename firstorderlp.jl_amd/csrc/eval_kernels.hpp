@@ -135,14 +135,8 @@ __global__ __launch_bounds__(TPB) void wave_sums_selftest_kernel(unsigned long l
 // wave q mod 16, which adds / maxes its `count` partials in a fixed order (lane i takes i, i + 64, ..., eight
 // loads in flight at a time; then the shuffle tree) -- no workgroup barrier between quantities, so 16 of them
 // cost what one does.
-// host_out != nullptr: the results also go straight into pinned host memory, followed by a checksum and the
-// call's sequence number ([EV_HOST_CK], [EV_HOST_SEQ]); the host polls those instead of a device-to-host
-// copy + stream synchronisation (20-30 us per round trip on this runtime, and the trust-region search makes
-// five to eight round trips per call).  No system-scope fence: the words may land in any order, a read counts
-// only when sequence number AND checksum match (as for the trial kernel's result word).
-constexpr int EV_HOST_SLOTS = 32;             // >= SCAL_MAX (dist.hpp)
-constexpr int EV_HOST_CK = EV_HOST_SLOTS, EV_HOST_SEQ = EV_HOST_SLOTS + 1;
-constexpr unsigned long long EV_CHECK_SALT = 0xD1B54A32D192ED03ull;
+// host_out != nullptr: the results also go straight into pinned host memory as result words (grid_sync.hpp) that
+// the host polls (the trust-region search makes five to eight round trips per call).
 __global__ __launch_bounds__(FINAL_TPB) void multi_final_kernel(const double *__restrict__ partials, int stride,
                                                                 int count, int ns, int nm, double *__restrict__ out,
                                                                 double *host_out, unsigned long long seq,
@@ -166,15 +160,7 @@ __global__ __launch_bounds__(FINAL_TPB) void multi_final_kernel(const double *__
   }
   if (host_out) {
     __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long ck = EV_CHECK_SALT ^ seq ^ ((unsigned long long)k << 56);
-      for (int q = 0; q < k; ++q) {
-        host_out[q] = res[q];
-        ck ^= (unsigned long long)__double_as_longlong(res[q]) * (2ull * (unsigned long long)q + 1ull);
-      }
-      host_out[EV_HOST_CK] = __longlong_as_double((long long)ck);
-      host_out[EV_HOST_SEQ] = __longlong_as_double((long long)seq);
-    }
+    if (threadIdx.x == 0) publish_words(host_out, EV_HOST_SLOTS, k, seq, [&](int q) { return res[q]; });
   }
 }
 
@@ -600,13 +586,7 @@ __global__ __launch_bounds__(TRS_TPB) void tr_small_kernel(TrSmallArgs a) {
       s_out[2] = S.at.v[2] + S.tstar * S.at.v[3];
       s_out[5] = S.tstar; s_out[6] = (double)S.passes;
     }
-    unsigned long long ck = EV_CHECK_SALT ^ a.seq ^ (8ull << 56);
-    for (int q = 0; q < 8; ++q) {
-      a.host_out[q] = s_out[q];
-      ck ^= (unsigned long long)__double_as_longlong(s_out[q]) * (2ull * (unsigned long long)q + 1ull);
-    }
-    a.host_out[EV_HOST_CK] = __longlong_as_double((long long)ck);
-    a.host_out[EV_HOST_SEQ] = __longlong_as_double((long long)a.seq);
+    publish_words(a.host_out, EV_HOST_SLOTS, 8, a.seq, [&](int q) { return s_out[q]; });
   }
 }
 

@@ -25,7 +25,7 @@
 //   ticket    the shard's last workgroup runs the second stage and publishes the shard's five sums to pinned host
 //             memory; the host adds the shards' sums in rank order and decides (as for every group path).
 //
-// Cross-shard barrier = the XCD-scoped grid barrier of trial_kernel.hpp with one more level: the shard's last XCD leader
+// Cross-shard barrier = the XCD-scoped grid barrier of grid_sync.hpp with one more level: the shard's last XCD leader
 // arrives on a counter all shards share (system scope) and releases its fellow leaders when every shard has arrived; the
 // write-back / invalidate of each XCD's L2 around it are system-scope (`buffer_wbl2 sc0 sc1` / `buffer_inv sc0 sc1`) so
 // that data another DEVICE wrote into this one's memory is read fresh.  Every spin is bounded; a barrier that cannot
@@ -74,52 +74,37 @@ struct GroupTrialArgs {
   int relaxed;
 };
 
-// grid barrier (trial_kernel.hpp) + the cross-shard level.  epoch: this shard's barrier count; xepoch: the group's
+// grid barrier (grid_sync.hpp) + the cross-shard level.  epoch: this shard's barrier count; xepoch: the group's
 // count of cross-shard barriers (the same on every shard).
 __device__ __forceinline__ void group_barrier(GridSync *s, GroupSync *gs, unsigned long long epoch, unsigned long long xepoch,
                                               unsigned nxcd, const unsigned *xcd_cnt, int world) {
-  __syncthreads();
-  if (threadIdx.x == 0 && __hip_atomic_load(&s->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-    const unsigned x = xcc_id();
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long cnt = xcd_cnt[x];
-    const unsigned long long prev = __hip_atomic_fetch_add(&s->xcd_arrive[x][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned x = xcc_id();
+  xcd_barrier<true>(s, epoch, x, xcd_cnt[x], ~0ull, 8ull, [&] {
     long spins = 0;
-    if (prev + 1 == cnt * epoch) {
-      asm volatile("buffer_wbl2 sc0 sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");      // system scope: peers read this shard's stores
-      const unsigned long long g = __hip_atomic_fetch_add(&s->global[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (g + 1 == (unsigned long long)nxcd * epoch) {
-        // this shard's last XCD: the shard has arrived; meet the other shards, then release the fellow leaders
-        __hip_atomic_fetch_add(&gs->arrive[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        while (__hip_atomic_load(&gs->arrive[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < (unsigned long long)world * xepoch) {
-          __builtin_amdgcn_s_sleep(1);
-          if (++spins > GRID_SPIN_LIMIT ||
-              ((spins & 0x3FF) == 0 && __hip_atomic_load(&gs->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0)) {
-            __hip_atomic_store(&gs->error[0], 6ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&s->error[0], 6ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-        }
-        __hip_atomic_store(&s->xrelease[0], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        while (__hip_atomic_load(&s->xrelease[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < epoch) {
-          __builtin_amdgcn_s_sleep(1);
-          if (++spins > GRID_SPIN_LIMIT) { __hip_atomic_store(&s->error[0], 7ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-          if ((spins & 0x3FF) == 0 && __hip_atomic_load(&s->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
+    asm volatile("buffer_wbl2 sc0 sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");      // system scope: peers read this shard's stores
+    const unsigned long long g = __hip_atomic_fetch_add(&s->global[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (g + 1 == (unsigned long long)nxcd * epoch) {
+      // this shard's last XCD: the shard has arrived; meet the other shards, then release the fellow leaders
+      __hip_atomic_fetch_add(&gs->arrive[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      while (__hip_atomic_load(&gs->arrive[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < (unsigned long long)world * xepoch) {
+        __builtin_amdgcn_s_sleep(1);
+        if (++spins > GRID_SPIN_LIMIT ||
+            ((spins & 0x3FF) == 0 && __hip_atomic_load(&gs->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0)) {
+          __hip_atomic_store(&gs->error[0], 6ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(&s->error[0], 6ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          break;
         }
       }
-      asm volatile("buffer_inv sc0 sc1" ::: "memory");
-      __hip_atomic_store(&s->xcd_release[x][0], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&s->xrelease[0], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else {
-      while (__hip_atomic_load(&s->xcd_release[x][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < epoch) {
+      while (__hip_atomic_load(&s->xrelease[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < epoch) {
         __builtin_amdgcn_s_sleep(1);
-        if (++spins > GRID_SPIN_LIMIT) { __hip_atomic_store(&s->error[0], 8ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+        if (++spins > GRID_SPIN_LIMIT) { __hip_atomic_store(&s->error[0], 7ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
         if ((spins & 0x3FF) == 0 && __hip_atomic_load(&s->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
       }
     }
-    asm volatile("s_dcache_inv" ::: "memory");
-  }
-  __syncthreads();
+    asm volatile("buffer_inv sc0 sc1" ::: "memory");
+  });
 }
 
 // the shards of one device's launch: their argument blocks (device memory) and the first workgroup of each
@@ -142,16 +127,14 @@ __global__ __launch_bounds__(TPB) void group_register_kernel(GroupDeviceArgs d, 
 // blocks are copied to device memory first (GroupDeviceArgs).
 constexpr int GROUP_INLINE_SHARDS = 2;
 
-__device__ __forceinline__ void group_trial_body(const GroupTrialArgs &a, int w, int nwg, double *prod, double (*red)[TPB / WAVE],
-                                                 int &done_flag);
+__device__ __forceinline__ void group_trial_body(const GroupTrialArgs &a, int w, int nwg, double *prod, double (*red)[TPB / WAVE]);
 
 __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void group_trial_kernel(GroupDeviceArgs d) {
   __shared__ double prod[BLOCK_NNZ];
   __shared__ double red[6][TPB / WAVE];
-  __shared__ int done_flag;
   int sh = 0;
   while (sh + 1 < d.nshards && (int)blockIdx.x >= d.base[sh + 1]) ++sh;
-  group_trial_body(d.shard[sh], (int)blockIdx.x - d.base[sh], d.base[sh + 1] - d.base[sh], prod, red, done_flag);
+  group_trial_body(d.shard[sh], (int)blockIdx.x - d.base[sh], d.base[sh + 1] - d.base[sh], prod, red);
 }
 // (one kernel parameter per shard: an array of blocks inside one parameter is copied to scratch as soon as a block is
 //  indexed -- 2.3 KB per lane; separate parameters stay in the kernel-argument segment)
@@ -159,13 +142,11 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void group_trial_inli
                                                                                           int base1, int total) {
   __shared__ double prod[BLOCK_NNZ];
   __shared__ double red[6][TPB / WAVE];
-  __shared__ int done_flag;
-  if (nshards > 1 && (int)blockIdx.x >= base1) group_trial_body(a1, (int)blockIdx.x - base1, total - base1, prod, red, done_flag);
-  else group_trial_body(a0, (int)blockIdx.x, nshards > 1 ? base1 : total, prod, red, done_flag);
+  if (nshards > 1 && (int)blockIdx.x >= base1) group_trial_body(a1, (int)blockIdx.x - base1, total - base1, prod, red);
+  else group_trial_body(a0, (int)blockIdx.x, nshards > 1 ? base1 : total, prod, red);
 }
 
-__device__ __forceinline__ void group_trial_body(const GroupTrialArgs &a, int w, int nwg, double *prod, double (*red)[TPB / WAVE],
-                                                 int &done_flag) {
+__device__ __forceinline__ void group_trial_body(const GroupTrialArgs &a, int w, int nwg, double *prod, double (*red)[TPB / WAVE]) {
   unsigned long long epoch = a.epoch, xepoch = a.xepoch;
   Prefetched f;
   // ---- phase 0: the owned slice of x' and xbar; xbar goes to every shard (elementwise: any distribution gives the same bits)
@@ -226,37 +207,14 @@ __device__ __forceinline__ void group_trial_body(const GroupTrialArgs &a, int w,
       }
     }
   }
-  // ---- second stage on the shard's last workgroup (two-level ticket as in trial_kernel)
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned x = xcc_id();
-    const unsigned long long cnt = a.xcd_cnt[x];
-    const unsigned long long t = __hip_atomic_fetch_add(&a.sync->xcd_done[x][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    done_flag = 0;
-    if (t + 1 == (a.launch + 1) * cnt) {
-      const unsigned long long u = __hip_atomic_fetch_add(&a.sync->ticket[2][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      done_flag = (u + 1 == (a.launch + 1) * (unsigned long long)a.nxcd);
-    }
-    if (done_flag) asm volatile("buffer_inv sc1" ::: "memory");
-  }
-  __syncthreads();
-  if (done_flag) {
+  // ---- second stage on the shard's last workgroup
+  if (last_workgroup(a.sync, a.xcd_cnt, a.nxcd, a.launch)) {
     double res[5];
     const unsigned long long errw = threadIdx.x == 0 ? (__hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) |
                                                         __hip_atomic_load(&a.gsync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) : 0ull;
     final_reduce_body<TPB / WAVE>(a.sp, res);
     if (threadIdx.x == 0) {
-      const double err = (double)errw;
-      const double seq = (double)a.seq;
-      unsigned long long ck = RESULT_CHECK_SALT ^ (unsigned long long)__double_as_longlong(err) ^ (unsigned long long)__double_as_longlong(seq);
-#pragma unroll
-      for (int k = 0; k < 5; ++k) ck ^= (unsigned long long)__double_as_longlong(res[k]);
-#pragma unroll
-      for (int k = 0; k < 5; ++k) a.res_host[k] = res[k];
-      a.res_host[5] = __longlong_as_double((long long)ck);
-      a.res_host[6] = err;
-      a.res_host[7] = seq;
+      publish_words(a.res_host, RES_HOST_CAP, RES_HOST_K, a.seq, [&](int q) { return q < 5 ? res[q] : (double)errw; });
       *a.seq_dev = a.seq;
     }
   }

@@ -66,7 +66,7 @@ SmallLpArgs small_lp_stage(pdhg_handle *h, int n, int max_trials, int table_len,
 
 // Wait for launch `seq` of h and take its results into the handle's bookkeeping and the step state (steps_collect).
 int small_lp_collect(pdhg_handle *h, unsigned long long seq, StepIO &io) {
-  double r[13];
+  double r[STEPS_RES_K];
   if (int rc = steps_collect(h, seq, io, r)) return rc;
   h->small_lp_launches += 1;
   h->state_version += 1;

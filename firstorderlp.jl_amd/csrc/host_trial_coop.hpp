@@ -163,7 +163,7 @@ int coop_trial(pdhg_handle *h, const TrialArgs &ta, double out[5]) {
   h->n_graph_trials += 1;
   if (!xbar_only) h->pend_x = false;
   h->pend_y = false;                  // the launch carries the deferred average update
-  rc = wait_result_word(h, out, true);
+  rc = wait_result_word(h, out);
   h->t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - c2).count();
   if (rc) return rc;
   if (h->res_error != 0.0) {
@@ -228,40 +228,12 @@ static int steps_prepare(pdhg_handle *h, int n, const StepIO &io, int *max_trial
   *table_len_out = table_len;
   return 0;
 }
-// wait for a multi-step launch's result words: r[0..12] once sequence number and checksum match (bounded spin, then the stream)
-// Every word is read through the volatile pointer (a plain read in the spin loop may be hoisted).  r14: the step size
-// on entry of a take_step the launch ended inside (0: none); it is under the checksum like the other words.
-static int steps_wait(pdhg_handle *h, unsigned long long seq, double r[13], double *r14) {
-  const volatile unsigned long long *bits = reinterpret_cast<const volatile unsigned long long *>(h->steps_res);
-  const double seq_d = (double)seq;
-  unsigned long long seq_bits;
-  memcpy(&seq_bits, &seq_d, 8);
-  auto ready = [&]() -> bool {
-    if (bits[15] != seq_bits) return false;
-    unsigned long long w[13], ck = RESULT_CHECK_SALT;
-    for (int k = 0; k < 13; ++k) { w[k] = bits[k]; ck ^= w[k] * (2ull * (unsigned long long)k + 1ull); }
-    const unsigned long long w14 = bits[14];
-    ck ^= w14 * 29ull;
-    if (ck != bits[13]) return false;
-    for (int k = 0; k < 13; ++k) memcpy(&r[k], &w[k], 8);
-    memcpy(r14, &w14, 8);
-    return r[12] == seq_d;
-  };
-  for (long spin = 0; spin < 400000000L; ++spin) {
-    if (ready()) return 0;
-    if ((spin & 0xFFFFF) == 0xFFFFF && hipStreamQuery(h->stream) != hipErrorNotReady) break;
-  }
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (ready()) return 0;
-  return fail(998, "multi-step kernel finished without publishing its results");
-}
-
-// Wait for launch `seq` of h and take its result words into the handle's bookkeeping and the step state: steps and
-// trials, the average's counts and weight sums, step size, iterations, KKT passes, steps done, `entry`.  r[13]: the words,
-// for what only one launcher reads.
-static int steps_collect(pdhg_handle *h, unsigned long long seq, StepIO &io, double r[13]) {
-  double r14 = 0.0;
-  if (int rc = steps_wait(h, seq, r, &r14)) return rc;
+// Wait for launch `seq` of h and take its result words (the table is at StepsKernelArgs, trial_kernel.hpp) into the
+// handle's bookkeeping and the step state: steps and trials, the average's counts and weight sums, step size, iterations,
+// KKT passes, steps done, `entry`.  r: the words, for what only one launcher reads.
+static int steps_collect(pdhg_handle *h, unsigned long long seq, StepIO &io, double r[STEPS_RES_K]) {
+  if (int rc = wait_words(h->stream, h->steps_res, STEPS_RES_CAP, STEPS_RES_K, seq, r, 400000000L,
+                          "multi-step kernel finished without publishing its results")) return rc;
   const int64_t steps = (int64_t)r[1], trials = (int64_t)r[2];
   h->n_graph_trials += trials;
   h->sum_x_count += steps; h->sum_y_count += steps;
@@ -272,7 +244,7 @@ static int steps_collect(pdhg_handle *h, unsigned long long seq, StepIO &io, dou
   io.steps_done += steps;
   // (also after a barrier time-out: the launch may have aborted inside a take_step whose earlier trials were rejected,
   //  and the word is written by the same thread as the other result words)
-  io.entry = r14;
+  io.entry = r[12];
   if (r[8] != 0.0) { io.numerical_error = 1; io.steps_done += 1; }   // the failing take_step counts as taken (it is not repeated)
   return 0;
 }
@@ -378,7 +350,7 @@ int coop_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   HIP_TRY(hipGetLastError());
   const auto c2 = std::chrono::steady_clock::now();
   h->t_launch += std::chrono::duration<double>(c2 - c1).count();
-  double r[13];
+  double r[STEPS_RES_K];
   if ((rc = steps_collect(h, a.seq, io, r))) return rc;
   h->t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - c2).count();
   const int64_t trials = (int64_t)r[2];

@@ -34,48 +34,27 @@ hipError_t graph_set_kernel(hipGraphExec_t exec, hipGraphNode_t node, const void
   return graph_set_kernel_lds(exec, node, func, grid, block, 0, args...);
 }
 
-// pinned, host-coherent result word of the one-launch paths: [0..5) sums, [6] error, [7] sequence number
+// pinned, host-coherent result words of the one-launch paths (grid_sync.hpp): [0..5) sums, [5] the barriers' error word
 int ensure_result_word(pdhg_handle *h) {
   if (h->seq_dev) return 0;
   HIP_TRY(hipMalloc((void **)&h->seq_dev, sizeof(unsigned long long)));
   HIP_TRY(hipMemsetAsync(h->seq_dev, 0, sizeof(unsigned long long), nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));   // the null stream does not order against h->stream
-  HIP_TRY(hipHostMalloc((void **)&h->res_host, 8 * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
-  for (int q = 0; q < 8; ++q) h->res_host[q] = 0.0;
+  HIP_TRY(hipHostMalloc((void **)&h->res_host, (RES_HOST_CAP + 2) * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
+  for (int q = 0; q < RES_HOST_CAP + 2; ++q) h->res_host[q] = 0.0;
   return 0;
 }
 
-// wait for launch number seq_expected's results in pinned memory (bounded spin, then the stream).
-// checked: the trial kernel publishes without a system-scope fence -- a read counts only when
-// the sequence number AND the checksum over the eight words match (trial_kernel.hpp).
-int wait_result_word(pdhg_handle *h, double out[5], bool checked = false) {
-  const double want = (double)h->seq_expected;
-  const volatile unsigned long long *bits = reinterpret_cast<const volatile unsigned long long *>(h->res_host);
-  auto ready = [&]() -> bool {
-    if (h->res_host[7] != want) return false;
-    if (!checked) return true;
-    unsigned long long w[8];
-    for (int q = 0; q < 8; ++q) w[q] = bits[q];
-    unsigned long long ck = RESULT_CHECK_SALT ^ w[6] ^ w[7];
-    for (int q = 0; q < 5; ++q) ck ^= w[q];
-    if (ck != w[5]) return false;
-    for (int q = 0; q < 5; ++q) memcpy(&out[q], &w[q], 8);
-    memcpy(&h->res_error, &w[6], 8);
-    return true;
-  };
-  bool seen = false;
-  for (long spin = 0; spin < 40000000L; ++spin) {
-    if (ready()) { seen = true; break; }
-    if ((spin & 0xFFFFF) == 0xFFFFF && hipStreamQuery(h->stream) != hipErrorNotReady) break;
-  }
-  if (!seen) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (!ready()) {
-      h->seq_expected = (unsigned long long)h->res_host[7];   // resynchronise: the next launch can succeed
-      return fail(998, "one-launch trial finished without publishing its results");
-    }
-  }
-  if (!checked) for (int q = 0; q < 5; ++q) out[q] = h->res_host[q];
+// wait for launch number seq_expected's results in pinned memory; the barriers' error word goes to h->res_error
+int wait_result_word(pdhg_handle *h, double out[5]) {
+  double w[RES_HOST_K];
+  const int rc = wait_words(h->stream, h->res_host, RES_HOST_CAP, RES_HOST_K, h->seq_expected, w, 40000000L,
+                            "one-launch trial finished without publishing its results");
+  if (rc == 998)      // resynchronise: the next launch can succeed
+    h->seq_expected = reinterpret_cast<const volatile unsigned long long *>(h->res_host)[RES_HOST_CAP + 1];
+  if (rc) return rc;
+  for (int q = 0; q < 5; ++q) out[q] = w[q];
+  h->res_error = w[5];
   out[4] *= 0.5;
   return 0;
 }

@@ -42,6 +42,7 @@
 #include "spmv_kernels.hpp"
 #include "sj_kernels.hpp"
 #include "vector_kernels.hpp"
+#include "grid_sync.hpp"
 #include "eval_kernels.hpp"
 #include "rescale_kernels.hpp"
 #include "device_layout.hpp"
@@ -195,7 +196,7 @@ struct pdhg_handle {
   int graph_mode = -1;                  // -1 undecided, 0 off, 1 on
   hipStream_t graph_stream = nullptr;   // graphs launch here (== stream)
   unsigned long long *seq_dev = nullptr;   // launch counter, incremented by the final kernel
-  volatile double *res_host = nullptr;     // pinned, coherent: 5 results + [7] = sequence number
+  volatile double *res_host = nullptr;     // pinned, coherent: result words of one trial (grid_sync.hpp)
   unsigned long long seq_expected = 0;
   int coop_fallbacks = 0;                   // trials repeated on the other paths after a barrier time-out
   double timeline_last_out[5] = {0, 0, 0, 0, 0};   // trial_timeline: when the last workgroup left each phase
@@ -588,20 +589,16 @@ int launch_q_interaction(pdhg_handle *h, int *count) {
   return 0;
 }
 
-// second stage of the block partials straight into pinned host memory, then the launch's
-// sequence number: the host polls that word instead of a device-to-host copy + stream
-// synchronisation (the copy alone is a 4 us kernel on this runtime).
+// second stage of the block partials straight into pinned host memory as result words (grid_sync.hpp; no barriers
+// here: the error word is 0).  The sequence number comes from device memory: a graph node's arguments are fixed at capture.
 __global__ __launch_bounds__(FINAL_TPB) void final_reduce_host_kernel(FinalSpec sp, unsigned long long *seq_dev,
                                                                       volatile double *res_host) {
   double res[5];
   final_reduce_body<FINAL_TPB / WAVE>(sp, res);
   if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) res_host[k] = res[k];
     const unsigned long long s = *seq_dev + 1ull;
+    publish_words(res_host, RES_HOST_CAP, RES_HOST_K, s, [&](int q) { return q < 5 ? res[q] : 0.0; });
     *seq_dev = s;
-    __threadfence_system();
-    res_host[7] = (double)s;      // exact up to 2^53 launches
   }
 }
 

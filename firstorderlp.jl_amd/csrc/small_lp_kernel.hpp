@@ -159,20 +159,11 @@ __device__ __forceinline__ void small_lp_steps_body(const SmallLpArgs &a) {
   for (int r = tid; r < m; r += THREADS) { a.y[r] = ys[r]; a.sum_y[r] = sy[r]; }
   __syncthreads();
   if (tid == 0) {
-    __threadfence_system();
-    unsigned long long ck = RESULT_CHECK_SALT;
-    int k = 0;
-#define PDHG_PUB(v) do { const double pv = (v); a.res_host[k] = pv; ck ^= (unsigned long long)__double_as_longlong(pv) * (2ull * k + 1ull); ++k; } while (0)
-    PDHG_PUB(s_st[0]); PDHG_PUB((double)steps); PDHG_PUB((double)trials); PDHG_PUB(0.0); PDHG_PUB(0.0);
-    PDHG_PUB(0.0); PDHG_PUB(s_st[3]); PDHG_PUB(s_st[4]); PDHG_PUB((double)num_err); PDHG_PUB(0.0);
-    PDHG_PUB(0.0); PDHG_PUB(0.0);
-    PDHG_PUB((double)a.seq);
-#undef PDHG_PUB
-    const double e14 = mid ? s_st[1] : 0.0;   // ended inside a take_step (table exhausted): its step size on entry, for the host to finish it
-    ck ^= (unsigned long long)__double_as_longlong(e14) * 29ull;     // (word 14 is under the checksum too: steps_wait)
-    a.res_host[14] = e14;
-    a.res_host[13] = __longlong_as_double((long long)ck);
-    a.res_host[15] = (double)a.seq;
+    __threadfence_system();                // (the vectors written back above, not the result words)
+    // steps_kernel's words (trial_kernel.hpp); [12]: ended inside a take_step (table exhausted), its step size on entry
+    const double r[STEPS_RES_K] = {s_st[0], (double)steps, (double)trials, 0.0, 0.0, 0.0, s_st[3], s_st[4], (double)num_err, 0.0, 0.0, 0.0,
+                                   mid ? s_st[1] : 0.0};
+    publish_words(a.res_host, STEPS_RES_CAP, STEPS_RES_K, a.seq, [&](int q) { return r[q]; });
   }
 }
 

@@ -230,17 +230,8 @@ __global__ __launch_bounds__(TPB) void tr_coop_kernel(TrCoopArgs a) {
       s_out[2] = S.at.v[2] + S.tstar * S.at.v[3];
       s_out[5] = S.tstar; s_out[6] = (double)S.passes;
     }
-    double w[10];
-    for (int q = 0; q < 8; ++q) w[q] = s_out[q];
-    w[8] = (double)__hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    w[9] = (double)epoch;
-    unsigned long long ck = EV_CHECK_SALT ^ a.seq ^ (10ull << 56);
-    for (int q = 0; q < 10; ++q) {
-      a.host_out[q] = w[q];
-      ck ^= (unsigned long long)__double_as_longlong(w[q]) * (2ull * (unsigned long long)q + 1ull);
-    }
-    a.host_out[EV_HOST_CK] = __longlong_as_double((long long)ck);
-    a.host_out[EV_HOST_SEQ] = __longlong_as_double((long long)a.seq);
+    const double err = (double)__hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    publish_words(a.host_out, EV_HOST_SLOTS, 10, a.seq, [&](int q) { return q < 8 ? s_out[q] : (q == 8 ? err : (double)epoch); });
   }
 }
 
@@ -460,14 +451,6 @@ __global__ __launch_bounds__(TPB) void tr_coop_batch_kernel(TrBatchArgs a) {
 #endif
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    const int k = 8 * P + 2;
-    unsigned long long ck = EV_CHECK_SALT ^ a.seq ^ ((unsigned long long)k << 56);
-    int slot = 0;
-    auto put = [&](double v) {
-      a.host_out[slot] = v;
-      ck ^= (unsigned long long)__double_as_longlong(v) * (2ull * (unsigned long long)slot + 1ull);
-      ++slot;
-    };
     for (int p = 0; p < P; ++p) {
       double *o = s_out[p];
       if (s_go[p] == 2) {
@@ -475,12 +458,10 @@ __global__ __launch_bounds__(TPB) void tr_coop_batch_kernel(TrBatchArgs a) {
         o[2] = S[p].at.v[2] + S[p].tstar * S[p].at.v[3];
         o[5] = S[p].tstar; o[6] = (double)S[p].passes;
       }
-      for (int j = 0; j < 8; ++j) put(o[j]);
     }
-    put((double)__hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    put((double)epoch);
-    a.host_out[EV_HOST_CK] = __longlong_as_double((long long)ck);
-    a.host_out[EV_HOST_SEQ] = __longlong_as_double((long long)a.seq);
+    const double err = (double)__hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    publish_words(a.host_out, EV_HOST_SLOTS, 8 * P + 2, a.seq,
+                  [&](int q) { return q < 8 * P ? s_out[q >> 3][q & 7] : (q == 8 * P ? err : (double)epoch); });
   }
 }
 

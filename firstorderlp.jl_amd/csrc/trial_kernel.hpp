@@ -17,47 +17,10 @@
 // them in the same order, so the results are bitwise those of the separate launches
 // (tests/test_gpu_native_take_step.py).
 //
-// Grid barrier (measured: tools/grid_barrier_probe.hip, profiles/r03_grid_barrier_probe.txt).
-// An agent-scope release / acquire on this chip writes back / invalidates the XCD's L2
-// (buffer_wbl2 sc1 / buffer_inv sc1), and when every workgroup issues its own they serialise
-// in the L2: 9.4 us per barrier for 256 workgroups, 19 us for 512, 65 us for 2048, whatever
-// the counter structure (flat, tree, per-XCD).  So the fences are scoped by hand: a
-// workgroup's stores are in its XCD's L2 once `s_waitcnt vmcnt(0)` returns (the L1 is
-// write-through); it then arrives on its XCD's counter; only the LAST arriver of the XCD writes
-// the L2 back, arrives on the global counter, waits for all 8 XCDs, invalidates the L2 and
-// releases its XCD.  3.2 / 3.8 / 5.0 / 7.4 us for 256 / 512 / 1024 / 2048 workgroups.
-// The other workgroups do NOT invalidate their CU's L1 (`buffer_inv sc0` is a no-op on this
-// chip, `sc1` would serialise in the L2 again): not needed for THIS kernel's data flow -- the
-// L1 is clean at kernel start and no address is read before the phase that produces it has
-// completed (x', xbar: written in phase 0, read from phase 1 on; y': written in phase 1, read
-// in phase 2; partial sums: read at the end only), so no CU can hold a stale line.
-// The XCD of a workgroup comes from the hardware register (XCC_ID); how many workgroups of a
-// launch land on each XCD is counted once per handle by a registration launch of the same
-// shape (the dispatcher deals workgroups round-robin; the probe saw exact, repeatable counts).
-// Every spin is bounded: a barrier that cannot complete (workgroups not co-resident because
-// the device is shared) raises the error word instead of hanging, and the host reports it.
+// The grid barrier, the completion ticket and the result words are grid_sync.hpp's.
 #pragma once
 
 namespace {
-
-struct GridSync {                           // device memory, one per handle; one 128-byte line per word
-  unsigned long long global[16];            // XCD leaders arrived (monotonic over launches)
-  unsigned long long xcd_arrive[8][16];
-  unsigned long long xcd_release[8][16];    // last completed barrier epoch of the XCD
-  unsigned long long xcd_count[8][16];      // workgroups of one launch on each XCD
-  unsigned long long xcd_done[8][16];       // workgroups of the XCD that have finished their last phase
-  unsigned long long ticket[3][16];         // [2]: XCDs done (the last workgroup of the last XCD runs the second-stage reduction)
-  unsigned long long error[16];
-  unsigned long long xrelease[16];          // group_kernel.hpp: last cross-shard barrier the shard's last XCD leader has passed
-};
-
-__device__ __forceinline__ unsigned xcc_id() {
-  return __builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20) & 7;   // hwreg(HW_REG_XCC_ID, 0, 4)
-}
-
-__global__ __launch_bounds__(TPB) void xcd_register_kernel(GridSync *s) {
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(&s->xcd_count[xcc_id()][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 #ifndef PDHG_TRIAL_WAVES_PER_EU
 #define PDHG_TRIAL_WAVES_PER_EU 4
@@ -65,79 +28,10 @@ __global__ __launch_bounds__(TPB) void xcd_register_kernel(GridSync *s) {
 #ifndef PDHG_TRIAL_PIPE
 #define PDHG_TRIAL_PIPE true
 #endif
-// the one-wave-per-quantity second stage of LPs (final_reduce_lp): load pairs in flight per lane; used by the single-trial kernel too
+// the one-wave-per-quantity second stage of LPs (final_reduce_lp): load pairs in flight per lane
 #ifndef PDHG_STEPS_LP_BATCH
 #define PDHG_STEPS_LP_BATCH 8      // (L1-SVM, 856 slots per quantity: 22.8-23.2k it/s with 4, 23.1-23.4k with 6, 23.4-23.5k with 8)
 #endif
-#ifndef PDHG_TRIAL_LP_SECOND_STAGE
-#define PDHG_TRIAL_LP_SECOND_STAGE 0   // (the single-trial kernel does not spill in the general form: no difference measured there)
-#endif
-constexpr unsigned long long RESULT_CHECK_SALT = 0x9E3779B97F4A7C15ull;
-constexpr long GRID_SPIN_LIMIT = 4000000L;   // x s_sleep(1): ~0.1 s
-
-// epoch = 1, 2, ... over the life of the handle; nxcd = XCDs that hold workgroups
-// xcd_cnt: workgroups of this launch on each XCD (the census, passed in the kernel arguments: a load of it here
-// would put one more ~1.5 us trip to memory in front of every arrival)
-// err_known: the error word as thread 0 read it a little earlier (the multi-step kernel requests it at the start of the
-// phase, off the critical path; ~0ull: read it here)
-__device__ __forceinline__ void grid_barrier(GridSync *s, unsigned long long epoch, unsigned nxcd, const unsigned *xcd_cnt,
-                                             unsigned long long err_known = ~0ull) {
-  __syncthreads();       // every wave's workgroup-scope release: its stores have reached the XCD's L2
-  if (threadIdx.x == 0 && (err_known != ~0ull ? err_known : __hip_atomic_load(&s->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) {
-    const unsigned x = xcc_id();
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long cnt = xcd_cnt[x];
-    const unsigned long long prev = __hip_atomic_fetch_add(&s->xcd_arrive[x][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    long spins = 0;
-    if (prev + 1 == cnt * epoch) {
-      asm volatile("buffer_wbl2 sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_fetch_add(&s->global[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      while (__hip_atomic_load(&s->global[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned long long)nxcd * epoch) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > GRID_SPIN_LIMIT) { __hip_atomic_store(&s->error[0], 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-      }
-      asm volatile("buffer_inv sc1" ::: "memory");
-      __hip_atomic_store(&s->xcd_release[x][0], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      while (__hip_atomic_load(&s->xcd_release[x][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < epoch) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > GRID_SPIN_LIMIT) { __hip_atomic_store(&s->error[0], 3ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-      }
-    }
-    asm volatile("s_dcache_inv" ::: "memory");
-  }
-  __syncthreads();
-}
-
-// The barrier of a launch whose workgroups all sit on ONE XCD (steps_kernel's XCD-local mode): they share one L2, so
-// there is nothing to write back or invalidate and no second level -- an arrival counter and a release word in that L2.
-// (Loads of data another compute unit rewrote still have to pass the reader's L1: the agent-scope loads the multi-step
-// kernel uses anyway.)  cnt: workgroups of the launch; x: their XCD.
-__device__ __forceinline__ void grid_barrier_local(GridSync *s, unsigned long long epoch, unsigned x, unsigned long long cnt,
-                                                   unsigned long long err_known) {
-  __syncthreads();
-  if (threadIdx.x == 0 && err_known == 0) {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long prev = __hip_atomic_fetch_add(&s->xcd_arrive[x][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev + 1 == cnt * epoch) {
-      __hip_atomic_store(&s->xcd_release[x][0], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      long spins = 0;
-      while (__hip_atomic_load(&s->xcd_release[x][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < epoch) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > GRID_SPIN_LIMIT) { __hip_atomic_store(&s->error[0], 3ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-      }
-    }
-    asm volatile("s_dcache_inv" ::: "memory");
-  }
-  __syncthreads();
-}
-
-// store that is visible device-wide once `s_waitcnt vmcnt(0)` has returned (write-through,
-// no L2 write-back needed): the few words a workgroup hands to a "last one finishes" ticket
-__device__ __forceinline__ void store_agent(double *p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // One fused SpMV of the trial: a stream layout (row blocks + long-row chunks) with its epilogue
 struct TrialProduct {
@@ -279,7 +173,6 @@ template <bool COH>
 __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void trial_kernel(TrialKernelArgs a) {
   __shared__ double prod[BLOCK_NNZ];
   __shared__ double red[6][TPB / WAVE];
-  __shared__ int done_flag;
   const int w = blockIdx.x, nwg = gridDim.x;
 #define PDHG_STAMP(k) do { if (a.trace && threadIdx.x == 0) a.trace[(size_t)w * 8 + (k)] = wall_clock64(); } while (0)
   PDHG_STAMP(0);
@@ -323,47 +216,14 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void trial_kernel(Tri
   }
   PDHG_STAMP(5);
   // ---- second stage: the workgroup that finishes last adds the block partials (K6b)
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    // every block partial of this workgroup went out as a write-through store: once they are
-    // acknowledged, take the ticket
-    // (two levels, like the barrier: atomics on ONE address are served at ~15-25 ns apiece, and a flat ticket over
-    // 500-1000 workgroups that finish together cost 8-12 us here)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned x = xcc_id();
-    const unsigned long long cnt = a.xcd_cnt[x];
-    const unsigned long long t = __hip_atomic_fetch_add(&a.sync->xcd_done[x][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    done_flag = 0;
-    if (t + 1 == (a.launch + 1) * cnt) {
-      const unsigned long long u = __hip_atomic_fetch_add(&a.sync->ticket[2][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      done_flag = (u + 1 == (a.launch + 1) * (unsigned long long)a.nxcd);
-    }
-    if (done_flag) asm volatile("buffer_inv sc1" ::: "memory");
-  }
-  __syncthreads();
-  if (done_flag) {
+  if (last_workgroup(a.sync, a.xcd_cnt, a.nxcd, a.launch)) {
     double res[5];
     // (requested before the partials so that its trip to memory overlaps theirs)
     const unsigned long long errw = threadIdx.x == 0 ? __hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-#if PDHG_TRIAL_LP_SECOND_STAGE
-    if (!a.has_q) final_reduce_lp<PDHG_STEPS_LP_BATCH>(a.sp, res, &red[0][0]);      // (uniform; `red` is free: 6 x 4 doubles)
-    else
-#endif
+    // (the one-wave-per-quantity form, final_reduce_lp, made no difference here: this kernel does not spill in the general one)
     final_reduce_body<TPB / WAVE>(a.sp, res);
     if (threadIdx.x == 0) {
-      // Publish WITHOUT a system-scope fence (an L2 write-back, microseconds): the eight words
-      // may reach host memory in any order, so word 5 carries a checksum over the others and
-      // the host accepts a read only when the sequence number AND the checksum match.
-      const double err = (double)errw;
-      const double seq = (double)a.seq;                  // exact up to 2^53 launches
-      unsigned long long ck = RESULT_CHECK_SALT ^ (unsigned long long)__double_as_longlong(err) ^ (unsigned long long)__double_as_longlong(seq);
-#pragma unroll
-      for (int k = 0; k < 5; ++k) ck ^= (unsigned long long)__double_as_longlong(res[k]);
-#pragma unroll
-      for (int k = 0; k < 5; ++k) a.res_host[k] = res[k];
-      a.res_host[5] = __longlong_as_double((long long)ck);
-      a.res_host[6] = err;
-      a.res_host[7] = seq;
+      publish_words(a.res_host, RES_HOST_CAP, RES_HOST_K, a.seq, [&](int q) { return q < 5 ? res[q] : (double)errw; });
       *a.seq_dev = a.seq;                                // the graph path's device-side counter stays in step
     }
     PDHG_STAMP(6);
@@ -438,15 +298,12 @@ struct StepsKernelArgs {
   unsigned long long local_ticket_base;            // tickets drawn by earlier launches (local_g each)
 };
 
-// result words: [0] step size, [1] steps taken, [2] trials, [3] flip, [4] pending average update, [5] its weight,
+// result words (grid_sync.hpp: STEPS_RES_K values, checksum at [STEPS_RES_CAP], sequence number behind it):
+// [0] step size, [1] steps taken, [2] trials, [3] flip, [4] pending average update, [5] its weight,
 // [6] / [7] weight sums, [8] numerical_error, [9] aborted on a barrier time-out, [10] barrier epoch, [11] the barriers'
-// error word, [12] sequence number; [13] checksum over [0..12]; [14] nonzero: ended inside a take_step (table exhausted) whose step size on entry this is;
-// [15] sequence number again (what the host polls)
-constexpr int STEPS_RES_WORDS = 16;
+// error word, [12] nonzero: ended inside a take_step (table exhausted) whose step size on entry this is
+constexpr int STEPS_RES_WORDS = STEPS_RES_CAP + 2;
 
-#ifndef PDHG_STEPS_PREFETCH
-#define PDHG_STEPS_PREFETCH 1
-#endif
 // LOCAL: the XCD-local mode as its own instantiation (the all-XCD kernel sits at its register limit: as a run-time flag
 // the mode cost it 92 more bytes of scratch per lane)
 template <bool LOCAL>
@@ -498,29 +355,21 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
     // trial's two powers (any workgroup may turn out to be its XCD's leader)
     unsigned long long err_pref = 0;
     double pw_r = 0.0, pw_g = 0.0;
-#if PDHG_STEPS_PREFETCH
     if (threadIdx.x == 0) {
       err_pref = __hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       pw_r = a.pow_red[trials]; pw_g = a.pow_growth[trials];
     }
-#else
-    err_pref = ~0ull;
-#endif
     // ---- phase 0: x' and xbar (+ the deferred sum_x update of the previous accept)
     primal_body<false, true, true>(a.n, x, a.c, aty, nullptr, a.lb, a.ub, tau, 1.0, xn, a.xbar, pend_w,
                                    pend ? a.sum_x : nullptr, w, nwg);
     product_prefetch(a.A, f, w, nwg);
-#if PDHG_STEPS_PREFETCH
     if (threadIdx.x == 0) { s_pow[0] = pw_r; s_pow[1] = pw_g; }
-#endif
     PDHG_STAMP(1);
     if (local) grid_barrier_local(a.sync, ++epoch, a.local_home, (unsigned long long)a.local_g, err_pref);
     else grid_barrier(a.sync, ++epoch, a.nxcd, a.xcd_cnt, err_pref);
     PDHG_STAMP(2);
     // ---- phase 1: y' and sum dy^2 (+ the deferred sum_y update)
-#if PDHG_STEPS_PREFETCH
     if (threadIdx.x == 0) err_pref = __hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     {
       EpiArgs e{};
       e.y = y; e.b = a.b; e.y_next = yn; e.sigma = sigma; e.num_eq = a.num_eq;
@@ -535,9 +384,7 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
     else grid_barrier(a.sync, ++epoch, a.nxcd, a.xcd_cnt, err_pref);
     PDHG_STAMP(4);
     // ---- phase 2: A'y' and the interaction sums
-#if PDHG_STEPS_PREFETCH
     if (threadIdx.x == 0) err_pref = __hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     {
       EpiArgs e{};
       e.x = x; e.x_next = xn; e.aty = aty; e.aty_next = atyn;
@@ -552,9 +399,6 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
     __syncthreads();
     if (threadIdx.x == 0) {
       s_leader = 0;
-#if !PDHG_STEPS_PREFETCH
-      err_pref = __hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
       s_dec[3] = (double)err_pref;
       if (err_pref == 0) {
         const unsigned xcd = xcc_id();
@@ -562,29 +406,21 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         const unsigned long long cnt = local ? (unsigned long long)a.local_g : (unsigned long long)a.xcd_cnt[xcd];
         const unsigned long long prev = __hip_atomic_fetch_add(&a.sync->xcd_arrive[xcd][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        long spins = 0;
         if (prev + 1 == cnt * epoch) {
           // (XCD-local mode: the partials are in this XCD's L2 already -- no write-back, no global phase; the invalidate
-          //  below still clears this compute unit's L1, which may hold the partials of an earlier trial)
-          if (!local) {
-            asm volatile("buffer_wbl2 sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add(&a.sync->global[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          while (!local && __hip_atomic_load(&a.sync->global[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned long long)a.nxcd * epoch) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > GRID_SPIN_LIMIT) { __hip_atomic_store(&a.sync->error[0], 4ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); s_dec[3] = 4.0; break; }
-          }
-          asm volatile("buffer_inv sc1" ::: "memory");
+          //  still clears this compute unit's L1, which may hold the partials of an earlier trial)
+          if (local) asm volatile("buffer_inv sc1" ::: "memory");
+          else if (!xcd_leader_meet(a.sync, epoch, a.nxcd, 4ull)) s_dec[3] = 4.0;
           // a leader whose global wait timed out must not reduce (the partials are incomplete) nor publish a decision
           // with the current epoch: its XCD's slot stays stale and the waiters below leave through the error word
           s_leader = (s_dec[3] == 0.0) ? 1 : 0;
           PDHG_STAMP(7);
         } else {
-          for (;;) {
+          for (long spins = 0;;) {
             const unsigned long long w0 = __hip_atomic_load(slot + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned long long w1 = __hip_atomic_load(slot + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned long long w2 = __hip_atomic_load(slot + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((w0 >> 2) == epoch && (w0 ^ w1 ^ RESULT_CHECK_SALT) == w2) {
+            if ((w0 >> 2) == epoch && (w0 ^ w1 ^ WORDS_CHECK_SALT) == w2) {
               s_dec[0] = (double)(w0 & 1ull); s_dec[1] = (double)((w0 >> 1) & 1ull);
               s_dec[2] = __longlong_as_double((long long)w1);
               break;
@@ -608,17 +444,13 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
       final_reduce_lp<PDHG_STEPS_LP_BATCH>(a.ctl->sp, res, s_res8);
       if (threadIdx.x == 0) {
         res[4] *= 0.5;
-#if PDHG_STEPS_PREFETCH
         const StepRule rule = adaptive_step_rule(res, a.primal_weight, s_st[0], s_pow[0], s_pow[1]);
-#else
-        const StepRule rule = adaptive_step_rule(res, a.primal_weight, s_st[0], a.pow_red[trials], a.pow_growth[trials]);
-#endif
         unsigned long long *slot = reinterpret_cast<unsigned long long *>(a.ctl->slot[xcc_id()]);
         const unsigned long long w0 = (epoch << 2) | (rule.accept ? 1ull : 0ull) | (rule.numerical_error ? 2ull : 0ull);
         const unsigned long long w1 = (unsigned long long)__double_as_longlong(rule.next_step);
         __hip_atomic_store(slot + 0, w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(slot + 1, w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(slot + 2, w0 ^ w1 ^ RESULT_CHECK_SALT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(slot + 2, w0 ^ w1 ^ WORDS_CHECK_SALT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_dec[0] = (double)rule.accept; s_dec[1] = (double)rule.numerical_error; s_dec[2] = rule.next_step;
       }
     }
@@ -647,21 +479,12 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
     __syncthreads();                                         // the state is read, s_dec / s_leader rewritten, in the next trial
   }
   if (w == 0 && threadIdx.x == 0) {
-    // results, checksum, sequence number: the host accepts a read when both match (as for the single-trial kernel)
-    unsigned long long ck = RESULT_CHECK_SALT;
-    int k = 0;
-#define PDHG_PUB(v) do { const double pv = (v); a.res_host[k] = pv; ck ^= (unsigned long long)__double_as_longlong(pv) * (2ull * k + 1ull); ++k; } while (0)
-    PDHG_PUB(s_st[0]); PDHG_PUB((double)steps); PDHG_PUB((double)trials); PDHG_PUB((double)flip); PDHG_PUB((double)pend);
-    PDHG_PUB(s_st[2]); PDHG_PUB(s_st[3]); PDHG_PUB(s_st[4]); PDHG_PUB((double)num_err); PDHG_PUB((double)hw_err);
-    PDHG_PUB((double)epoch);
-    PDHG_PUB((double)__hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    PDHG_PUB((double)a.seq);
-#undef PDHG_PUB
-    const double e14 = mid ? s_st[1] : 0.0;   // ended inside a take_step (table exhausted): its step size on entry, for the host to finish it
-    ck ^= (unsigned long long)__double_as_longlong(e14) * 29ull;     // (word 14 is under the checksum too: steps_wait)
-    a.res_host[14] = e14;
-    a.res_host[13] = __longlong_as_double((long long)ck);
-    a.res_host[15] = (double)a.seq;
+    // (ended inside a take_step, table exhausted: its step size on entry, for the host to finish it)
+    const double r[STEPS_RES_K] = {s_st[0], (double)steps, (double)trials, (double)flip, (double)pend, s_st[2], s_st[3], s_st[4],
+                                   (double)num_err, (double)hw_err, (double)epoch,
+                                   (double)__hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                                   mid ? s_st[1] : 0.0};
+    publish_words(a.res_host, STEPS_RES_CAP, STEPS_RES_K, a.seq, [&](int q) { return r[q]; });
   }
 }
 
