@@ -160,3 +160,83 @@ def assert_products_match_oracle(eng, A, x, y, forced_sweep=False, label=""):
         short = nnz_per <= limit
         assert np.array_equal(got[short], want[short]), f"{label} {name}: rows of <= {limit} entries differ from the oracle"
         assert np.all(np.abs(got - want) <= 1e-13 * scale + 1e-300), f"{label} {name}: beyond 1e-13 * sum |a x|"
+
+
+LADDER_LENS = (0, 1, 7, 8, 9, 15, 16, 17, 127, 128, 129, 255, 256, 257, 384, 1024, 1025, 1152, 2047, 2048, 2049, 2176)
+
+
+def ladder_lp(lens, seed, num_eq=None, blocks="both"):
+    """An LP whose constraint matrix is block_diag(L, L'): row i of L has exactly lens[i] entries (distinct sorted columns,
+    standard-normal values), so A's rows AND A's columns hold every length of `lens`: both products of a trial, A xbar
+    and A'y', see every row length.  Bounds mix -inf / finite below, +inf / finite above and some lb == ub; b and c are
+    random; num_eq defaults to m // 3.  blocks="rows": A = L alone (the lengths are A's rows', its columns stay short);
+    blocks="cols": A = L' alone."""
+    rng = np.random.default_rng(seed)
+    lens = [int(v) for v in lens]
+    rows_l, cols_l = len(lens), max(max(lens), 1)
+    ri = np.repeat(np.arange(rows_l), lens)
+    ci = np.concatenate([np.sort(rng.choice(cols_l, size=k, replace=False)) for k in lens] + [np.zeros(0, dtype=np.int64)])
+    L = sp.csr_matrix((rng.standard_normal(len(ci)), (ri, ci.astype(np.int64))), shape=(rows_l, cols_l))
+    A = {"both": lambda: sp.block_diag([L, L.T], format="csc"), "rows": L.tocsc, "cols": lambda: L.T.tocsc()}[blocks]()
+    A.sort_indices()
+    m, n = A.shape
+    lb = np.where(rng.random(n) < 0.25, -INF, -rng.random(n))
+    ub = np.where(rng.random(n) < 0.25, INF, 1.0 + rng.random(n))
+    fixed = rng.random(n) < 0.1
+    lb[fixed] = ub[fixed] = rng.standard_normal(int(fixed.sum()))
+    b = rng.standard_normal(m)
+    c = rng.standard_normal(n)
+    return linear_programming_problem(lb, ub, c, 0.0, A, b, m // 3 if num_eq is None else int(num_eq))
+
+
+_MATRIX_PARTS = []      # the last matrix assert_trial_matches_oracle saw, and what it derives from it
+
+
+def _matrix_parts(A):
+    """(|A| in CSR, |A|' in CSR, entries per row, entries per column) of A, kept for the next call with the same matrix
+    object."""
+    if not (_MATRIX_PARTS and _MATRIX_PARTS[0] is A):
+        Ar = sp.csr_matrix(A)
+        Aa = abs(Ar)
+        _MATRIX_PARTS[:] = [A, Aa, sp.csr_matrix(Aa.T), np.diff(Ar.indptr), np.diff(sp.csc_matrix(A).indptr)]
+    return _MATRIX_PARTS[1:]
+
+
+def _bits64(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def assert_trial_matches_oracle(got_raw, got_trial, oracle_state, step, weight, A, label=""):
+    """One trial of a device path against the CPU oracle's from the same state.  got_raw: the five sums the device
+    returned; got_trial: its (x', y', A'y'); oracle_state: an OracleState holding the iterate the device trial started
+    from (left holding its own trial vectors); A: the constraint matrix.  The oracle runs trial_step(step, weight, 1.0)
+    with exact sums.  x' bitwise; y' bitwise on rows of at most bitexact_row_limit() entries, longer rows within
+    1e-13 * sigma * sum |a xbar| + 4 eps |y'| (sigma = weight * step); A'y' bitwise on columns of at most the limit whose
+    rows are all short, elsewhere within |A|'|dy'| + 1e-13 |A|'|y'| + 4 eps |A'y'|; the four sums bitwise when every row
+    and column is short, else to rtol 1e-9; out[4] == 0.  Returns (long rows, long columns) of A."""
+    eps = np.finfo(np.float64).eps
+    lim = bitexact_row_limit()
+    Aa, AaT, row_nnz, col_nnz = _matrix_parts(A)
+    oracle_state.exact_sums = True
+    x_prev = oracle_state.x
+    want_raw, wx, wy, wa = oracle_state.trial_step(step, weight, 1.0)
+    gx, gy, ga = got_trial
+    got_raw = np.asarray(got_raw, dtype=np.float64)
+    assert np.array_equal(_bits64(gx), _bits64(wx)), label + ": x'"
+    short_r = row_nnz <= lim
+    assert np.array_equal(_bits64(gy[short_r]), _bits64(wy[short_r])), label + ": y' on short rows"
+    sigma = weight * step
+    xbar = 2.0 * wx - x_prev
+    tol_y = 1e-13 * sigma * (Aa @ np.abs(xbar)) + 4 * eps * np.abs(wy)
+    assert np.all(np.abs(gy - wy) <= tol_y), label + ": y' on long rows beyond 1e-13 * sigma * sum |a xbar|"
+    short_c = col_nnz <= lim
+    clean = short_c & (AaT @ (~short_r).astype(float) == 0)
+    assert np.array_equal(_bits64(ga[clean]), _bits64(wa[clean])), label + ": A'y' on short columns of short rows"
+    tol_a = AaT @ np.abs(gy - wy) + 1e-13 * (AaT @ np.abs(wy)) + 4 * eps * np.abs(wa)
+    assert np.all(np.abs(ga - wa) <= tol_a), label + ": A'y' beyond the relaxed bar"
+    if short_r.all() and short_c.all():
+        assert np.array_equal(_bits64(got_raw[:4]), _bits64(want_raw[:4])), label + ": sums"
+    else:
+        assert np.allclose(got_raw[:4], want_raw[:4], rtol=1e-9, atol=0), label + ": sums"
+    assert got_raw[4] == 0.0, label + ": out[4]"
+    return int((~short_r).sum()), int((~short_c).sum())
