@@ -40,6 +40,7 @@ EXPORTS = [
     "pdhg_create_batch", "pdhg_batch_member", "pdhg_batch_trial_step", "pdhg_batch_accept",
     "pdhg_batch_take_steps_adaptive",
     "pdhg_create_fleet", "pdhg_fleet_add", "pdhg_fleet_take_steps_adaptive", "pdhg_fleet_info",
+    "pdhg_fleet_eval_points", "pdhg_fleet_trust_region_bounds",
 ]
 
 ABI_VERSION = 11
@@ -230,6 +231,10 @@ def lib():
     L.pdhg_fleet_take_steps_adaptive.argtypes = [_vp, _ip, d, d, _dp, _dp, _ip, _dp, _int_p, _ip]
     L.pdhg_fleet_info.restype = i32
     L.pdhg_fleet_info.argtypes = [_vp, _ip]
+    L.pdhg_fleet_eval_points.restype = i32
+    L.pdhg_fleet_eval_points.argtypes = [_vp, _int_p, _dp]
+    L.pdhg_fleet_trust_region_bounds.restype = i32
+    L.pdhg_fleet_trust_region_bounds.argtypes = [_vp, i32, _int_p, _int_p, _dp, _dp, _dp, _int_p, _int_p, _dp]
     L.pdhg_kernel_name.restype = ctypes.c_char_p
     L.pdhg_kernel_name.argtypes = [_vp, i32]
     L.pdhg_layout_info.restype = i32

@@ -156,6 +156,7 @@ int pdhg_set_original_problem(pdhg_handle *h0, const double *constraint_rescalin
   if (rc) return rc;
   if (!constraint_rescaling || !variable_rescaling || !c_o || !lb_o || !ub_o || (h0->m_global > 0 && !b_o))
     return fail(-1, "null input array");
+  fleet_forget(h0);                                            // (a member's stored evaluation was of the problem before)
   const Shards L = shards_of(h0);
   FOR_SHARDS(L, h) {
     auto up = [&](double **dst, const double *src, int64_t len) -> int {
@@ -181,6 +182,10 @@ int pdhg_eval_point(pdhg_handle *h0, int point, double out[24]) {
   int rc = check_handle(h0);
   if (rc) return rc;
   if (!h0->has_original) return fail(-1, "pdhg_set_original_problem has not been called");
+  if (h0->fleet_of) {                                          // a fleet's member: did pdhg_fleet_eval_points leave this result here?
+    if (fleet_stored_eval(h0, point, out)) return 0;
+    fleet_count_miss(h0);
+  }
   const Shards L = shards_of(h0);
   if ((rc = flush_pending(L))) return rc;
   if ((rc = point_products(L, point))) return rc;
@@ -391,6 +396,10 @@ int pdhg_trust_region_bound(pdhg_handle *h0, int point, double primal_weight_nor
   int rc = check_handle(h0);
   if (rc) return rc;
   if (range < 0 || range > 2) return fail(-1, "range must be 0, 1 or 2");
+  if (h0->fleet_of) {                                          // a fleet's member: did pdhg_fleet_trust_region_bounds solve this problem?
+    if (fleet_stored_tr(h0, point, primal_weight_norm, dual_weight_norm, radius, range, approximate, out)) return 0;
+    fleet_count_miss(h0);
+  }
   const Shards L = shards_of(h0);
   if ((rc = flush_pending(L))) return rc;
   const double wp = primal_weight_norm, wd = dual_weight_norm;
@@ -504,6 +513,12 @@ int pdhg_trust_region_bounds(pdhg_handle *h0, int count, const int *points, doub
   if (rc) return rc;
   if (count < 1 || count > TRB_MAX || !points || !radii || !ranges || !out) return fail(-1, "count must be 1..3 and the arrays non-null");
   for (int p = 0; p < count; ++p) if (ranges[p] < 0 || ranges[p] > 2) return fail(-1, "range must be 0, 1 or 2");
+  if (h0->fleet_of) {                                          // every problem solved by the fleet's call already?
+    int have = 0;
+    for (int p = 0; p < count; ++p)
+      have += fleet_stored_tr(h0, points[p], primal_weight_norm, dual_weight_norm, radii[p], ranges[p], approximate, out + 8 * p) ? 1 : 0;
+    if (have == count) return 0;
+  }
   const Shards L = shards_of(h0);
   pdhg_handle *h = L.p[0];
   const char *se = dev_env("PDHG_SMALL_EVAL");

@@ -16,8 +16,12 @@ static void fleet_release(pdhg_handle *h) {
   for (pdhg_handle *m : F->mem) destroy_shard(m);
   for (void *p : {(void *)F->args_dev, (void *)F->pow_dev})
     if (p) (void)hipFree(p);
-  for (void *p : {(void *)F->args_host, (void *)F->pow_host})
+  for (void *p : {(void *)F->args_host, (void *)F->pow_host, (void *)F->chk_res})
     if (p) (void)hipHostFree(p);
+  for (FleetState::Table &T : F->chk_table) {
+    if (T.dev) (void)hipFree(T.dev);
+    if (T.host) (void)hipHostFree(T.host);
+  }
   delete F;
   h->fleet = nullptr;
 }
@@ -123,5 +127,10 @@ int pdhg_fleet_info(pdhg_handle *fleet, int64_t info[8]) {
   info[1] = F.launches;
   info[2] = F.last_carried;
   info[3] = F.last_single;
+  // the checks in shared launches (abi_fleet_checks.hpp)
+  info[4] = F.chk_launches;
+  info[5] = F.chk_carried;
+  info[6] = F.chk_single;
+  info[7] = F.chk_misses;
   return 0;
 }

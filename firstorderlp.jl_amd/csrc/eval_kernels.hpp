@@ -64,9 +64,10 @@ struct WaveSplit<N, 0, M> {       // one quantity left per lane: plain butterfli
 };
 constexpr int pow2_at_least(int n) { return n <= 8 ? 8 : (n <= 16 ? 16 : (n <= 32 ? 32 : 64)); }
 
-// partials[q*stride + blockIdx.x]: q < NS sums, then NM maxes (all maxes are of non-negative values)
+// partials[q*stride + blk]: q < NS sums, then NM maxes (all maxes are of non-negative values).  blk: the block the
+// accumulators belong to -- blockIdx.x, or the virtual block a one-workgroup kernel is working through (fleet_eval_kernel)
 template <int NS, int NM>
-__device__ __forceinline__ void block_reduce_store(const RedAcc<NS, NM> &a, double *partials, int stride) {
+__device__ __forceinline__ void block_reduce_store(const RedAcc<NS, NM> &a, double *partials, int stride, int blk) {
   __shared__ double red[NS + NM][TPB / WAVE];
   const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
 #ifndef PDHG_NO_WAVE_SPLIT
@@ -94,8 +95,12 @@ __device__ __forceinline__ void block_reduce_store(const RedAcc<NS, NM> &a, doub
     double t = 0.0;
 #pragma unroll
     for (int w = 0; w < TPB / WAVE; ++w) t = (q >= NS) ? fmax(t, red[q][w]) : t + red[q][w];
-    partials[q * stride + blockIdx.x] = t;
+    partials[q * stride + blk] = t;
   }
+}
+template <int NS, int NM>
+__device__ __forceinline__ void block_reduce_store(const RedAcc<NS, NM> &a, double *partials, int stride) {
+  block_reduce_store<NS, NM>(a, partials, stride, (int)blockIdx.x);
 }
 
 // Self-test of the check kernels' block reduction (eval_kernels.hpp: WaveSplit): NS quantities per lane, pseudo-random
@@ -137,27 +142,37 @@ __global__ __launch_bounds__(TPB) void wave_sums_selftest_kernel(unsigned long l
 // cost what one does.
 // host_out != nullptr: the results also go straight into pinned host memory as result words (grid_sync.hpp) that
 // the host polls (the trust-region search makes five to eight round trips per call).
+// One quantity's second stage on one wave (every lane calls it; the total ends in lane 63): the ONE statement of the
+// lane-to-partial assignment and the tree, for multi_final_kernel and the one-workgroup fleet_eval_kernel.
+__device__ __forceinline__ double final_quantity(const double *__restrict__ p, int count, bool is_max, int lane) {
+  double v = 0.0;
+  for (int base = lane; base < count; base += 8 * WAVE) {
+    double t[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) t[j] = (base + j * WAVE < count) ? p[base + j * WAVE] : 0.0;   // partials of maxes are >= 0
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v = is_max ? fmax(v, t[j]) : v + t[j];
+  }
+  return is_max ? wave_max_nonneg_dpp(v) : wave_sum_dpp(v);
+}
+// the quantities a workgroup of `waves` waves reduces, wave w taking q = w, w + waves, ...: into out[] and res[] (LDS)
+__device__ __forceinline__ void final_quantities(const double *__restrict__ partials, int stride, int count, int ns, int nm,
+                                                 unsigned max_mask, int waves, double *__restrict__ out, double *res) {
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  const int k = ns + nm;
+  for (int q = wave; q < k; q += waves) {
+    const bool is_max = max_mask ? ((max_mask >> q) & 1u) != 0 : q >= ns;   // max_mask: several kernels' partials side by side (pdhg_eval_point)
+    const double v = final_quantity(partials + (size_t)q * stride, count, is_max, lane);
+    if (lane == WAVE - 1) { out[q] = v; res[q] = v; }
+  }
+}
 __global__ __launch_bounds__(FINAL_TPB) void multi_final_kernel(const double *__restrict__ partials, int stride,
                                                                 int count, int ns, int nm, double *__restrict__ out,
                                                                 double *host_out, unsigned long long seq,
                                                                 unsigned max_mask) {
   __shared__ double res[EV_HOST_SLOTS];
-  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
   const int k = ns + nm;
-  for (int q = wave; q < k; q += FINAL_TPB / WAVE) {
-    const double *p = partials + (size_t)q * stride;
-    const bool is_max = max_mask ? ((max_mask >> q) & 1u) != 0 : q >= ns;   // max_mask: several kernels' partials side by side (pdhg_eval_point)
-    double v = 0.0;
-    for (int base = lane; base < count; base += 8 * WAVE) {
-      double t[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) t[j] = (base + j * WAVE < count) ? p[base + j * WAVE] : 0.0;   // partials of maxes are >= 0
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v = is_max ? fmax(v, t[j]) : v + t[j];
-    }
-    v = is_max ? wave_max_nonneg_dpp(v) : wave_sum_dpp(v);
-    if (lane == WAVE - 1) { out[q] = v; res[q] = v; }
-  }
+  final_quantities(partials, stride, count, ns, nm, max_mask, FINAL_TPB / WAVE, out, res);
   if (host_out) {
     __syncthreads();
     if (threadIdx.x == 0) publish_words(host_out, EV_HOST_SLOTS, k, seq, [&](int q) { return res[q]; });
@@ -169,12 +184,12 @@ __global__ __launch_bounds__(FINAL_TPB) void multi_final_kernel(const double *__
 //   activities A_o x_o = E .* (A_s x_s),  y_o = y_s ./ E.
 // sums: 0 sum viol^2, 1 sum y_o^2, 2 b_o.y_o, 3 sum max(-y_o,0)^2 (ineq rows)
 // maxs: 0 max|viol|, 1 max|viol_homogeneous|, 2 max|y_o|, 3 max max(-y_o,0)
-__global__ __launch_bounds__(TPB) void eval_rows_kernel(int m, int ne, const double *__restrict__ ax_s,
-                                                        const double *__restrict__ py, const double *__restrict__ E,
-                                                        const double *__restrict__ b_o, double *__restrict__ partials,
-                                                        int stride) {
+// (the body as a function of the block: blk of nblk -- a launch's blockIdx.x of gridDim.x, or a virtual block of fleet_eval_kernel)
+__device__ __forceinline__ void eval_rows_body(int blk, int nblk, int m, int ne, const double *__restrict__ ax_s,
+                                               const double *__restrict__ py, const double *__restrict__ E,
+                                               const double *__restrict__ b_o, double *__restrict__ partials, int stride) {
   RedAcc<4, 4> a;
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < m; i += gridDim.x * TPB) {
+  for (int i = blk * TPB + threadIdx.x; i < m; i += nblk * TPB) {
     const double e = E[i];
     const double act = e * ax_s[i];
     const double r = b_o[i] - act;
@@ -188,7 +203,13 @@ __global__ __launch_bounds__(TPB) void eval_rows_kernel(int m, int ne, const dou
     a.m[0] = fmax(a.m[0], fabs(viol)); a.m[1] = fmax(a.m[1], fabs(violh));
     a.m[2] = fmax(a.m[2], fabs(yo)); a.m[3] = fmax(a.m[3], dres);
   }
-  block_reduce_store<4, 4>(a, partials, stride);
+  block_reduce_store<4, 4>(a, partials, stride, blk);
+}
+__global__ __launch_bounds__(TPB) void eval_rows_kernel(int m, int ne, const double *__restrict__ ax_s,
+                                                        const double *__restrict__ py, const double *__restrict__ E,
+                                                        const double *__restrict__ b_o, double *__restrict__ partials,
+                                                        int stride) {
+  eval_rows_body((int)blockIdx.x, (int)gridDim.x, m, ne, ax_s, py, E, b_o, partials, stride);
 }
 
 // Column side (LP): g = c_o - D .* (A_s' y_s), reduced costs, bound violations,
@@ -198,14 +219,13 @@ __global__ __launch_bounds__(TPB) void eval_rows_kernel(int m, int ne, const dou
 // maxs: 0 max|resid|, 1 max|x_o|, 2 max bound viol, 3 max|resid_h|, 4 max|rc_h|, 5 max ray bound viol,
 //       6 max|Q_o x_o|
 // qx_s = Q_s x_s on the scaled point (NULL for an LP); Q_o x_o = D .* (Q_s x_s) because Q_s = D^-1 Q_o D^-1.
-__global__ __launch_bounds__(TPB) void eval_cols_kernel(int n, const double *__restrict__ aty_s,
-                                                        const double *__restrict__ qx_s,
-                                                        const double *__restrict__ px, const double *__restrict__ D,
-                                                        const double *__restrict__ c_o, const double *__restrict__ lb_o,
-                                                        const double *__restrict__ ub_o, double *__restrict__ partials,
-                                                        int stride) {
+__device__ __forceinline__ void eval_cols_body(int blk, int nblk, int n, const double *__restrict__ aty_s,
+                                               const double *__restrict__ qx_s, const double *__restrict__ px,
+                                               const double *__restrict__ D, const double *__restrict__ c_o,
+                                               const double *__restrict__ lb_o, const double *__restrict__ ub_o,
+                                               double *__restrict__ partials, int stride) {
   RedAcc<7, 7> a;
-  for (int j = blockIdx.x * TPB + threadIdx.x; j < n; j += gridDim.x * TPB) {
+  for (int j = blk * TPB + threadIdx.x; j < n; j += nblk * TPB) {
     const double d = D[j];
     const double aty = d * aty_s[j];
     const double xo = px[j] / d;
@@ -230,20 +250,33 @@ __global__ __launch_bounds__(TPB) void eval_cols_kernel(int n, const double *__r
     a.m[0] = fmax(a.m[0], fabs(resid)); a.m[1] = fmax(a.m[1], fabs(xo)); a.m[2] = fmax(a.m[2], fmax(lv, uv));
     a.m[3] = fmax(a.m[3], fabs(residh)); a.m[4] = fmax(a.m[4], fabs(rch)); a.m[5] = fmax(a.m[5], rayv);
   }
-  block_reduce_store<7, 7>(a, partials, stride);
+  block_reduce_store<7, 7>(a, partials, stride, blk);
+}
+__global__ __launch_bounds__(TPB) void eval_cols_kernel(int n, const double *__restrict__ aty_s,
+                                                        const double *__restrict__ qx_s,
+                                                        const double *__restrict__ px, const double *__restrict__ D,
+                                                        const double *__restrict__ c_o, const double *__restrict__ lb_o,
+                                                        const double *__restrict__ ub_o, double *__restrict__ partials,
+                                                        int stride) {
+  eval_cols_body((int)blockIdx.x, (int)gridDim.x, n, aty_s, qx_s, px, D, c_o, lb_o, ub_o, partials, stride);
 }
 
 // sum (a-b)^2 over two vector pairs: distances to the last restart point
 // (saddle_point.jl:445-477, 911-920; weights are uniform per block in PDHG).
+__device__ __forceinline__ void dist2_body(int blk, int nblk, int n, int m, const double *__restrict__ xa,
+                                           const double *__restrict__ xb, const double *__restrict__ ya,
+                                           const double *__restrict__ yb, double *__restrict__ partials, int stride) {
+  RedAcc<2, 0> a;
+  const int tid = blk * TPB + threadIdx.x, st = nblk * TPB;
+  for (int j = tid; j < n; j += st) { const double d = xb ? xa[j] - xb[j] : xa[j]; a.s[0] += d * d; }
+  for (int i = tid; i < m; i += st) { const double d = yb ? ya[i] - yb[i] : ya[i]; a.s[1] += d * d; }
+  block_reduce_store<2, 0>(a, partials, stride, blk);
+}
 __global__ __launch_bounds__(TPB) void dist2_kernel(int n, int m, const double *__restrict__ xa,
                                                     const double *__restrict__ xb, const double *__restrict__ ya,
                                                     const double *__restrict__ yb, double *__restrict__ partials,
                                                     int stride) {
-  RedAcc<2, 0> a;
-  const int tid = blockIdx.x * TPB + threadIdx.x, st = gridDim.x * TPB;
-  for (int j = tid; j < n; j += st) { const double d = xb ? xa[j] - xb[j] : xa[j]; a.s[0] += d * d; }
-  for (int i = tid; i < m; i += st) { const double d = yb ? ya[i] - yb[i] : ya[i]; a.s[1] += d * d; }
-  block_reduce_store<2, 0>(a, partials, stride);
+  dist2_body((int)blockIdx.x, (int)gridDim.x, n, m, xa, xb, ya, yb, partials, stride);
 }
 
 // bound_optimal_objective (trust_region_utils.jl:271-360) set-up on the SCALED
@@ -479,7 +512,9 @@ __device__ __forceinline__ void block_reduce_lds(const RedAcc<NS, NM> &a, double
   }
   __syncthreads();
 }
-__global__ __launch_bounds__(TRS_TPB) void tr_small_kernel(TrSmallArgs a) {
+// The whole launch of one problem: what a workgroup does with one argument block, whoever handed it over -- the solo
+// kernel (the block by value) or fleet_tr_kernel (its entry of a table in device memory); small_lp_steps_body's pattern.
+__device__ __forceinline__ void tr_small_body(const TrSmallArgs &a) {
   extern __shared__ double trs_dyn[];          // thr, w d^2, g d: n + m each
   double *s_thr = trs_dyn, *s_wd2 = trs_dyn + (a.n + a.m), *s_gd = trs_dyn + 2 * (a.n + a.m);
   __shared__ double red[TR_Q * TR_K + 2][TRS_TPB / WAVE];
@@ -589,5 +624,6 @@ __global__ __launch_bounds__(TRS_TPB) void tr_small_kernel(TrSmallArgs a) {
     publish_words(a.host_out, EV_HOST_SLOTS, 8, a.seq, [&](int q) { return s_out[q]; });
   }
 }
+__global__ __launch_bounds__(TRS_TPB) void tr_small_kernel(TrSmallArgs a) { tr_small_body(a); }
 
 }  // namespace

@@ -14,7 +14,76 @@ struct FleetState {
   double *pow_dev = nullptr, *pow_host = nullptr;               // [2 * pow_cap]: k1^-reduction_exponent, then k1^-growth_exponent
   size_t pow_cap = 0;
   int64_t launches = 0, last_carried = 0, last_single = 0;
+  // the checks in shared launches (abi_fleet_checks.hpp): one argument table per kernel (device copy, pinned staging), the
+  // fleet-owned result words of the trust-region items (EV_HOST_SLOTS + 2 doubles per item) and their sequence number
+  struct Table { void *dev = nullptr, *host = nullptr; size_t cap = 0; } chk_table[3];     // point products, evaluation, trust region
+  double *chk_res = nullptr;
+  size_t chk_res_cap = 0;
+  unsigned long long chk_seq = 0;
+  int64_t chk_launches = 0, chk_carried = 0, chk_single = 0, chk_misses = 0;
+  bool chk_serving = false;                                     // inside a fleet call's own per-member calls
 };
+
+// ---- what a fleet's check calls leave in a member (pdhg_handle::fc_eval / fc_tr): pdhg_eval_point and
+// pdhg_trust_region_bound on the member answer from them, without a launch, while the member's state, restart point and
+// matrix are those of the fleet call and the arguments are the same bits.
+inline bool fleet_versions_hold(const pdhg_handle *h, const uint64_t v[3]) {
+  return v[0] == h->state_version && v[1] == h->restart_version && v[2] == h->matrix_version;
+}
+inline uint64_t fleet_bits(double v) { uint64_t b; memcpy(&b, &v, 8); return b; }
+
+bool fleet_stored_eval(pdhg_handle *h, int point, double out[24]) {
+  const pdhg_handle::FleetEvalResult &r = h->fc_eval;
+  if (!r.valid || r.point != point || !fleet_versions_hold(h, r.version)) return false;
+  for (int q = 0; q < 24; ++q) out[q] = r.out[q];
+  // (what pdhg_eval_point leaves for pdhg_distance_to_restart / pdhg_point_sumsq)
+  for (int q = 0; q < 6; ++q) h->chk_vals[q] = r.chk_vals[q];
+  h->chk_state = h->state_version; h->chk_restart = h->restart_version; h->chk_point = point; h->chk_have_avg = r.have_avg;
+  return true;
+}
+void fleet_store_eval(pdhg_handle *h, int point, const double out[24]) {
+  pdhg_handle::FleetEvalResult &r = h->fc_eval;
+  r.valid = h->chk_state == h->state_version && h->chk_restart == h->restart_version && h->chk_point == point;   // (the prefetch ran)
+  r.point = point;
+  r.version[0] = h->state_version; r.version[1] = h->restart_version; r.version[2] = h->matrix_version;
+  for (int q = 0; q < 24; ++q) r.out[q] = out[q];
+  for (int q = 0; q < 6; ++q) r.chk_vals[q] = h->chk_vals[q];
+  r.have_avg = h->chk_have_avg;
+}
+static bool fleet_tr_same(const pdhg_handle *h, const pdhg_handle::FleetTrResult &r, int point, double wp, double wd,
+                          double radius, int range, int approximate) {
+  return r.valid && r.point == point && r.range == range && r.approximate == (approximate ? 1 : 0) && r.wp == fleet_bits(wp) &&
+         r.wd == fleet_bits(wd) && r.radius == fleet_bits(radius) && fleet_versions_hold(h, r.version);
+}
+bool fleet_stored_tr(pdhg_handle *h, int point, double wp, double wd, double radius, int range, int approximate, double out[8]) {
+  for (const pdhg_handle::FleetTrResult &r : h->fc_tr)
+    if (fleet_tr_same(h, r, point, wp, wd, radius, range, approximate)) {
+      for (int q = 0; q < 8; ++q) out[q] = r.out[q];
+      return true;
+    }
+  return false;
+}
+void fleet_store_tr(pdhg_handle *h, int point, double wp, double wd, double radius, int range, int approximate, const double out[8]) {
+  pdhg_handle::FleetTrResult *slot = nullptr;
+  for (pdhg_handle::FleetTrResult &r : h->fc_tr)                      // the same problem again, or a result that went stale
+    if (!slot && (fleet_tr_same(h, r, point, wp, wd, radius, range, approximate) || !r.valid || !fleet_versions_hold(h, r.version))) slot = &r;
+  if (!slot) { slot = &h->fc_tr[h->fc_tr_next]; h->fc_tr_next = (h->fc_tr_next + 1) % pdhg_handle::FC_TR_SLOTS; }
+  slot->valid = true; slot->point = point; slot->range = range; slot->approximate = approximate ? 1 : 0;
+  slot->wp = fleet_bits(wp); slot->wd = fleet_bits(wd); slot->radius = fleet_bits(radius);
+  slot->version[0] = h->state_version; slot->version[1] = h->restart_version; slot->version[2] = h->matrix_version;
+  for (int q = 0; q < 8; ++q) slot->out[q] = out[q];
+}
+// what the three versions do not see: the evaluation also reads the original problem (E, Dv, b_o, c_o, lb_o, ub_o), so
+// pdhg_set_original_problem forgets the stored results
+void fleet_forget(pdhg_handle *h) {
+  h->fc_eval.valid = false;
+  for (pdhg_handle::FleetTrResult &r : h->fc_tr) r.valid = false;
+}
+// a pdhg_eval_point / pdhg_trust_region_bound call on a member that no stored result answered -- the caller's calls only:
+// the calls by which a fleet call itself serves a member it does not carry (chk_serving) are no misses
+void fleet_count_miss(pdhg_handle *h) {
+  if (h->fleet_of && h->fleet_of->fleet && !h->fleet_of->fleet->chk_serving) h->fleet_of->fleet->chk_misses += 1;
+}
 
 // one carried member of a call
 struct FleetCarry {

@@ -49,6 +49,7 @@
 #include "layout.hpp"
 #include "trial_kernel.hpp"
 #include "small_lp_kernel.hpp"
+#include "fleet_check_kernels.hpp"
 #include "tr_coop_kernel.hpp"
 #include "batch_kernels.hpp"
 
@@ -223,6 +224,24 @@ struct pdhg_handle {
   // handle of its own -- matrix included -- on the fleet's device and stream (`fleet_of` = the fleet, which frees it).
   FleetState *fleet = nullptr;
   pdhg_handle *fleet_of = nullptr;
+  // a member: the results the fleet's check calls left here (host_fleet.hpp, abi_fleet_checks.hpp); version = the
+  // member's state_version, restart_version and matrix_version at the call
+  struct FleetEvalResult {
+    bool valid = false, have_avg = false;
+    int point = -1;
+    uint64_t version[3] = {0, 0, 0};
+    double out[24] = {}, chk_vals[6] = {};
+  } fc_eval;
+  struct FleetTrResult {
+    bool valid = false;
+    int point = -1, range = 0, approximate = 0;
+    uint64_t wp = 0, wd = 0, radius = 0;     // the arguments' bits
+    uint64_t version[3] = {0, 0, 0};
+    double out[8] = {};
+  };
+  static constexpr int FC_TR_SLOTS = 8;
+  FleetTrResult fc_tr[FC_TR_SLOTS];
+  int fc_tr_next = 0;
 };
 
 #include "dist.hpp"
@@ -778,4 +797,5 @@ static int batch_scale_members(pdhg_handle *h, const double *dv, const double *e
 #include "abi_measure.hpp"
 #include "abi_batch.hpp"
 #include "abi_fleet.hpp"
+#include "abi_fleet_checks.hpp"
 }  // extern "C"

@@ -32,7 +32,18 @@ def _div(a, b):
         return float(np.float64(a) / np.float64(b))
 
 
+def trust_region_problems(requests, norm):
+    """The trust-region problems behind a ``bounds`` request, in the order the device solves them:
+    [(point, radius, range)] -- one EUCLIDEAN_NORM problem (range 0) per request, or the primal and the dual half
+    (ranges 1 and 2) of a MAX_NORM one."""
+    if norm == EUCLIDEAN_NORM:
+        return [(point, radius, 0) for point, radius in requests]
+    return [(point, radius, rng) for point, radius in requests for rng in (1, 2)]
+
+
 class HostEvaluator:
+    tr_problems = staticmethod(trust_region_problems)
+
     def __init__(self, engine, scaled_problem, qp_cache, ops, original_ops):
         self.engine = engine
         self.scaled_problem = scaled_problem
@@ -184,24 +195,28 @@ class DeviceEvaluator:
         lag = float(op[0]) + const
         return OptimalObjectiveBoundResult(lag, lag + float(op[1]), lag - float(od[2]), None, None)
 
+    tr_problems = staticmethod(trust_region_problems)
+
     def bounds(self, requests, primal_w, dual_w, norm, approximate=False):
         """Several bound_optimal_objective problems at once: requests = [(point, radius), ...] -> one
         OptimalObjectiveBoundResult each, the very numbers ``bound`` returns one by one (pdhg_trust_region_bounds: on
-        medium single handles the searches share one persistent launch)."""
+        medium single handles the searches share one persistent launch).  ``tr_problems`` names the trust-region
+        problems; they go to the engine three EUCLIDEAN_NORM ones, or the two halves of a MAX_NORM one, per call."""
         const = self.objective_constant_scaled
-        if norm == EUCLIDEAN_NORM:
-            out = []
-            for i in range(0, len(requests), 3):
-                chunk = requests[i:i + 3]
-                rows = self.engine.trust_region_bounds([p for p, _ in chunk], primal_w, dual_w, [r for _, r in chunk],
-                                                       [0] * len(chunk), approximate)
-                for o in rows:
-                    lag = float(o[0]) + const
-                    out.append(OptimalObjectiveBoundResult(lag, lag + float(o[1]), lag - float(o[2]), None, None))
-            return out
+        problems = self.tr_problems(requests, norm)
+        per_call = 3 if norm == EUCLIDEAN_NORM else 2
+        rows = []
+        for i in range(0, len(problems), per_call):
+            chunk = problems[i:i + per_call]
+            rows.extend(self.engine.trust_region_bounds([p for p, _, _ in chunk], primal_w, dual_w, [r for _, r, _ in chunk],
+                                                        [g for _, _, g in chunk], approximate))
         out = []
-        for point, radius in requests:           # MAX_NORM: the primal and the dual half of one point share a launch
-            op, od = self.engine.trust_region_bounds([point, point], primal_w, dual_w, [radius, radius], [1, 2], approximate)
+        if norm == EUCLIDEAN_NORM:
+            for o in rows:
+                lag = float(o[0]) + const
+                out.append(OptimalObjectiveBoundResult(lag, lag + float(o[1]), lag - float(o[2]), None, None))
+            return out
+        for op, od in zip(rows[0::2], rows[1::2]):     # MAX_NORM: the primal and the dual half of one point
             lag = float(op[0]) + const
             out.append(OptimalObjectiveBoundResult(lag, lag + float(op[1]), lag - float(od[2]), None, None))
         return out

@@ -6,7 +6,10 @@ small-LP path (csrc/small_lp_kernel.hpp: every vector in one workgroup's LDS) ta
 one workgroup, and ``pdhg_fleet_take_steps_adaptive`` carries one such workgroup per problem in one launch instead of one
 launch per problem on one of 256 compute units.  The members do not run in lockstep: each accepts, rejects, restarts and
 terminates on its own, at the iterations ``optimize`` would.  Both drivers run the same per-problem solve object
-(``primal_dual_hybrid_gradient._Solve``); the evaluations between the steps stay per member and serial.
+(``primal_dual_hybrid_gradient._Solve``).  The checks between the steps go the same way: a fleet with ``eval_points`` and
+``trust_region_bounds`` gets the device requests of every member's check -- the termination evaluation, the
+objective-bound estimates, the restart test -- in shared launches, one workgroup per member or trust-region problem
+(csrc/fleet_check_kernels.hpp), and each member then reads its own result; the restarts themselves stay per member.
 
 ``HipPdhgFleet`` is the device side: one fleet handle that owns K ordinary member handles on one stream (``.members``:
 ``HipPdhgEngine`` views -- every single-LP method works on them, ``rescale`` included: a member's matrix is its own).
@@ -18,7 +21,7 @@ import time as _time
 import numpy as np
 
 from . import _lib
-from .engine import _MemberEngine, _MemberOwner, _d, _i, _pd, _pi
+from .engine import _int_p, _MemberEngine, _MemberOwner, _d, _i, _pd, _pi
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams, _check_inputs,
                                           _constant_step_estimate, _device_scaled_problem, _drive_solves,
                                           _host_scaled_problem, _pack_step_states, _rescales_on_device, _Solve,
@@ -88,6 +91,43 @@ class HipPdhgFleet(_MemberOwner):
         _lib.check(self._L.pdhg_fleet_info(self._h, _pi(info)))
         return dict(zip(["members", "shared_launches", "carried", "single"], info[:4].tolist()))
 
+    # ---- the checks in shared launches (pdhg_fleet_eval_points / pdhg_fleet_trust_region_bounds) ----
+    def eval_points(self, points):
+        """``members[k].eval_point(points[k])`` for every k (-1: member k is left alone, its row stays as it is), the
+        members that suit it in one launch: a (K, 24) array.  Every result is also left in its member: the member's own
+        ``eval_point`` with the same point answers from it until the member's state moves."""
+        pts = np.ascontiguousarray(np.broadcast_to(points, (self.K,)), dtype=np.int32)
+        out = np.zeros((self.K, 24))
+        _lib.check(self._L.pdhg_fleet_eval_points(self._h, pts.ctypes.data_as(_int_p), _pd(out)))
+        return out
+
+    def trust_region_bounds(self, items):
+        """``members[k].trust_region_bound(point, wp, wd, radius, range, approximate)`` for every item
+        ``(k, point, wp, wd, radius, range, approximate)``, the members that suit it in one launch: a (len(items), 8)
+        array.  Left in the members like ``eval_points``' results."""
+        items = list(items)
+        count = len(items)
+        out = np.zeros((count, 8))
+        if count == 0:
+            return out
+        col = list(zip(*items))
+        ints = [np.ascontiguousarray(col[q], dtype=np.int32) for q in (0, 1, 5)]
+        approx = np.ascontiguousarray([int(bool(a)) for a in col[6]], dtype=np.int32)
+        dbl = [_d(col[q]) for q in (2, 3, 4)]
+        _lib.check(self._L.pdhg_fleet_trust_region_bounds(
+            self._h, count, ints[0].ctypes.data_as(_int_p), ints[1].ctypes.data_as(_int_p), _pd(dbl[0]), _pd(dbl[1]),
+            _pd(dbl[2]), ints[2].ctypes.data_as(_int_p), approx.ctypes.data_as(_int_p), _pd(out)))
+        return out
+
+    def check_info(self):
+        """dict(check_launches, carried, single, misses): launches of the check kernels so far; items of the last
+        ``eval_points`` / ``trust_region_bounds`` carried by a shared launch / served per member; ``eval_point`` and
+        ``trust_region_bound`` calls on members so far that no stored fleet result answered (the fleet's own calls
+        for the members it serves one by one are not counted)."""
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(self._L.pdhg_fleet_info(self._h, _pi(info)))
+        return dict(zip(["check_launches", "carried", "single", "misses"], info[4:8].tolist()))
+
 
 def _default_fleet_factory(problems):
     return HipPdhgFleet.from_problems(problems)
@@ -121,13 +161,35 @@ def _step_fleet(fleet, solves, policy, requests):
     return out
 
 
+def _fleet_checks(fleet, solves, pending):
+    """One sweep of a round's checks (``_check_round``): the members' requests -- ``pending`` = [(solve, (method,
+    arguments))] -- as ONE ``fleet.eval_points`` and / or ONE ``fleet.trust_region_bounds``.  The results stay with the
+    members: each member's own evaluator call, which follows, finds them."""
+    slot = {id(mb): k for k, mb in enumerate(solves)}
+    points = np.full(len(solves), -1, dtype=np.int32)
+    items = []
+    for mb, (method, arguments) in pending:
+        k = slot[id(mb)]
+        if method == "iteration_stats":
+            points[k] = arguments[0]
+        elif method == "bounds":
+            requests, primal_w, dual_w, norm, approximate = arguments
+            items.extend((k, point, primal_w, dual_w, radius, rng, approximate)
+                         for point, radius, rng in mb.ev.tr_problems(requests, norm))
+    if (points >= 0).any():
+        fleet.eval_points(points)
+    if items:
+        fleet.trust_region_bounds(items)
+
+
 def optimize_many(params, problems, fleet_factory=None):
     """``optimize(params, problems[k])`` for every k, side by side: a list of ``SaddlePointOutput`` in input order.
 
     Anything ``optimize`` accepts: any mix of shapes, LPs and QPs, every step-size policy, any number of problems (an
     empty list raises ``ValueError`` before any device work).  ``fleet_factory(problems) -> fleet`` builds the device
     side (default ``HipPdhgFleet``): an object with ``.members`` (one engine per problem, in order), ``close()`` and,
-    optionally, ``take_steps_adaptive``; a factory whose ``takes_original_problem`` is true receives the original
+    optionally, ``take_steps_adaptive`` and the pair ``eval_points`` / ``trust_region_bounds`` (the checks in shared
+    launches); a factory whose ``takes_original_problem`` is true receives the original
     problems and every member rescales on the device, any other one receives the host-rescaled problems."""
     problems = list(problems)
     if not problems:
@@ -150,7 +212,10 @@ def optimize_many(params, problems, fleet_factory=None):
         solves = [_Solve(params, p, s, eng, a) for p, s, eng, a in zip(problems, scaled, fleet.members, max_abs)]
         for mb in solves:
             mb.start(_constant_step_estimate(mb) if isinstance(policy, ConstantStepsizeParams) else None)
-        return _drive_solves(solves, lambda requests: _step_fleet(fleet, solves, policy, requests))
+        checks = None
+        if hasattr(fleet, "eval_points") and hasattr(fleet, "trust_region_bounds"):
+            checks = lambda pending: _fleet_checks(fleet, solves, pending)      # noqa: E731
+        return _drive_solves(solves, lambda requests: _step_fleet(fleet, solves, policy, requests), checks)
     finally:
         if fleet is not None and hasattr(fleet, "close"):
             fleet.close()

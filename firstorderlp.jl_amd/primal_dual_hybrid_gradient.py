@@ -21,11 +21,12 @@ from .iteration_stats_utils import print_to_screen_this_iteration
 from .preprocess import rescale_problem, validate
 from .quadratic_programming import (QuadraticProgrammingProblem, ScaledQpProblem,
                                     is_linear_programming_problem)
-from .saddle_point import (RestartParameters, compute_new_primal_weight,
-                           create_last_restart_info, run_restart_scheme,
-                           select_initial_primal_weight,
+from .saddle_point import (RestartParameters, answer_request, compute_new_primal_weight,
+                           create_last_restart_info, drive_requests, run_restart_scheme,
+                           run_restart_scheme_steps, select_initial_primal_weight,
                            unscaled_saddle_point_output,
-                           update_objective_bound_estimates)
+                           update_objective_bound_estimates,
+                           update_objective_bound_estimates_steps)
 from .solve_log import PointType, RestartChoice, TerminationReason
 from .termination import (TerminationCriteria, cached_quadratic_program_info,
                           check_termination_criteria)
@@ -470,6 +471,12 @@ class _Solve:
     def evaluate(self):
         """The top of one iteration of optimize's loop (pdhg.jl:862-1023).  Returns the number of take_steps to
         run before the next evaluation, or 0 once the solve has terminated (``self.output`` set)."""
+        return drive_requests(self.evaluate_steps(), self.ev)
+
+    def evaluate_steps(self):
+        """``evaluate`` as a generator (saddle_point.py, "the check's device requests"): yields at the three places where
+        the check asks the evaluator for device results -- the iteration stats, the bounds behind the objective-bound
+        estimates, the bounds of the restart test -- and returns ``evaluate``'s step count."""
         params, st, ev = self.params, self.state, self.ev
         termination_criteria = params.termination_criteria
         iteration_limit = termination_criteria.iteration_limit
@@ -486,10 +493,10 @@ class _Solve:
             else:
                 avg_point = POINT_AVERAGE
 
-            current_iteration_stats = ev.iteration_stats(
+            current_iteration_stats = yield ("iteration_stats", (
                 avg_point, termination_criteria, params.record_iteration_stats, iteration,
                 _time.time() - self.start_time, st.cumulative_kkt_passes,
-                st.step_size, st.primal_weight, PointType.POINT_TYPE_AVERAGE_ITERATE)
+                st.step_size, st.primal_weight, PointType.POINT_TYPE_AVERAGE_ITERATE))
             method_specific_stats = current_iteration_stats.method_specific_stats
             method_specific_stats["time_spent_doing_basic_algorithm"] = \
                 self.time_spent_doing_basic_algorithm
@@ -508,7 +515,7 @@ class _Solve:
             # trust-region problems behind them (a quarter of a check on medium LPs); the values of kept stats are
             # the reference's (both functions only read the state, so their order does not matter).
             if params.record_iteration_stats or termination_reason is not False:
-                update_objective_bound_estimates(
+                yield from update_objective_bound_estimates_steps(
                     method_specific_stats, ev, avg_point, primal_weight_norm, dual_weight_norm)
                 self.iteration_stats.append(current_iteration_stats)
 
@@ -527,7 +534,7 @@ class _Solve:
                     termination_reason, iteration - 1, self.iteration_stats)
                 return 0
 
-            current_iteration_stats.restart_used = run_restart_scheme(
+            current_iteration_stats.restart_used = yield from run_restart_scheme_steps(
                 ev, self.last_restart_info, iteration - 1, primal_weight_norm,
                 dual_weight_norm, st.primal_weight, params.verbosity,
                 params.restart_params)
@@ -556,16 +563,44 @@ class _Solve:
         self.time_spent_doing_basic_algorithm += seconds
 
 
-def _drive_solves(solves, step):
+def _check_round(active, checks):
+    """One round's evaluations of the active solves with their device requests gathered: every solve's
+    ``evaluate_steps`` is advanced to its next request, ``checks(pending)`` -- ``pending`` = [(solve, request)] in the
+    solves' order -- lets the device answer the requests of all of them at once and leave the results with the
+    members, then each solve's OWN evaluator call runs unchanged (it finds the result) and its return value goes into
+    the generator; until every generator has returned its step count (at most three sweeps: the iteration stats, the
+    objective-bound estimates, the restart test).  Returns {id(solve): steps}."""
+    steps = {}
+    pending = []
+
+    def advance(mb, gen, answer=None, first=False):
+        try:
+            pending.append((mb, gen, next(gen) if first else gen.send(answer)))
+        except StopIteration as stop:
+            steps[id(mb)] = stop.value
+
+    for mb in active:
+        advance(mb, mb.evaluate_steps(), first=True)
+    while pending:
+        sweep, pending = pending, []
+        checks([(mb, request) for mb, _, request in sweep])
+        for mb, gen, request in sweep:
+            advance(mb, gen, answer_request(mb.ev, request))
+    return steps
+
+
+def _drive_solves(solves, step, checks=None):
     """The outer loop of several solves side by side (``batch.optimize_batch``, ``fleet.optimize_many``): at each
     round every active solve evaluates and names its step count, a solve that terminated leaves, and
     ``step(requests)`` -- ``requests`` = [(solve, steps)] in the solves' order -- takes those steps and returns
-    (solve, steps taken, seconds) for each.  Returns the outputs in the solves' order."""
+    (solve, steps taken, seconds) for each.  ``checks``: the round's evaluations go through ``_check_round``.
+    Returns the outputs in the solves' order."""
     active = list(solves)
     while active:
         requests = []
+        round_steps = _check_round(active, checks) if checks is not None else None
         for mb in active:
-            steps = mb.evaluate()
+            steps = round_steps[id(mb)] if round_steps is not None else mb.evaluate()
             if steps > 0:
                 requests.append((mb, steps))
         active = [mb for mb in active if mb.output is None]

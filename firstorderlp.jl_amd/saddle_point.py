@@ -119,8 +119,38 @@ def create_last_restart_info():
     return RestartInfo(None, 1, 0.0, 0.0, 1.0)
 
 
+# ---- the check's device requests, stated once and resumable ------------------------------------------------------
+# The functions of a check that ask the evaluator for device results -- the iteration stats and the trust-region
+# bounds -- exist as GENERATORS (``*_steps``): they yield a request ``(method name, arguments)`` where the plain form
+# calls ``ev.<method>(*arguments)`` and receive its return value.  The plain functions drive their generator against the
+# evaluator at once (``drive_requests``); a driver of many solves (``_drive_solves`` with a fleet) collects the requests
+# of all of them first and lets the device answer them in shared launches.
+
+def answer_request(ev, request):
+    """What the evaluator returns for one request of a ``*_steps`` generator."""
+    method, arguments = request
+    return getattr(ev, method)(*arguments)
+
+
+def drive_requests(steps, ev):
+    """Run a ``*_steps`` generator to its end, every request answered by ``ev`` immediately; returns its result."""
+    try:
+        request = next(steps)
+        while True:
+            request = steps.send(answer_request(ev, request))
+    except StopIteration as stop:
+        return stop.value
+
+
 def compute_localized_duality_gaps(ev, primal_weight_norm, dual_weight_norm,
                                    use_approximate_localized_duality_gap, extra_request=None):
+    """saddle_point.jl:432-496 (``compute_localized_duality_gaps_steps`` answered at once)."""
+    return drive_requests(compute_localized_duality_gaps_steps(
+        ev, primal_weight_norm, dual_weight_norm, use_approximate_localized_duality_gap, extra_request), ev)
+
+
+def compute_localized_duality_gaps_steps(ev, primal_weight_norm, dual_weight_norm,
+                                         use_approximate_localized_duality_gap, extra_request=None):
     """saddle_point.jl:432-496.  ``ev`` is an evaluator (evaluation.py); the norm
     weights are uniform per block in PDHG (define_norms, pdhg.jl:265-277), so
     weighted_norm(v, w)^2 == w * sum(v^2).
@@ -136,8 +166,8 @@ def compute_localized_duality_gaps(ev, primal_weight_norm, dual_weight_norm,
     requests = [(POINT_AVERAGE, distance_traveled_by_average), (POINT_CURRENT, distance_traveled_by_current)]
     if extra_request is not None:
         requests.append(extra_request)
-    got = ev.bounds(requests, primal_weight_norm, dual_weight_norm, EUCLIDEAN_NORM,
-                    use_approximate_localized_duality_gap)
+    got = yield ("bounds", (requests, primal_weight_norm, dual_weight_norm, EUCLIDEAN_NORM,
+                            use_approximate_localized_duality_gap))
     return dict(gap_at_average=got[0],
                 distance_traveled_by_average=distance_traveled_by_average,
                 gap_at_current=got[1],
@@ -223,6 +253,15 @@ def should_do_distance_based_adaptive_restart(candidate_localized_gap,
 def run_restart_scheme(ev, last_restart_info, iterations_completed,
                        primal_weight_norm, dual_weight_norm, primal_weight,
                        verbosity, restart_params):
+    """saddle_point.jl:688-846 (``run_restart_scheme_steps`` answered at once).  Returns a RestartChoice."""
+    return drive_requests(run_restart_scheme_steps(
+        ev, last_restart_info, iterations_completed, primal_weight_norm, dual_weight_norm, primal_weight, verbosity,
+        restart_params), ev)
+
+
+def run_restart_scheme_steps(ev, last_restart_info, iterations_completed,
+                             primal_weight_norm, dual_weight_norm, primal_weight,
+                             verbosity, restart_params):
     """saddle_point.jl:688-846.  ``ev`` (evaluation.py) owns the vector work:
     solution_weighted_avg, the current iterate and the last restart point live
     on the device; a restart to the average is performed there
@@ -253,7 +292,7 @@ def run_restart_scheme(ev, last_restart_info, iterations_completed,
         if not do_restart and restart_params.restart_scheme == RestartScheme.ADAPTIVE_NORMALIZED:
             from .evaluation import POINT_RESTART
             extra = (POINT_RESTART, distance_traveled_in_last_restart_period(last_restart_info, primal_weight))
-        gaps = compute_localized_duality_gaps(
+        gaps = yield from compute_localized_duality_gaps_steps(
             ev, primal_weight_norm, dual_weight_norm,
             restart_params.use_approximate_localized_duality_gap, extra)
         average_distance_sq = gaps["average_distance_sq"]
@@ -334,15 +373,22 @@ def compute_new_primal_weight(last_restart_info, primal_weight,
 
 def update_objective_bound_estimates(method_specific_stats, ev, point,
                                      primal_weight_norm, dual_weight_norm):
+    """saddle_point.jl:1015-1047 (``update_objective_bound_estimates_steps`` answered at once)."""
+    return drive_requests(update_objective_bound_estimates_steps(
+        method_specific_stats, ev, point, primal_weight_norm, dual_weight_norm), ev)
+
+
+def update_objective_bound_estimates_steps(method_specific_stats, ev, point,
+                                           primal_weight_norm, dual_weight_norm):
     """saddle_point.jl:1015-1047 (uniform norm weights)."""
     sx2, sy2 = ev.point_sumsq(point)
     estimated_primal_distance_to_optimality = max(1e-8, math.sqrt(primal_weight_norm * sx2))
     estimated_dual_distance_to_optimality = max(1e-8, math.sqrt(dual_weight_norm * sy2))
     # (through `bounds`: the primal and the dual half of MAX_NORM are two trust-region problems, one launch on the device)
-    gap = ev.bounds([(point, 1.0)],
-                    _div(primal_weight_norm, estimated_primal_distance_to_optimality ** 2),
-                    _div(dual_weight_norm, estimated_dual_distance_to_optimality ** 2),
-                    MAX_NORM, False)[0]
+    gap = (yield ("bounds", ([(point, 1.0)],
+                             _div(primal_weight_norm, estimated_primal_distance_to_optimality ** 2),
+                             _div(dual_weight_norm, estimated_dual_distance_to_optimality ** 2),
+                             MAX_NORM, False)))[0]
     method_specific_stats["lagrangian_value"] = gap.lagrangian_value
     method_specific_stats["estimated_lower_bound"] = gap.lower_bound_value
     method_specific_stats["estimated_upper_bound"] = gap.upper_bound_value

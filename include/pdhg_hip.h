@@ -559,9 +559,46 @@ int pdhg_fleet_take_steps_adaptive(pdhg_handle *fleet, const int64_t *n_steps, d
                                    const double *primal_weight, int64_t *total_number_iterations,
                                    double *cumulative_kkt_passes, int *numerical_error,
                                    int64_t *steps_done);
-/* info[0] members, info[1] shared launches so far, info[2] members carried by the shared launch of the
- * last pdhg_fleet_take_steps_adaptive, info[3] members that call stepped singly, info[4..7] 0. */
+/* info[0] members, info[1] shared STEP launches so far, info[2] members carried by the shared launch of
+ * the last pdhg_fleet_take_steps_adaptive, info[3] members that call stepped singly; the checks in shared
+ * launches (below): info[4] launches of the three check kernels so far, info[5] / info[6] items of the
+ * last pdhg_fleet_eval_points / pdhg_fleet_trust_region_bounds carried by a shared launch / served per
+ * member, info[7] the CALLER's pdhg_eval_point + pdhg_trust_region_bound calls on members so far that
+ * were NOT answered from a result a fleet call had stored (the calls by which a fleet call itself serves
+ * a member it does not carry are not counted: after a mixed list, a miss is a request no fleet call had
+ * taken). */
 int pdhg_fleet_info(pdhg_handle *fleet, int64_t info[8]);
+
+/* ---- a fleet's checks in shared launches, one workgroup per member -------------------------------
+ * Between two batches of steps every member asks for a termination evaluation (pdhg_eval_point) and up
+ * to five trust-region problems (pdhg_trust_region_bound): a dozen small launches and up to four host
+ * round trips per member.  These two calls take the requests of many members at once.  A member rides
+ * in the shared launches (one workgroup per member or problem; at most one launch for the stale A x /
+ * A'y products and one for the work itself) when it is an LP, not profiled, n + m <= 4096 and no row of
+ * A or A' holds more than 256 entries; every other member (a QP, a larger or longer-rowed LP) is served
+ * inside the same call by its own pdhg_eval_point / pdhg_trust_region_bound, member after member.
+ * Every row of `out` is bit for bit what the single-handle call on that member returns.
+ *
+ * Both calls also LEAVE their results in the member: a following pdhg_eval_point(member, point, ...) or
+ * pdhg_trust_region_bound(member, ...) (pdhg_trust_region_bounds too) with the same arguments -- the
+ * doubles compared by their bits -- answers from the stored result without a launch, as long as
+ * nothing has moved the member's iterate or averages, its restart point or its matrix since the fleet
+ * call; pdhg_set_original_problem on the member forgets them too.  A member keeps one evaluation and at
+ * least 6 trust-region results.
+ *
+ * Argument errors return the single call's code with the member / item index in the text, before
+ * anything is launched or changed: a handle that is not a fleet (-1), a point selector out of range
+ * (-1), PDHG_POINT_AVERAGE while the average is empty (-1), a range outside 0..2 (-1), a member without
+ * pdhg_set_original_problem (-1, evaluation only). */
+/* pdhg_eval_point(member k, points[k], out + 24 k) for every member k; points[k] == -1: member k and
+ * its row of out are left alone. */
+int pdhg_fleet_eval_points(pdhg_handle *fleet, const int *points /* [K] */, double *out /* [24 * K] */);
+/* pdhg_trust_region_bound(member[i], points[i], primal_weight_norm[i], dual_weight_norm[i], radii[i],
+ * ranges[i], approximate[i], out + 8 i) for i < count; a member may appear in several items. */
+int pdhg_fleet_trust_region_bounds(pdhg_handle *fleet, int count, const int *member, const int *points,
+                                   const double *primal_weight_norm, const double *dual_weight_norm,
+                                   const double *radii, const int *ranges, const int *approximate,
+                                   double *out /* [8 * count] */);
 
 #ifdef __cplusplus
 }

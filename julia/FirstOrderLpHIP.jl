@@ -1084,4 +1084,30 @@ function fleet_info(fleet::Ptr{Cvoid})
   return info[1], info[2], info[3], info[4]
 end
 
+"(launches of the check kernels so far, items of the last check call carried / served per member, member calls not answered from a stored result) (`pdhg_fleet_info`)."
+function fleet_check_info(fleet::Ptr{Cvoid})
+  info = zeros(Int64, 8)
+  check(ccall((:pdhg_fleet_info, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), fleet, info))
+  return info[5], info[6], info[7], info[8]
+end
+
+"`pdhg_eval_point` of member k at `points[k]` (0-based selectors; -1: the member is left alone), the members that suit it in one launch (`pdhg_fleet_eval_points`): a 24 x K matrix, column k the member's row."
+function fleet_eval_points(fleet::Ptr{Cvoid}, points::Vector{Cint})
+  out = zeros(Float64, 24, length(points))
+  check(ccall((:pdhg_fleet_eval_points, LIB), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Float64}), fleet, points, out))
+  return out
+end
+
+"`pdhg_trust_region_bound` for every item (member index 0-based), the members that suit it in one launch (`pdhg_fleet_trust_region_bounds`): an 8 x count matrix."
+function fleet_trust_region_bounds(fleet::Ptr{Cvoid}, member::Vector{Cint}, points::Vector{Cint},
+                                   primal_weight_norm::Vector{Float64}, dual_weight_norm::Vector{Float64},
+                                   radii::Vector{Float64}, ranges::Vector{Cint}, approximate::Vector{Cint})
+  count = length(member)
+  out = zeros(Float64, 8, count)
+  check(ccall((:pdhg_fleet_trust_region_bounds, LIB), Cint,
+    (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}),
+    fleet, count, member, points, primal_weight_norm, dual_weight_norm, radii, ranges, approximate, out))
+  return out
+end
+
 end # module

@@ -20,8 +20,12 @@ upload, and the K result waits behind the kernel (wall - kernel).
 Whole solves: optimize_many on K members against a Python loop of optimize over (at most --loop-cap of) the same
 members, at solve_qp's defaults (Ruiz-10 + Pock-Chambolle, adaptive steps, adaptive-normalized restarts, an evaluation
 every 40 iterations, tolerance 1e-6), solves per second, and the share of optimize_many's wall time spent inside the
-per-member evaluations (`_Solve.evaluate`: eval_point, the termination test, the trust-region bounds of the restart
-scheme), which stay serial host round trips per member.
+evaluations -- `_check_round` where the fleet takes the checks of all members in shared launches (eval_points,
+trust_region_bounds), `_Solve.evaluate` where they run member by member -- with the fleet's `check_info()` at the end of
+the solve: launches of the three check kernels, and the members' own eval_point / trust_region_bound calls that no
+shared launch had answered (`misses`).  `--solve-reps N` repeats every whole-solve measurement and reports the best
+optimize_many time and the spread; `--check-kernels` adds the kernel durations of the three check kernels at
+--profile-k members from a `rocprofv3 --kernel-trace --stats` run of a child of its own.
 """
 import argparse
 import os
@@ -146,35 +150,95 @@ def solve_params(iteration_limit):
     return PdhgParameters(10, False, 1.0, 1.0, True, 0, False, 40, tc, rp, AdaptiveStepsizeParams(0.3, 0.6))
 
 
-def whole_solves(problems, K, loop_cap, iteration_limit):
-    """(optimize_many solves/s, share of its wall time in the evaluations, loop solves/s, loop members)"""
+def whole_solves(problems, K, loop_cap, iteration_limit, with_loop=True):
+    """(optimize_many solves/s, share of its wall time in the evaluations, loop solves/s, loop members, solves that
+    differ from the loop's, the fleet's check_info() at the end or None)"""
     import firstorderlp_jl_amd.primal_dual_hybrid_gradient as pd
+    import firstorderlp_jl_amd.fleet as fl
     from firstorderlp_jl_amd import optimize_many
     params = solve_params(iteration_limit)
     spent = [0.0]
-    inner = pd._Solve.evaluate
+    depth = [0]
+    inner = {"evaluate": pd._Solve.evaluate, "round": getattr(pd, "_check_round", None)}
 
-    def timed(self):
-        t = time.perf_counter()
-        try:
-            return inner(self)
-        finally:
-            spent[0] += time.perf_counter() - t
-    pd._Solve.evaluate = timed
+    def timed(which):
+        def run(*a):
+            depth[0] += 1
+            t = time.perf_counter()
+            try:
+                return inner[which](*a)
+            finally:
+                depth[0] -= 1
+                if depth[0] == 0:
+                    spent[0] += time.perf_counter() - t
+        return run
+    info = [None]
+
+    def factory(ps):
+        fleet = fl.HipPdhgFleet.from_problems(ps)
+        close = fleet.close
+
+        def closing():
+            if getattr(fleet, "_h", None) and hasattr(fleet, "check_info"):
+                info[0] = fleet.check_info()
+            close()
+        fleet.close = closing
+        return fleet
+    factory.takes_original_problem = True
+    pd._Solve.evaluate = timed("evaluate")
+    if inner["round"]:
+        pd._check_round = timed("round")
     try:
         t0 = time.perf_counter()
-        outs = optimize_many(params, problems[:K])
+        outs = optimize_many(params, problems[:K], fleet_factory=factory)
         many = time.perf_counter() - t0
         in_checks = spent[0]
     finally:
-        pd._Solve.evaluate = inner
+        pd._Solve.evaluate = inner["evaluate"]
+        if inner["round"]:
+            pd._check_round = inner["round"]
+    if not with_loop:
+        return K / many, in_checks / many, None, 0, 0, info[0]
     n_loop = min(K, loop_cap)
     t0 = time.perf_counter()
     solo = [pd.optimize(params, p) for p in problems[:n_loop]]
     loop = time.perf_counter() - t0
     differ = sum(1 for a, b in zip(outs, solo)
                  if a.iteration_count != b.iteration_count or not np.array_equal(a.primal_solution, b.primal_solution))
-    return K / many, in_checks / many, n_loop / loop, n_loop, differ
+    return K / many, in_checks / many, n_loop / loop, n_loop, differ, info[0]
+
+
+def child_solve(shape, K, iteration_limit):
+    """What the profiled child of --check-kernels runs: one optimize_many of K members."""
+    from firstorderlp_jl_amd import optimize_many
+    optimize_many(solve_params(iteration_limit), members(shape, K))
+
+
+def check_kernels_us(shape, K, iteration_limit, timeout=400):
+    """{kernel: (calls, average us)} of the three check kernels in a `rocprofv3 --kernel-trace --stats` run of a child of
+    its own, or a string saying why there is none."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from rocprof_summary import summarize
+    rp = shutil.which("rocprofv3")
+    if not rp:
+        return "rocprofv3 not on PATH"
+    work = tempfile.mkdtemp(prefix="pdhg_fleet_prof_", dir="/tmp")
+    try:
+        cmd = [rp, "--kernel-trace", "--stats", "-d", work, "--", sys.executable, os.path.abspath(__file__), "--child-solve", shape, str(K),
+               str(iteration_limit)]
+        r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), timeout=timeout, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
+        if r.returncode != 0:
+            return f"profiled child failed ({r.returncode}): {r.stderr.decode(errors='replace')[-200:]}"
+        out = {}
+        for k in summarize(work):
+            for name in ("fleet_point_products_kernel", "fleet_eval_kernel", "fleet_tr_kernel", "small_lp_fleet_kernel"):
+                if name in k["name"]:
+                    out[k["name"].split("(")[0]] = (k.get("calls"), k["avg_us"])
+        return out or "no check kernel in the trace"
+    except subprocess.TimeoutExpired:
+        return f"profiled child timed out after {timeout} s"
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
 
 
 def main(argv=None):
@@ -189,17 +253,23 @@ def main(argv=None):
     ap.add_argument("--profile-k", type=int, default=256)
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--solve-reps", type=int, default=1, help="repeat every whole-solve measurement; report the best and the spread")
+    ap.add_argument("--check-kernels", action="store_true", help="kernel durations of the check kernels (a rocprofv3 run of its own)")
     ap.add_argument("--child", nargs=3, default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--child-solve", nargs=3, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     import folp_loader
     pkg = folp_loader.load()
     if args.child:
         child_launch(args.child[0], int(args.child[1]), int(args.child[2]))
         return
-    ks = [int(k) for k in args.ks.split(",")]
+    if args.child_solve:
+        child_solve(args.child_solve[0], int(args.child_solve[1]), int(args.child_solve[2]))
+        return
+    ks = [int(k) for k in args.ks.split(",") if k]
     solve_ks = [int(k) for k in args.solve_ks.split(",") if k]
     lines = [f"# tools/fleet_bench.py --shapes {args.shapes} --ks {args.ks} --steps {args.steps} --reps {args.reps} "
-             f"--solve-ks {args.solve_ks} --loop-cap {args.loop_cap} --iteration-limit {args.iteration_limit}",
+             f"--solve-ks {args.solve_ks} --loop-cap {args.loop_cap} --iteration-limit {args.iteration_limit} --solve-reps {args.solve_reps}",
              "# stepping: one call = `steps` take_steps of each of K members; best of `reps` calls; wall time includes the device",
              f"{'shape':<15} {'K':>5} {'call ms':>9} {'member-it/s':>12} {'solo call ms':>12} {'solo it/s':>10} {'ratio':>7}"]
     print("\n".join(lines), flush=True)
@@ -209,7 +279,7 @@ def main(argv=None):
         lines.append(line)
 
     shapes = args.shapes.split(",")
-    for shape in shapes:
+    for shape in shapes if ks else []:
         problems = members(shape, max(ks))
         solo = solo_call_seconds(problems[0], args.steps, args.reps)
         fleet = pkg.HipPdhgFleet.from_problems(problems, device_id=0)
@@ -240,13 +310,31 @@ def main(argv=None):
     if solve_ks:
         emit(f"# whole solves: solve_qp defaults, tolerance 1e-6, iteration limit {args.iteration_limit}; the loop of optimize runs over "
              f"the first min(K, {args.loop_cap}) members")
-        emit(f"{'shape':<15} {'K':>5} {'many solves/s':>13} {'loop solves/s':>13} {'ratio':>7} {'share in checks':>15} {'loop over':>9}")
+        emit(f"{'shape':<15} {'K':>5} {'many solves/s':>13} {'loop solves/s':>13} {'ratio':>7} {'share in checks':>15} {'loop over':>9}"
+             f"   (many solves/s: best of {args.solve_reps}; check_info() of the fleet at the end of the solve)")
     for shape in shapes if solve_ks else []:
         problems = members(shape, max(solve_ks))
         for K in solve_ks:
-            many, share, loop, n_loop, differ = whole_solves(problems, K, args.loop_cap, args.iteration_limit)
+            many, share, loop, n_loop, differ, info = whole_solves(problems, K, args.loop_cap, args.iteration_limit)
+            rates = [many]
+            for _ in range(args.solve_reps - 1):
+                again = whole_solves(problems, K, args.loop_cap, args.iteration_limit, with_loop=False)
+                rates.append(again[0])
+                if again[0] >= max(rates):
+                    share = again[1]
+            many = max(rates)
             emit(f"{shape:<15} {K:>5} {many:>13.2f} {loop:>13.2f} {many / loop:>7.2f} {share:>15.2f} {n_loop:>9}"
+                 + (f"   # all runs: {' '.join('%.2f' % r for r in rates)}" if len(rates) > 1 else "")
+                 + (f"   # check_info: {info}" if info else "")
                  + (f"   # {differ} solves differ from optimize's" if differ else ""))
+        if args.check_kernels:
+            K = min(args.profile_k, max(solve_ks))
+            got = check_kernels_us(shape, K, args.iteration_limit)
+            if isinstance(got, str):
+                emit(f"# {shape}: check kernels at K = {K}: not measured ({got})")
+            else:
+                emit(f"# {shape}: kernels of one optimize_many at K = {K} (rocprofv3 --kernel-trace --stats, a run of its own), calls x average us: "
+                     + "; ".join(f"{n} {c} x {us:.1f}" for n, (c, us) in sorted(got.items())))
         del problems
     if args.out:
         with open(args.out, "w") as fh:

@@ -34,9 +34,21 @@ if a.breakdown:
                 stage_time[name] = stage_time.get(name, 0.0) + time.perf_counter() - t
                 stage_calls[name] = stage_calls.get(name, 0) + 1
         setattr(mod, name, g)
-    for nm in ("update_objective_bound_estimates", "check_termination_criteria", "run_restart_scheme",
-               "compute_new_primal_weight", "take_steps"):
+    def _timed_steps(mod, name):
+        # a check's generator form (saddle_point.py): optimize answers each request at once, inside this span
+        f = getattr(mod, name + "_steps")
+        def g(*args, **kw):
+            t = time.perf_counter()
+            try:
+                return (yield from f(*args, **kw))
+            finally:
+                stage_time[name] = stage_time.get(name, 0.0) + time.perf_counter() - t
+                stage_calls[name] = stage_calls.get(name, 0) + 1
+        setattr(mod, name + "_steps", g)
+    for nm in ("check_termination_criteria", "compute_new_primal_weight", "take_steps"):
         _timed(_pd, nm)
+    for nm in ("update_objective_bound_estimates", "run_restart_scheme"):
+        _timed_steps(_pd, nm)
     _it = _pd.DeviceEvaluator.iteration_stats
     def _its(self, *args, **kw):
         t = time.perf_counter()
