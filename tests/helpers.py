@@ -206,37 +206,84 @@ def _bits64(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def assert_trial_matches_oracle(got_raw, got_trial, oracle_state, step, weight, A, label=""):
+def assert_trial_matches_oracle(got_raw, got_trial, oracle_state, step, weight, A, label="", theta=1.0, dual_only=False,
+                                Q=None):
     """One trial of a device path against the CPU oracle's from the same state.  got_raw: the five sums the device
     returned; got_trial: its (x', y', A'y'); oracle_state: an OracleState holding the iterate the device trial started
-    from (left holding its own trial vectors); A: the constraint matrix.  The oracle runs trial_step(step, weight, 1.0)
-    with exact sums.  x' bitwise; y' bitwise on rows of at most bitexact_row_limit() entries, longer rows within
+    from (left holding its own trial vectors); A: the constraint matrix.  The oracle runs trial_step(step, weight, theta)
+    with exact sums -- with dual_only (the retries of a Malitsky-Pock step) trial_dual(step, weight, theta) from the x' its
+    own trial_primal left.  x' bitwise; y' bitwise on rows of at most bitexact_row_limit() entries, longer rows within
     1e-13 * sigma * sum |a xbar| + 4 eps |y'| (sigma = weight * step); A'y' bitwise on columns of at most the limit whose
     rows are all short, elsewhere within |A|'|dy'| + 1e-13 |A|'|y'| + 4 eps |A'y'|; the four sums bitwise when every row
-    and column is short, else to rtol 1e-9; out[4] == 0.  Returns (long rows, long columns) of A."""
+    and column is short, else to rtol 1e-9; out[4] == 0.  Returns (long rows, long columns) of A.
+
+    Q: the objective matrix of a QP (the oracle state was built with it).  A row of Q beyond the limit puts the same
+    1e-13 * sum |q x| on that entry of Q x, so x' is bitwise on the other entries and within
+    tau * 1e-13 * sum |q x| + 4 eps |x'| there (tau = step / weight); what x' differs by reaches y' through
+    sigma (1 + theta) |A| |dx'|, which joins its bar, and only rows that touch no such entry stay bitwise.  The fifth sum,
+    0.5 dx'Q dx, is held like the other four: bitwise when every row and column of A and of Q is short, else rtol 1e-9."""
     eps = np.finfo(np.float64).eps
     lim = bitexact_row_limit()
     Aa, AaT, row_nnz, col_nnz = _matrix_parts(A)
     oracle_state.exact_sums = True
     x_prev = oracle_state.x
-    want_raw, wx, wy, wa = oracle_state.trial_step(step, weight, 1.0)
+    if dual_only:
+        want_raw, wx, wy, wa = oracle_state.trial_dual(step, weight, theta)
+    else:
+        want_raw, wx, wy, wa = oracle_state.trial_step(step, weight, theta)
     gx, gy, ga = got_trial
     got_raw = np.asarray(got_raw, dtype=np.float64)
-    assert np.array_equal(_bits64(gx), _bits64(wx)), label + ": x'"
+    q_short = True
+    loose_x = np.zeros(len(wx), dtype=bool)
+    if Q is not None:
+        Qr = sp.csr_matrix(Q)
+        loose_x = np.diff(Qr.indptr) > lim
+        q_short = not loose_x.any() and (np.diff(sp.csc_matrix(Q).indptr) <= lim).all()
+        tol_x = 1e-13 * (step / weight) * (abs(Qr) @ np.abs(x_prev)) + 4 * eps * np.abs(wx)
+        assert np.all(np.abs(gx - wx)[loose_x] <= tol_x[loose_x]), label + ": x' on long rows of Q"
+    assert np.array_equal(_bits64(gx[~loose_x]), _bits64(wx[~loose_x])), label + ": x'"
+    dx = np.abs(gx - wx)
     short_r = row_nnz <= lim
-    assert np.array_equal(_bits64(gy[short_r]), _bits64(wy[short_r])), label + ": y' on short rows"
+    clean_r = short_r & (Aa @ loose_x.astype(float) == 0)
+    assert np.array_equal(_bits64(gy[clean_r]), _bits64(wy[clean_r])), label + ": y' on short rows"
     sigma = weight * step
-    xbar = 2.0 * wx - x_prev
-    tol_y = 1e-13 * sigma * (Aa @ np.abs(xbar)) + 4 * eps * np.abs(wy)
+    xbar = wx + theta * (wx - x_prev)
+    tol_y = 1e-13 * sigma * (Aa @ np.abs(xbar)) + 4 * eps * np.abs(wy) + sigma * (1.0 + abs(theta)) * (Aa @ dx)
     assert np.all(np.abs(gy - wy) <= tol_y), label + ": y' on long rows beyond 1e-13 * sigma * sum |a xbar|"
     short_c = col_nnz <= lim
-    clean = short_c & (AaT @ (~short_r).astype(float) == 0)
+    clean = short_c & (AaT @ (~clean_r).astype(float) == 0)
     assert np.array_equal(_bits64(ga[clean]), _bits64(wa[clean])), label + ": A'y' on short columns of short rows"
     tol_a = AaT @ np.abs(gy - wy) + 1e-13 * (AaT @ np.abs(wy)) + 4 * eps * np.abs(wa)
     assert np.all(np.abs(ga - wa) <= tol_a), label + ": A'y' beyond the relaxed bar"
-    if short_r.all() and short_c.all():
+    bitwise_sums = short_r.all() and short_c.all() and q_short
+    if bitwise_sums:
         assert np.array_equal(_bits64(got_raw[:4]), _bits64(want_raw[:4])), label + ": sums"
     else:
         assert np.allclose(got_raw[:4], want_raw[:4], rtol=1e-9, atol=0), label + ": sums"
-    assert got_raw[4] == 0.0, label + ": out[4]"
+    if Q is None:
+        assert got_raw[4] == 0.0, label + ": out[4]"
+    elif bitwise_sums:
+        assert _bits64(got_raw[4]) == _bits64(want_raw[4]), label + ": 0.5 dx'Q dx"
+    else:
+        assert np.isclose(got_raw[4], want_raw[4], rtol=1e-9, atol=0), label + ": 0.5 dx'Q dx"
     return int((~short_r).sum()), int((~short_c).sum())
+
+
+def rows_with_lens(lens, n, seed, num_eq=None):
+    """An LP with len(lens) rows over n columns: row i holds exactly lens[i] entries, a window of consecutive columns
+    (wrapped) from a random start, standard-normal values.  Bounds mix -inf / finite below, +inf / finite above and some
+    lb == ub; b and c are random; num_eq defaults to m // 3."""
+    rng = np.random.default_rng(seed)
+    lens = np.asarray(lens, dtype=np.int64)
+    m = len(lens)
+    assert lens.max(initial=0) <= n
+    start = rng.integers(0, n, m)
+    ci = np.concatenate([(s + np.arange(k)) % n for s, k in zip(start, lens)] + [np.zeros(0, dtype=np.int64)])
+    A = sp.csr_matrix((rng.standard_normal(len(ci)), ci, np.concatenate([[0], np.cumsum(lens)])), shape=(m, n)).tocsc()
+    A.sort_indices()
+    lb = np.where(rng.random(n) < 0.25, -INF, -rng.random(n))
+    ub = np.where(rng.random(n) < 0.25, INF, 1.0 + rng.random(n))
+    fixed = rng.random(n) < 0.1
+    lb[fixed] = ub[fixed] = rng.standard_normal(int(fixed.sum()))
+    return linear_programming_problem(lb, ub, rng.standard_normal(n), 0.0, A, rng.standard_normal(m),
+                                      m // 3 if num_eq is None else int(num_eq))
