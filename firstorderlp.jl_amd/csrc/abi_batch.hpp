@@ -111,6 +111,8 @@ static int batch_scale_members(pdhg_handle *h, const double *dv, const double *e
   for (pdhg_handle *m : h->bat->mem) {
     hipLaunchKernelGGL(batch_scale_vectors_kernel, dim3(h->ew_grid_nm), dim3(TPB), 0, h->stream, (int)h->n, (int)h->m, dv, ev,
                        m->c, m->lb, m->ub, m->b);
+    HIP_TRY(hipGetLastError());
+    if (int rcb = bounds_rebuild(m)) return rcb;
     m->state_version += 1;
     m->matrix_version += 1;
   }

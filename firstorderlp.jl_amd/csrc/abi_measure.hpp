@@ -389,6 +389,14 @@ int pdhg_layout_describe(pdhg_handle *h, char *buf, int cap) {
       out += (c ? ", " : "") + describe_matrix(h, h->Achunk[c], c + 1 < h->Achunk.size() ? MODE_PLAIN : MODE_DUAL, 0);
     out += "]}";
   }
+  {
+    // how primal_kernel reads lb / ub on a plain handle (vector_kernels.hpp: BoundView)
+    static const char *mode_name[3] = {"dense", "const", "sparse"};
+    char b[256];
+    snprintf(b, sizeof b, ", \"bounds\": {\"lb\": {\"mode\": \"%s\", \"exceptions\": %lld}, \"ub\": {\"mode\": \"%s\", \"exceptions\": %lld}}",
+             mode_name[h->bnd[0].mode], (long long)h->bnd[0].nexc, mode_name[h->bnd[1].mode], (long long)h->bnd[1].nexc);
+    out += b;
+  }
   const char *tv = getenv("PDHG_TUNE");
   out += std::string(", \"row_order\": \"") + (h->relaxed ? "relaxed" : "strict") + "\", \"timing_at_create\": " + ((tv && tv[0] == '0') ? "false" : "true") + "}";
   if (buf && cap > 0) {

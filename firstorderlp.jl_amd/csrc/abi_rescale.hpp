@@ -90,6 +90,7 @@ static int apply_scaling(pdhg_handle *h, RescaleTmp &t) {
   hipLaunchKernelGGL(resc_apply_vectors_kernel, dim3(h->ew_grid_nm), dim3(TPB), 0, h->stream, n, m, t.dv, t.ev,
                      h->c, h->lb, h->ub, h->b, t.cum_d, t.cum_e);
   HIP_TRY(hipGetLastError());
+  if (int rcb = bounds_rebuild(h)) return rcb;             // lb / ub were rescaled in place: 0 and +-inf stay, the rest moves
   if (h->bat) return batch_scale_members(h, t.dv, t.ev);   // the same step on every batch member's vectors
   return 0;
 }

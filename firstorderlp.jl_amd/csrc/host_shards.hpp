@@ -558,7 +558,7 @@ static int alloc_shard_vectors(pdhg_handle *h, const double *c, const double *b,
   if (e != hipSuccess) return fail((int)e, "hipHostMalloc failed");
   e = hipEventCreate(&h->ev0); if (e == hipSuccess) e = hipEventCreate(&h->ev1);
   if (e != hipSuccess) return fail((int)e, "hipEventCreate failed");
-  return 0;
+  return bounds_rebuild(h);      // lb / ub were written: their compact views (pdhg_hip.hip)
 }
 
 int create_shard(pdhg_handle **out, int64_t m, int64_t n, int64_t nnz,
@@ -676,6 +676,7 @@ void destroy_shard(pdhg_handle *h) {
                     h->ev_caty[0], h->ev_caty[1], h->ev_caty[2], h->ev_cqx[0], h->ev_cqx[1], h->ev_cqx[2],
                     h->ev_qx, h->ev_xg};
   for (double *p : bufs) if (p) (void)hipFree(p);
+  bounds_free(h);
   graph_destroy(h->tgraph[0]); graph_destroy(h->tgraph[1]);
   if (h->comm_stream) { (void)hipStreamSynchronize(h->comm_stream); (void)hipStreamDestroy(h->comm_stream); }
   for (hipEvent_t ev : h->ev_part) if (ev) (void)hipEventDestroy(ev);

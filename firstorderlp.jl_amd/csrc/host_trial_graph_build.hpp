@@ -214,7 +214,7 @@ int graph_build(pdhg_handle *h, pdhg_handle::TrialGraph &G, double tau, double t
   // K1+K2
   HIP_TRY(graph_add_kernel(G.graph, &G.n_primal, {}, (const void *)primal_kernel<false, true>, a.primal_grid, dim3(TPB),
                            a.n, (const double *)h->x, (const double *)h->c, (const double *)h->aty, nullq,
-                           (const double *)h->lb, (const double *)h->ub, tau, theta, h->x_next, h->xbar,
+                           bound_view(h, 0), bound_view(h, 1), tau, theta, h->x_next, h->xbar,
                            h->pend_w, h->pend_x ? h->sum_x : (double *)nullptr));
   // K3+K4 on CSR(A), K5+K6 on CSR(A'): the stream kernel (or its column-slab passes, a
   // chain) and the long-row pair are independent branches
@@ -239,6 +239,7 @@ int graph_build(pdhg_handle *h, pdhg_handle::TrialGraph &G, double tau, double t
   HIP_TRY(hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0));
   G.x = h->x; G.y = h->y; G.aty = h->aty;
   G.tau = tau; G.theta = theta; G.sigma = sigma;
+  G.bounds_version = h->bounds_version;
   G.add_x = h->pend_x; G.add_wx = h->pend_w;
   G.add_y = h->pend_y; G.add_wy = h->pend_w;
   return 0;
@@ -257,13 +258,14 @@ int graph_trial(pdhg_handle *h, const TrialArgs &ta, double out[5]) {
   } else {
     const auto c0 = std::chrono::steady_clock::now();
     GraphArgs a(h, sigma);
-    if (G->tau != tau || G->theta != theta || G->add_x != h->pend_x || (h->pend_x && G->add_wx != h->pend_w)) {
+    if (G->tau != tau || G->theta != theta || G->add_x != h->pend_x || (h->pend_x && G->add_wx != h->pend_w) ||
+        G->bounds_version != h->bounds_version) {      // (bounds_rebuild: the node's views point at freed arrays)
       const double *nullq = nullptr;
       HIP_TRY(graph_set_kernel(G->exec, G->n_primal, (const void *)primal_kernel<false, true>, a.primal_grid, dim3(TPB),
                                a.n, (const double *)h->x, (const double *)h->c, (const double *)h->aty, nullq,
-                               (const double *)h->lb, (const double *)h->ub, tau, theta, h->x_next, h->xbar,
+                               bound_view(h, 0), bound_view(h, 1), tau, theta, h->x_next, h->xbar,
                                h->pend_w, h->pend_x ? h->sum_x : (double *)nullptr));
-      G->tau = tau; G->theta = theta;
+      G->tau = tau; G->theta = theta; G->bounds_version = h->bounds_version;
       G->add_x = h->pend_x; G->add_wx = h->pend_w;
     }
     if (G->sigma != sigma || G->add_y != h->pend_y || (h->pend_y && G->add_wy != h->pend_w)) {

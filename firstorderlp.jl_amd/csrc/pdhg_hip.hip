@@ -74,6 +74,17 @@ struct pdhg_handle {
   CsrDev Qt;   // CSR(Q')  for dx'*Q
 
   double *c = nullptr, *b = nullptr, *lb = nullptr, *ub = nullptr;
+  // lb / ub as primal_kernel reads them (vector_kernels.hpp: BoundView): derived from the dense arrays by
+  // bounds_rebuild, which every writer of lb / ub calls.  [0] lb, [1] ub.
+  struct BoundsDev {
+    int mode = BND_DENSE;
+    double def = 0.0;
+    int64_t nexc = 0;
+    unsigned long long *mask = nullptr;
+    int *blk = nullptr;
+    double *exc = nullptr;
+  } bnd[2];
+  uint64_t bounds_version = 0;       // bumped by bounds_rebuild: the trial graphs' primal nodes carry the views
   double *x = nullptr, *x_next = nullptr, *xbar = nullptr;
   double *y = nullptr, *y_next = nullptr;
   double *aty = nullptr, *aty_next = nullptr;  // n+1 each (slot n: exchange scalar)
@@ -178,6 +189,7 @@ struct pdhg_handle {
     hipGraphNode_t n_primal = nullptr, n_dual = nullptr, n_dual_long = nullptr;
     const double *x = nullptr, *y = nullptr, *aty = nullptr;   // the buffers this instance was built for
     double tau = 0.0, theta = 0.0, sigma = 0.0;                // scalars currently baked into the nodes
+    uint64_t bounds_version = 0;                               // the bound views baked into the primal node
     bool add_x = false, add_y = false;                         // deferred K7 baked into the primal / dual nodes
     double add_wx = 0.0, add_wy = 0.0;
   } tgraph[2];
@@ -473,6 +485,79 @@ int launch_spmv_plain_part(pdhg_handle *h, const CsrDev &D, const double *xin, d
   return 0;
 }
 
+// ---- lb / ub as default + exceptions (vector_kernels.hpp: BoundView) ----
+void bounds_free(pdhg_handle *h) {
+  for (pdhg_handle::BoundsDev &B : h->bnd) {
+    for (void *p : {(void *)B.mask, (void *)B.blk, (void *)B.exc}) if (p) (void)hipFree(p);
+    B = pdhg_handle::BoundsDev{};
+  }
+}
+
+// Derive both views again from the dense arrays as h->stream leaves them.  EVERY writer of h->lb / h->ub ends with
+// this call (alloc_shard_vectors, apply_scaling, batch_scale_members): a stale view is the one way the compact
+// forms could give other bits than the dense read.  The default is the most frequent of four bit patterns -- the
+// first entry's, +inf, -inf, +0.0 (the earliest on a tie); no exception: CONST, at most a quarter of the entries:
+// SPARSE, else DENSE.  PDHG_BOUNDS=dense (dev) keeps DENSE, for A/B runs.  Returns with the stream idle.
+int bounds_rebuild(pdhg_handle *h) {
+  HIP_TRY(hipStreamSynchronize(h->stream));      // a queued primal_kernel may still read the old arrays
+  bounds_free(h);
+  h->bounds_version += 1;
+  const int n = (int)h->n;
+  const char *ev = dev_env("PDHG_BOUNDS");
+  if (n <= 0 || (ev && !strcmp(ev, "dense"))) return 0;
+  unsigned *cnt = nullptr;
+  HIP_TRY(hipMalloc((void **)&cnt, sizeof(unsigned) * 8));
+  auto body = [&]() -> int {
+    const double *src[2] = {h->lb, h->ub};
+    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned) * 8, h->stream));
+    for (int k = 0; k < 2; ++k)
+      hipLaunchKernelGGL(bound_census_kernel, dim3(h->ew_grid_n), dim3(TPB), 0, h->stream, n, src[k], cnt + 4 * k);
+    HIP_TRY(hipGetLastError());
+    unsigned hc[8];
+    uint64_t first[2];
+    HIP_TRY(hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, h->stream));
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipMemcpyAsync(&first[k], src[k], sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 2; ++k) {
+      pdhg_handle::BoundsDev &B = h->bnd[k];
+      const uint64_t cand[4] = {first[k], 0x7FF0000000000000ull, 0xFFF0000000000000ull, 0ull};
+      int best = 0;
+      for (int q = 1; q < 4; ++q) if (hc[4 * k + q] > hc[4 * k + best]) best = q;
+      const int64_t nexc = (int64_t)n - (int64_t)hc[4 * k + best];
+      if (4 * nexc > (int64_t)n) continue;                       // DENSE
+      memcpy(&B.def, &cand[best], sizeof(double));
+      B.nexc = nexc;
+      if (nexc == 0) { B.mode = BND_CONST; continue; }
+      const int nblk = (n + BND_BLOCK - 1) / BND_BLOCK;
+      HIP_TRY(hipMalloc((void **)&B.mask, sizeof(unsigned long long) * 2 * (size_t)nblk));
+      HIP_TRY(hipMalloc((void **)&B.blk, sizeof(int) * (size_t)nblk));
+      HIP_TRY(hipMalloc((void **)&B.exc, sizeof(double) * (size_t)nexc));
+      hipLaunchKernelGGL(bound_mask_kernel, dim3(ew_grid((int64_t)nblk * WAVE)), dim3(TPB), 0, h->stream, n, src[k],
+                         (unsigned long long)cand[best], B.mask, B.blk);
+      HIP_TRY(hipGetLastError());
+      int rc = device_exclusive_scan(B.blk, B.blk, nblk, nullptr, h->stream);
+      if (rc) return rc;
+      hipLaunchKernelGGL(bound_pack_kernel, dim3(h->ew_grid_n), dim3(TPB), 0, h->stream, n, src[k],
+                         (const unsigned long long *)B.mask, (const int *)B.blk, B.exc);
+      HIP_TRY(hipGetLastError());
+      B.mode = BND_SPARSE;
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+  };
+  const int rc = body();
+  (void)hipFree(cnt);
+  if (rc) bounds_free(h);                 // never a half-built view: DENSE reads the arrays themselves
+  return rc;
+}
+
+BoundView bound_view(const pdhg_handle *h, int k) {
+  const pdhg_handle::BoundsDev &B = h->bnd[k];
+  BoundView v = bound_dense(k == 0 ? h->lb : h->ub);
+  v.mask = B.mask; v.blk = B.blk; v.exc = B.exc; v.def = B.def; v.mode = B.mode;
+  return v;
+}
+
 // K1+K2 on this shard's column slice (the whole vector for a plain handle).
 // QP: Q is replicated and acts on the full x (kept full on every shard).
 int launch_primal(pdhg_handle *h, double tau, double theta, bool write_xbar) {
@@ -486,9 +571,12 @@ int launch_primal(pdhg_handle *h, double tau, double theta, bool write_xbar) {
   const int n = (int)h->cn;
   const int64_t o = h->clo;
   const int grid = ew_grid((h->cn + 1) / 2);
+  // a plain handle reads the compact bounds; a column slice does not start on a block of the masks: DENSE
+  const bool whole = o == 0 && h->cn == h->n;
+  const BoundView lbv = whole ? bound_view(h, 0) : bound_dense(h->lb + o), ubv = whole ? bound_view(h, 1) : bound_dense(h->ub + o);
 #define PK(HQ, WX)                                                                           \
   hipLaunchKernelGGL((primal_kernel<HQ, WX>), dim3(grid), dim3(TPB), 0, h->stream, n,        \
-                     h->x + o, h->c + o, h->aty + o, h->has_q ? h->qx + o : nullptr, h->lb + o, h->ub + o, tau, theta, \
+                     h->x + o, h->c + o, h->aty + o, h->has_q ? h->qx + o : nullptr, lbv, ubv, tau, theta, \
                      h->x_next + o, h->xbar + o, h->pend_w, h->pend_x ? h->sum_x + o : nullptr)
   if (h->has_q) { if (write_xbar) PK(true, true); else PK(true, false); }
   else          { if (write_xbar) PK(false, true); else PK(false, false); }

@@ -186,8 +186,8 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void trial_kernel(Tri
   }
   // ---- phase 0: x' and xbar (elementwise; any distribution over the workgroups gives the same bits)
   if (a.xbar_only) xbar_body(a.n, a.x, a.x_next, a.theta, a.xbar, w, nwg);
-  else if (a.has_q) primal_body<true, true>(a.n, a.x, a.c, a.aty, a.qx, a.lb, a.ub, a.tau, a.theta, a.x_next, a.xbar, a.avg_w, a.sum_x, w, nwg);
-  else primal_body<false, true, COH>(a.n, a.x, a.c, a.aty, nullptr, a.lb, a.ub, a.tau, a.theta, a.x_next, a.xbar, a.avg_w, a.sum_x, w, nwg);
+  else if (a.has_q) primal_body<true, true>(a.n, a.x, a.c, a.aty, a.qx, bound_dense(a.lb), bound_dense(a.ub), a.tau, a.theta, a.x_next, a.xbar, a.avg_w, a.sum_x, w, nwg);
+  else primal_body<false, true, COH>(a.n, a.x, a.c, a.aty, nullptr, bound_dense(a.lb), bound_dense(a.ub), a.tau, a.theta, a.x_next, a.xbar, a.avg_w, a.sum_x, w, nwg);
   // dx for the interaction term.  After the primal step every thread reads back the x' it wrote itself (same
   // element mapping); on the Malitsky-Pock retries x' is an earlier kernel's output.
   if (a.has_q) diff_pairs_body(a.n, a.x_next, a.x, a.dx, w, nwg);
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
       pw_r = a.pow_red[trials]; pw_g = a.pow_growth[trials];
     }
     // ---- phase 0: x' and xbar (+ the deferred sum_x update of the previous accept)
-    primal_body<false, true, true>(a.n, x, a.c, aty, nullptr, a.lb, a.ub, tau, 1.0, xn, a.xbar, pend_w,
+    primal_body<false, true, true>(a.n, x, a.c, aty, nullptr, bound_dense(a.lb), bound_dense(a.ub), tau, 1.0, xn, a.xbar, pend_w,
                                    pend ? a.sum_x : nullptr, w, nwg);
     product_prefetch(a.A, f, w, nwg);
     if (threadIdx.x == 0) { s_pow[0] = pw_r; s_pow[1] = pw_g; }

@@ -471,6 +471,11 @@ class HipPdhgEngine:
                         out[k + "_sj"] = 1 if sj else 0
                     out[k + "_sj_wide"] = 1 if sj and sj["slices_per_wave"] > 1 else 0
                     out[k + "_sj_hub_rows"] = sj["hub_rows"] if sj else 0
+            # how primal_kernel reads the bounds: "const" (one value, nothing read), "sparse" (a default plus this many
+            # exceptions) or "dense" (the arrays; the exception count is then 0)
+            for k in ("lb", "ub"):
+                out[k + "_mode"] = desc["bounds"][k]["mode"]
+                out[k + "_exceptions"] = desc["bounds"][k]["exceptions"]
         except Exception:      # a diagnostic: never fail layout_info for it
             pass
         for k in ("A", "At"):    # width in bits of an entry's column field

@@ -436,7 +436,10 @@ int pdhg_layout_info(pdhg_handle *h, int64_t info[16]);
  * ("chosen_by": "timing at create" | "static rule"), the sliced jagged copy's window, hub threshold,
  * hub rows and fill.  A handle's dispatch -- hence its timing, never its bits -- can depend on a
  * measurement taken at create (PDHG_TUNE=0 pins the static rules): a bench line or a profile quotes
- * this text to say which variant it ran.  Writes at most cap - 1 characters + NUL into buf (buf may be
+ * this text to say which variant it ran.  "bounds": how primal_kernel reads lb / ub on this handle --
+ * {"lb": {"mode": "const" | "sparse" | "dense", "exceptions": k}, "ub": ...}: one bit pattern and nothing read, a
+ * default plus k exceptions (at most n / 4), or the arrays (k = 0); derived from the arrays whenever they are written
+ * (create, pdhg_rescale), the same bits in every mode.  Writes at most cap - 1 characters + NUL into buf (buf may be
  * NULL); returns the full length of the text, or < 0 on error.  (abi 11) */
 int pdhg_layout_describe(pdhg_handle *h, char *buf, int cap);
 /* Diagnostics: order-sensitive 64-bit checksums of every device array of the two layouts
