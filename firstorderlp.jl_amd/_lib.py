@@ -41,6 +41,8 @@ EXPORTS = [
     "pdhg_batch_take_steps_adaptive",
     "pdhg_create_fleet", "pdhg_fleet_add", "pdhg_fleet_take_steps_adaptive", "pdhg_fleet_info",
     "pdhg_fleet_eval_points", "pdhg_fleet_trust_region_bounds",
+    "pdhg_take_steps_constant", "pdhg_take_steps_malitsky_pock", "pdhg_steps_info",
+    "pdhg_fleet_take_steps_constant", "pdhg_fleet_take_steps_malitsky_pock",
 ]
 
 ABI_VERSION = 11
@@ -152,6 +154,12 @@ def lib():
     L.pdhg_take_step_adaptive.argtypes = [_vp, d, d, _dp, d, _ip, _dp, ctypes.POINTER(i32)]
     L.pdhg_take_steps_adaptive.restype = i32
     L.pdhg_take_steps_adaptive.argtypes = [_vp, i64, d, d, _dp, d, _ip, _dp, ctypes.POINTER(i32), _ip]
+    L.pdhg_take_steps_constant.restype = i32
+    L.pdhg_take_steps_constant.argtypes = [_vp, i64, d, d, _dp, _ip]
+    L.pdhg_take_steps_malitsky_pock.restype = i32
+    L.pdhg_take_steps_malitsky_pock.argtypes = [_vp, i64, d, d, d, _dp, _dp, d, _ip, _dp, ctypes.POINTER(i32), _ip]
+    L.pdhg_steps_info.restype = i32
+    L.pdhg_steps_info.argtypes = [_vp, _ip]
     L.pdhg_add_current_primal_to_average.restype = i32
     L.pdhg_add_current_primal_to_average.argtypes = [_vp, d]
     L.pdhg_get_average_info.restype = i32
@@ -229,6 +237,10 @@ def lib():
     L.pdhg_fleet_add.argtypes = [_vp, i64, i64, i64, _ip, _ip, _dp, i32, _dp, _dp, _dp, _dp, i64, ctypes.POINTER(_vp)]
     L.pdhg_fleet_take_steps_adaptive.restype = i32
     L.pdhg_fleet_take_steps_adaptive.argtypes = [_vp, _ip, d, d, _dp, _dp, _ip, _dp, _int_p, _ip]
+    L.pdhg_fleet_take_steps_constant.restype = i32
+    L.pdhg_fleet_take_steps_constant.argtypes = [_vp, _ip, _dp, _dp, _dp, _ip]
+    L.pdhg_fleet_take_steps_malitsky_pock.restype = i32
+    L.pdhg_fleet_take_steps_malitsky_pock.argtypes = [_vp, _ip, d, d, d, _dp, _dp, _dp, _ip, _dp, _int_p, _ip]
     L.pdhg_fleet_info.restype = i32
     L.pdhg_fleet_info.argtypes = [_vp, _ip]
     L.pdhg_fleet_eval_points.restype = i32

@@ -1,5 +1,6 @@
 // abi_fleet.hpp -- part of the single translation unit pdhg_hip.hip (included there, inside its extern "C" block).
-// C ABI: a fleet of independent small LPs stepped by one launch (host_fleet.hpp, small_lp_fleet_kernel).
+// C ABI: a fleet of independent small LPs stepped by one launch (host_fleet.hpp, small_lp_fleet_kernel and its two
+// siblings for the constant and the Malitsky-Pock policy).
 //
 // A fleet is a pdhg_handle that runs no iterations of its own: it owns one stream, the argument table and the shared
 // tables of powers of the many-LP launch, and its members.  A member is what pdhg_create makes -- its own matrix, its
@@ -116,6 +117,95 @@ int pdhg_fleet_take_steps_adaptive(pdhg_handle *fleet, const int64_t *n_steps, d
       if ((rc = take_steps_adaptive_resume(F.mem[(size_t)c.k], n_steps[c.k], *c.io))) return rc;
     }
   return 0;
+}
+
+/* pdhg_take_steps_constant / pdhg_take_steps_malitsky_pock (member k, n_steps[k], ...) for every k, as
+ * pdhg_fleet_take_steps_adaptive does for its policy: the members that are small_lp_eligible and ask for at least 2
+ * steps -- under Malitsky-Pock: whose primal average is not empty -- go into the shared launch (fleet_policy_launch);
+ * whatever it left of them and every other member is stepped by the per-handle loop (take_steps_policy_resume). */
+static int fleet_take_steps_policy(pdhg_handle *fleet, const int64_t *n_steps, std::vector<PolicyIO> &io, const std::vector<int> &member) {
+  FleetState &F = *fleet->fleet;
+  std::vector<FleetCarry> carry, single;
+  for (size_t i = 0; i < io.size(); ++i) {
+    const int k = member[i];
+    pdhg_handle *h = F.mem[(size_t)k];
+    FleetCarry c;
+    c.k = k;
+    c.pio = &io[i];
+    c.n = small_policy_launch_steps(io[i].policy, n_steps[k]);
+    const bool quirk = io[i].policy == SMALL_MALITSKY_POCK && h->sum_x_count == 0;
+    (n_steps[k] >= 2 && !quirk && check_handle(h) == 0 && small_lp_eligible(h) ? carry : single).push_back(c);
+  }
+  F.last_carried = (int64_t)carry.size();
+  F.last_single = (int64_t)single.size();
+  int rc = fleet_policy_launch(fleet, carry);
+  if (rc) return rc;
+  for (const std::vector<FleetCarry> *part : {&carry, &single})
+    for (const FleetCarry &c : *part)
+      if ((rc = take_steps_policy_resume(F.mem[(size_t)c.k], n_steps[c.k], *c.pio))) return rc;
+  return 0;
+}
+
+int pdhg_fleet_take_steps_constant(pdhg_handle *fleet, const int64_t *n_steps, const double *step_size,
+                                   const double *primal_weight, double *cumulative_kkt_passes, int64_t *steps_done) {
+  RoctxRange roctx_range("pdhg_fleet_take_steps_constant");
+  if (!fleet) return fail(-1, "null handle");
+  if (!fleet_of(fleet)) return fail(-1, "pdhg_fleet_take_steps_constant: not a fleet handle");
+  if (!n_steps || !step_size || !primal_weight || !cumulative_kkt_passes || !steps_done) return fail(-1, "null argument");
+  FleetState &F = *fleet->fleet;
+  const int K = (int)F.mem.size();
+  for (int k = 0; k < K; ++k)
+    if (n_steps[k] < 0) return fail(-2, "pdhg_fleet_take_steps_constant: n_steps[" + std::to_string(k) + "] < 0");
+  // (what the constant policy neither reads nor writes, per member: PolicyIO binds references)
+  std::vector<double> step((size_t)K), ratio((size_t)K, 0.0);
+  std::vector<int64_t> iterations((size_t)K, 0);
+  std::vector<int> numerical_error((size_t)K, 0);
+  std::vector<PolicyIO> io;
+  std::vector<int> member;
+  io.reserve((size_t)K);
+  for (int k = 0; k < K; ++k) {
+    if (n_steps[k] == 0) continue;              // neither read nor written
+    steps_done[k] = 0;
+    step[(size_t)k] = step_size[k];
+    io.push_back(PolicyIO{SMALL_CONSTANT, step[(size_t)k], ratio[(size_t)k], iterations[(size_t)k], cumulative_kkt_passes[k],
+                          numerical_error[(size_t)k], steps_done[k], primal_weight[k], 0.0, 0.0, 0.0});
+    member.push_back(k);
+  }
+  return fleet_take_steps_policy(fleet, n_steps, io, member);
+}
+
+int pdhg_fleet_take_steps_malitsky_pock(pdhg_handle *fleet, const int64_t *n_steps, double downscaling_factor,
+                                        double breaking_factor, double interpolation_coefficient, double *step_size,
+                                        double *ratio_step_sizes, const double *primal_weight,
+                                        int64_t *total_number_iterations, double *cumulative_kkt_passes,
+                                        int *numerical_error, int64_t *steps_done) {
+  RoctxRange roctx_range("pdhg_fleet_take_steps_malitsky_pock");
+  if (!fleet) return fail(-1, "null handle");
+  if (!fleet_of(fleet)) return fail(-1, "pdhg_fleet_take_steps_malitsky_pock: not a fleet handle");
+  if (!n_steps || !step_size || !ratio_step_sizes || !primal_weight || !total_number_iterations || !cumulative_kkt_passes ||
+      !numerical_error || !steps_done)
+    return fail(-1, "null argument");
+  FleetState &F = *fleet->fleet;
+  const int K = (int)F.mem.size();
+  for (int k = 0; k < K; ++k) {
+    if (n_steps[k] < 0) return fail(-2, "pdhg_fleet_take_steps_malitsky_pock: n_steps[" + std::to_string(k) + "] < 0");
+    if (n_steps[k] > 0 && F.mem[(size_t)k]->has_q)
+      return fail(-2, "pdhg_fleet_take_steps_malitsky_pock: member " + std::to_string(k) +
+                          ": Malitsky and Pock linesearch is only supported for linear programming problems");
+  }
+  std::vector<PolicyIO> io;
+  std::vector<int> member;
+  io.reserve((size_t)K);
+  for (int k = 0; k < K; ++k) {
+    if (n_steps[k] == 0) continue;              // neither read nor written
+    numerical_error[k] = 0;
+    steps_done[k] = 0;
+    io.push_back(PolicyIO{SMALL_MALITSKY_POCK, step_size[k], ratio_step_sizes[k], total_number_iterations[k],
+                          cumulative_kkt_passes[k], numerical_error[k], steps_done[k], primal_weight[k], downscaling_factor,
+                          breaking_factor, interpolation_coefficient});
+    member.push_back(k);
+  }
+  return fleet_take_steps_policy(fleet, n_steps, io, member);
 }
 
 int pdhg_fleet_info(pdhg_handle *fleet, int64_t info[8]) {

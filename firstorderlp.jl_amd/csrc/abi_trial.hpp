@@ -564,6 +564,112 @@ int pdhg_take_steps_adaptive(pdhg_handle *h, int64_t n_steps, double reduction_e
   return take_steps_adaptive_resume(h, n_steps, io);
 }
 
+/* take_step(::ConstantStepsizeParams, ...) -- pdhg.jl:737-767 -- and take_step(::MalitskyPockStepsizeParameters, ...)
+ * -- pdhg.jl:555-647 -- with their host part in C: the statements of take_step_constant / take_step_malitsky_pock of
+ * primal_dual_hybrid_gradient.py, one by one, around the same entry points (bitwise equal results;
+ * tests/test_gpu_step_policies.py).  Every kind of handle takes them. */
+int pdhg_add_current_primal_to_average(pdhg_handle *h0, double weight);
+static int take_step_constant_one(pdhg_handle *h, PolicyIO &io) {
+  double raw[5];
+  if (int rc = pdhg_trial_step(h, io.step_size, io.primal_weight, 1.0, raw)) return rc;
+  io.kkt_passes += 1;
+  return pdhg_accept(h, io.step_size);
+}
+static int take_step_malitsky_pock_one(pdhg_handle *h, PolicyIO &io) {
+  const double step_on_entry = io.step_size;
+  double ratio = io.ratio;
+  int rc = pdhg_trial_primal(h, step_on_entry, io.primal_weight);
+  if (rc) return rc;
+  io.kkt_passes += 0.5;
+  double step = malitsky_pock_first_step(step_on_entry, ratio, io.interpolation_coefficient);
+  bool done = false;
+  for (int it = 0; !done && it < MALITSKY_POCK_MAX_TRIALS; ++it) {
+    io.iterations += 1;
+    ratio = step / step_on_entry;
+    double raw[5];
+    if ((rc = pdhg_trial_dual(h, step, io.primal_weight, ratio, raw))) return rc;
+    io.kkt_passes += 0.5;
+    const MalitskyPockRule rule = malitsky_pock_rule(raw, step, io.breaking_factor, io.downscaling_factor);
+    if (rule.accept) {
+      // the first accept into an empty primal average adds the CURRENT x first (pdhg.jl:621-627)
+      if (h->sum_x_count == 0 && (rc = pdhg_add_current_primal_to_average(h, step * ratio))) return rc;
+      if ((rc = pdhg_accept(h, step_on_entry))) return rc;
+      done = true;
+    } else step = rule.next_step;
+  }
+  if (!done) { io.numerical_error = 1; return 0; }       // step size and ratio stay as they came
+  io.step_size = step;
+  io.ratio = ratio;
+  return 0;
+}
+
+// The per-handle loop of the two calls from a given place (io.steps_done of the n_steps are taken already): batches of
+// two and more go to the one-workgroup kernel where the handle suits it (small_policy_steps), everything else -- and a
+// Malitsky-Pock take_step into an empty primal average -- is taken launch by launch.
+static int take_steps_policy_resume(pdhg_handle *h, int64_t n_steps, PolicyIO &io) {
+  while (io.steps_done < n_steps && !io.numerical_error) {
+    const bool quirk = io.policy == SMALL_MALITSKY_POCK && h->sum_x_count == 0;
+    if (!quirk && n_steps - io.steps_done >= 2 && !h->grp && check_handle(h) == 0) {
+      const int rc = small_policy_steps(h, n_steps - io.steps_done, io);
+      if (rc == 0) continue;
+      if (rc != 1) return rc;
+    }
+    if (int rc = io.policy == SMALL_MALITSKY_POCK ? take_step_malitsky_pock_one(h, io) : take_step_constant_one(h, io)) return rc;
+    io.steps_done += 1;
+  }
+  return 0;
+}
+
+static int policy_handle_check(pdhg_handle *h, int policy, const char *who) {
+  if (int rc = check_handle(h, false)) return rc;
+  if (policy == SMALL_MALITSKY_POCK && h->has_q)
+    return fail(-2, std::string(who) + ": Malitsky and Pock linesearch is only supported for linear programming problems");
+  return 0;
+}
+
+int pdhg_take_steps_constant(pdhg_handle *h, int64_t n_steps, double step_size, double primal_weight,
+                             double *cumulative_kkt_passes_io, int64_t *steps_done_out) {
+  RoctxRange roctx_range("pdhg_take_steps_constant");
+  if (!steps_done_out) return fail(-1, "null argument");
+  if (n_steps < 0) return fail(-2, "pdhg_take_steps_constant: n_steps < 0");
+  *steps_done_out = 0;
+  if (!h || !cumulative_kkt_passes_io) return fail(-1, "null argument");
+  if (int rc = policy_handle_check(h, SMALL_CONSTANT, "pdhg_take_steps_constant")) return rc;
+  double ratio = 0.0;
+  int64_t iterations = 0;
+  int numerical_error = 0;
+  PolicyIO io{SMALL_CONSTANT, step_size, ratio, iterations, *cumulative_kkt_passes_io, numerical_error, *steps_done_out,
+              primal_weight, 0.0, 0.0, 0.0};
+  return take_steps_policy_resume(h, n_steps, io);
+}
+
+int pdhg_take_steps_malitsky_pock(pdhg_handle *h, int64_t n_steps, double downscaling_factor, double breaking_factor,
+                                  double interpolation_coefficient, double *step_size_io, double *ratio_step_sizes_io,
+                                  double primal_weight, int64_t *total_number_iterations_io,
+                                  double *cumulative_kkt_passes_io, int *numerical_error_out, int64_t *steps_done_out) {
+  RoctxRange roctx_range("pdhg_take_steps_malitsky_pock");
+  if (!steps_done_out) return fail(-1, "null argument");
+  if (n_steps < 0) return fail(-2, "pdhg_take_steps_malitsky_pock: n_steps < 0");
+  *steps_done_out = 0;
+  if (!h || !step_size_io || !ratio_step_sizes_io || !total_number_iterations_io || !cumulative_kkt_passes_io ||
+      !numerical_error_out)
+    return fail(-1, "null argument");
+  *numerical_error_out = 0;
+  if (int rc = policy_handle_check(h, SMALL_MALITSKY_POCK, "pdhg_take_steps_malitsky_pock")) return rc;
+  PolicyIO io{SMALL_MALITSKY_POCK, *step_size_io, *ratio_step_sizes_io, *total_number_iterations_io, *cumulative_kkt_passes_io,
+              *numerical_error_out, *steps_done_out, primal_weight, downscaling_factor, breaking_factor,
+              interpolation_coefficient};
+  return take_steps_policy_resume(h, n_steps, io);
+}
+
+/* The multi-step launches a handle has made so far: [0] launches of the one-workgroup small-LP kernels (any policy),
+ * [1] launches of the persistent multi-step kernel, [2] trials inside those, [3] 0. */
+int pdhg_steps_info(pdhg_handle *h, int64_t out[4]) {
+  if (!h || !out) return fail(-1, "null argument");
+  out[0] = h->small_lp_launches; out[1] = h->steps_launches; out[2] = h->steps_trials; out[3] = 0;
+  return 0;
+}
+
 int pdhg_add_current_primal_to_average(pdhg_handle *h0, double weight) {
   int rc = check_handle(h0);
   if (rc) return rc;

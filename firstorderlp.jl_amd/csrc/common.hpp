@@ -188,6 +188,32 @@ __host__ __device__ inline StepRule adaptive_step_rule(const double raw[5], doub
   return r;
 }
 
+// The scalar part of take_step(::MalitskyPockStepsizeParameters) (pdhg.jl:555-647), ONE definition for the host loop
+// (pdhg_take_steps_malitsky_pock) and for the one-workgroup kernel (small_lp_kernel.hpp): the expression trees of
+// take_step_malitsky_pock in primal_dual_hybrid_gradient.py, IEEE sqrt on both sides, -ffp-contract=off.
+// (The constant policy, pdhg.jl:737-767, has no rule: every trial is accepted.)
+// The step size a take_step tries first (pdhg.jl:580-584): the step on entry, extrapolated by the last ratio.
+__host__ __device__ inline double malitsky_pock_first_step(double step_on_entry, double ratio_step_sizes,
+                                                           double interpolation_coefficient) {
+  const double f = interpolation_coefficient * (sqrt(1 + ratio_step_sizes) - 1);
+  return step_on_entry + f * step_on_entry;
+}
+// After a dual trial with sums raw[] (pdhg.jl:615-616, 637): accepted, or the step size of the next trial.  A NaN on
+// either side makes the comparison false, as in the reference: the trial is rejected.
+struct MalitskyPockRule {
+  int accept;
+  double next_step;
+};
+__host__ __device__ inline MalitskyPockRule malitsky_pock_rule(const double raw[5], double step_size, double breaking_factor,
+                                                               double downscaling_factor) {
+  MalitskyPockRule r;
+  const double norm_delta_dual_product = sqrt(raw[3]), norm_delta_dual = sqrt(raw[2]);
+  r.accept = step_size * norm_delta_dual_product <= breaking_factor * norm_delta_dual ? 1 : 0;
+  r.next_step = r.accept ? step_size : step_size * downscaling_factor;
+  return r;
+}
+constexpr int MALITSKY_POCK_MAX_TRIALS = 60;      // dual trials of one take_step before numerical_error (pdhg.jl:586)
+
 // The adaptive policy's scalars of one solve on the host side of stepping.  What the caller reads afterwards is BOUND
 // by reference (the C ABI's pointers, or elements of its arrays: every update lands in the caller's storage at once,
 // nothing is copied back at the end of a call); what it only passes in is held by value.
@@ -217,6 +243,19 @@ inline StepRule step_after_trial(StepIO &io, const double raw[5]) {
   else io.step_size = rule.next_step;
   return rule;
 }
+
+// The same for the two other policies (pdhg_take_steps_constant / _malitsky_pock).  The constant policy reads step_size
+// and primal_weight alone and moves kkt_passes and steps_done; its callers bind the others to storage nobody reads.
+struct PolicyIO {
+  int policy;                   // SMALL_CONSTANT or SMALL_MALITSKY_POCK (small_lp_kernel.hpp)
+  double &step_size;
+  double &ratio;                // ratio_step_sizes
+  int64_t &iterations;
+  double &kkt_passes;
+  int &numerical_error;
+  int64_t &steps_done;
+  double primal_weight, downscaling_factor, breaking_factor, interpolation_coefficient;
+};
 
 // A load that cannot be served by a stale line of this CU's L1: agent scope (sc1), served by the L2.  The
 // multi-step trial kernel re-reads vectors that OTHER compute units rewrote since this CU last read them, and a

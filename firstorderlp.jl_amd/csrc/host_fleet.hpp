@@ -89,6 +89,7 @@ void fleet_count_miss(pdhg_handle *h) {
 struct FleetCarry {
   int k = 0;                   // index in FleetState::mem
   StepIO *io = nullptr;        // its step state (bound to the caller's arrays at k)
+  PolicyIO *pio = nullptr;     // ... under the constant or the Malitsky-Pock policy (fleet_policy_launch)
   int n = 0, max_trials = 0, table_len = 0;
   int64_t k1_first = 0;        // k1 of its first trial
   bool few = false;
@@ -176,7 +177,7 @@ int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry) {
     if (c.few) { n_few += 1; lds_few = std::max(lds_few, small_lp_lds_bytes(h)); }
     else lds_big = std::max(lds_big, small_lp_lds_bytes(h));
   }
-  if ((rc = small_lp_lds_limit(f->device, 1, std::max(lds_few, lds_big)))) return rc;
+  if ((rc = small_lp_lds_limit(f->device, SMALL_ADAPTIVE, 1, std::max(lds_few, lds_big)))) return rc;
   HIP_TRY(hipMemcpyAsync(F.args_dev, F.args_host, sizeof(SmallLpArgs) * carry.size(), hipMemcpyHostToDevice, f->stream));
   const size_t n_big = carry.size() - n_few;
   if (n_few > 0) {
@@ -192,5 +193,55 @@ int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry) {
   HIP_TRY(hipGetLastError());
   for (const FleetCarry &c : carry)
     if ((rc = small_lp_collect(F.mem[(size_t)c.k], c.seq, *c.io))) return rc;
+  return 0;
+}
+
+// The same for the constant and the Malitsky-Pock policy (every entry small_lp_eligible, n >= 2, Malitsky-Pock: a primal
+// average that is not empty): no tables of powers, the policy's own kernels, what small_policy_steps would have left.
+int fleet_policy_launch(pdhg_handle *f, std::vector<FleetCarry> &carry) {
+  FleetState &F = *f->fleet;
+  if (carry.empty()) return 0;
+  const int policy = carry[0].pio->policy;
+  HIP_TRY(hipSetDevice(f->device));
+  int rc;
+  for (FleetCarry &c : carry) {
+    pdhg_handle *h = F.mem[(size_t)c.k];
+    if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
+    if ((rc = steps_result_words(h))) return rc;
+    c.few = small_lp_few_rows(h);
+  }
+  if ((rc = fleet_reserve(f, carry.size(), 0))) return rc;
+  std::stable_sort(carry.begin(), carry.end(), [&](const FleetCarry &a, const FleetCarry &b) {
+    if (a.few != b.few) return a.few;
+    return F.mem[(size_t)a.k]->nnz > F.mem[(size_t)b.k]->nnz;
+  });
+  size_t n_few = 0, lds_few = 0, lds_big = 0;
+  for (size_t i = 0; i < carry.size(); ++i) {
+    FleetCarry &c = carry[i];
+    pdhg_handle *h = F.mem[(size_t)c.k];
+    F.args_host[i] = small_policy_stage(h, c.n, *c.pio);
+    c.seq = F.args_host[i].seq;
+    if (c.few) { n_few += 1; lds_few = std::max(lds_few, small_lp_lds_bytes(h)); }
+    else lds_big = std::max(lds_big, small_lp_lds_bytes(h));
+  }
+  if ((rc = small_lp_lds_limit(f->device, policy, 1, std::max(lds_few, lds_big)))) return rc;
+  HIP_TRY(hipMemcpyAsync(F.args_dev, F.args_host, sizeof(SmallLpArgs) * carry.size(), hipMemcpyHostToDevice, f->stream));
+  const size_t n_big = carry.size() - n_few;
+  const SmallLpArgs *few_table = F.args_dev, *big_table = F.args_dev + n_few;
+  if (n_few > 0) {
+    if (policy == SMALL_MALITSKY_POCK)
+      hipLaunchKernelGGL(small_fleet_malitsky_pock_kernel<256>, dim3((unsigned)n_few), dim3(256), lds_few, f->stream, few_table, (int)n_few);
+    else hipLaunchKernelGGL(small_fleet_constant_kernel<256>, dim3((unsigned)n_few), dim3(256), lds_few, f->stream, few_table, (int)n_few);
+    F.launches += 1;
+  }
+  if (n_big > 0) {
+    if (policy == SMALL_MALITSKY_POCK)
+      hipLaunchKernelGGL(small_fleet_malitsky_pock_kernel<SMALL_TPB>, dim3((unsigned)n_big), dim3(SMALL_TPB), lds_big, f->stream, big_table, (int)n_big);
+    else hipLaunchKernelGGL(small_fleet_constant_kernel<SMALL_TPB>, dim3((unsigned)n_big), dim3(SMALL_TPB), lds_big, f->stream, big_table, (int)n_big);
+    F.launches += 1;
+  }
+  HIP_TRY(hipGetLastError());
+  for (const FleetCarry &c : carry)
+    if ((rc = small_policy_collect(F.mem[(size_t)c.k], c.seq, *c.pio))) return rc;
   return 0;
 }

@@ -17,20 +17,28 @@ bool small_lp_eligible(pdhg_handle *h) {
 }
 
 // The opt-in for the launch's dynamic LDS (beyond 64 KiB), per device and kernel instance; it only ever grows
-// (ensure_lds_limit's reasoning).  `which`: 0 the solo instantiations, 1 the fleet's.
-int small_lp_lds_limit(int device, int which, size_t lds) {
-  static size_t limit[64][2] = {};
+// (ensure_lds_limit's reasoning).  `policy`: SMALL_ADAPTIVE / _CONSTANT / _MALITSKY_POCK; `which`: 0 the solo
+// instantiations, 1 the fleet's.
+int small_lp_lds_limit(int device, int policy, int which, size_t lds) {
+  static size_t limit[64][3][2] = {};
   static std::mutex mu;
   std::lock_guard<std::mutex> lock(mu);
-  size_t &cur = limit[device & 63][which];
+  size_t &cur = limit[device & 63][policy][which];
   if (cur < lds) {
-    if (which == 0) {
-      HIP_TRY(hipFuncSetAttribute((const void *)small_lp_steps_kernel<SMALL_TPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      HIP_TRY(hipFuncSetAttribute((const void *)small_lp_steps_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else {
-      HIP_TRY(hipFuncSetAttribute((const void *)small_lp_fleet_kernel<SMALL_TPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      HIP_TRY(hipFuncSetAttribute((const void *)small_lp_fleet_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+#define SMALL_LDS_OPT_IN(KERNEL)                                                                                               \
+  do {                                                                                                                         \
+    HIP_TRY(hipFuncSetAttribute((const void *)KERNEL<SMALL_TPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
+    HIP_TRY(hipFuncSetAttribute((const void *)KERNEL<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));              \
+  } while (0)
+    switch (policy * 2 + which) {
+      case SMALL_ADAPTIVE * 2 + 0: SMALL_LDS_OPT_IN(small_lp_steps_kernel); break;
+      case SMALL_ADAPTIVE * 2 + 1: SMALL_LDS_OPT_IN(small_lp_fleet_kernel); break;
+      case SMALL_CONSTANT * 2 + 0: SMALL_LDS_OPT_IN(small_lp_constant_kernel); break;
+      case SMALL_CONSTANT * 2 + 1: SMALL_LDS_OPT_IN(small_fleet_constant_kernel); break;
+      case SMALL_MALITSKY_POCK * 2 + 0: SMALL_LDS_OPT_IN(small_lp_malitsky_pock_kernel); break;
+      default: SMALL_LDS_OPT_IN(small_fleet_malitsky_pock_kernel); break;
     }
+#undef SMALL_LDS_OPT_IN
     cur = lds;
   }
   return 0;
@@ -83,7 +91,7 @@ int small_lp_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   int max_trials = 0, table_len = 0;
   if ((rc = steps_prepare(h, n, io, &max_trials, &table_len))) return rc;
   const size_t lds = small_lp_lds_bytes(h);
-  if ((rc = small_lp_lds_limit(h->device, 0, lds))) return rc;
+  if ((rc = small_lp_lds_limit(h->device, SMALL_ADAPTIVE, 0, lds))) return rc;
   const SmallLpArgs a = small_lp_stage(h, n, max_trials, table_len, io.step_size, io.primal_weight, h->steps_pow_dev,
                                        h->steps_pow_dev + table_len);
   const auto c1 = std::chrono::steady_clock::now();
@@ -93,6 +101,80 @@ int small_lp_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   const auto c2 = std::chrono::steady_clock::now();
   h->t_launch += std::chrono::duration<double>(c2 - c1).count();
   rc = small_lp_collect(h, a.seq, io);
+  h->t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - c2).count();
+  return rc;
+}
+
+// ---- the constant and the Malitsky-Pock policy in the same kernel body (PolicyIO, common.hpp) -------------------------
+// take_steps of one launch: its worst case -- MALITSKY_POCK_MAX_TRIALS trials in every take_step; one per step under the
+// constant policy -- stays within the trials steps_budget allows the largest adaptive launch (steps_collect's time-out
+// is sized for that).
+int small_policy_launch_steps(int policy, int64_t n_steps) {
+  int max_trials = 0, table_len = 0;
+  steps_budget(1 << 20, &max_trials, &table_len);
+  const int cap = policy == SMALL_MALITSKY_POCK ? max_trials / MALITSKY_POCK_MAX_TRIALS : 1 << 20;
+  return (int)std::min<int64_t>(n_steps, std::max(cap, 1));
+}
+
+SmallLpArgs small_policy_stage(pdhg_handle *h, int n, const PolicyIO &io) {
+  SmallLpArgs a = small_lp_stage(h, n, 0, 0, io.step_size, io.primal_weight, nullptr, nullptr);
+  if (io.policy == SMALL_MALITSKY_POCK) {
+    a.ratio = io.ratio;
+    a.downscaling_factor = io.downscaling_factor; a.breaking_factor = io.breaking_factor;
+    a.interpolation_coefficient = io.interpolation_coefficient;
+  }
+  return a;
+}
+
+// Wait for launch `seq` of h; its result words into the handle's bookkeeping and the step state, by the statements of
+// the host loops (abi_trial.hpp): half a KKT pass for x' and for every dual trial, a whole one per constant step.
+int small_policy_collect(pdhg_handle *h, unsigned long long seq, PolicyIO &io) {
+  double r[STEPS_RES_K];
+  if (int rc = wait_words(h->stream, h->steps_res, STEPS_RES_CAP, STEPS_RES_K, seq, r, 400000000L,
+                          "small-LP kernel finished without publishing its results")) return rc;
+  const int64_t steps = (int64_t)r[1], trials = (int64_t)r[2], failed = r[8] != 0.0 ? 1 : 0;
+  h->n_graph_trials += trials;
+  h->sum_x_count += steps; h->sum_y_count += steps;
+  h->sum_x_weights = r[6]; h->sum_y_weights = r[7];
+  if (io.policy == SMALL_MALITSKY_POCK) {
+    io.step_size = r[0];
+    io.ratio = r[3];
+    io.iterations += trials;
+    for (int64_t q = 0; q < steps + failed + trials; ++q) io.kkt_passes += 0.5;
+  } else {
+    for (int64_t q = 0; q < steps; ++q) io.kkt_passes += 1;
+  }
+  io.steps_done += steps + failed;      // the failing take_step counts as taken (it is not repeated), as under the adaptive policy
+  if (failed) io.numerical_error = 1;
+  h->small_lp_launches += 1;
+  h->state_version += 1;
+  return 0;
+}
+
+// Up to n_steps take_steps of io.policy in one launch; returns 1 when not eligible (nothing launched).  Malitsky-Pock:
+// the caller has seen to it that the primal average is not empty.
+int small_policy_steps(pdhg_handle *h, int64_t n_steps, PolicyIO &io) {
+  if (!small_lp_eligible(h)) return 1;
+  HIP_TRY(hipSetDevice(h->device));
+  int rc;
+  if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
+  if ((rc = steps_result_words(h))) return rc;
+  const size_t lds = small_lp_lds_bytes(h);
+  if ((rc = small_lp_lds_limit(h->device, io.policy, 0, lds))) return rc;
+  const SmallLpArgs a = small_policy_stage(h, small_policy_launch_steps(io.policy, n_steps), io);
+  const bool few = small_lp_few_rows(h);
+  const auto c1 = std::chrono::steady_clock::now();
+  if (io.policy == SMALL_MALITSKY_POCK) {
+    if (few) hipLaunchKernelGGL(small_lp_malitsky_pock_kernel<256>, dim3(1), dim3(256), lds, h->stream, a);
+    else hipLaunchKernelGGL(small_lp_malitsky_pock_kernel<SMALL_TPB>, dim3(1), dim3(SMALL_TPB), lds, h->stream, a);
+  } else {
+    if (few) hipLaunchKernelGGL(small_lp_constant_kernel<256>, dim3(1), dim3(256), lds, h->stream, a);
+    else hipLaunchKernelGGL(small_lp_constant_kernel<SMALL_TPB>, dim3(1), dim3(SMALL_TPB), lds, h->stream, a);
+  }
+  HIP_TRY(hipGetLastError());
+  const auto c2 = std::chrono::steady_clock::now();
+  h->t_launch += std::chrono::duration<double>(c2 - c1).count();
+  rc = small_policy_collect(h, a.seq, io);
   h->t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - c2).count();
   return rc;
 }

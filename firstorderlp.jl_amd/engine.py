@@ -229,6 +229,37 @@ class HipPdhgEngine:
             ctypes.byref(it), ctypes.byref(kkt), ctypes.byref(err), ctypes.byref(done)))
         return ss.value, it.value, kkt.value, bool(err.value), done.value
 
+    def take_steps_constant(self, n_steps, step_size, primal_weight, cumulative_kkt_passes):
+        """pdhg_take_steps_constant: `n_steps` constant-step take_steps in one call.  Returns
+        (cumulative_kkt_passes, steps_done)."""
+        kkt = ctypes.c_double(cumulative_kkt_passes)
+        done = ctypes.c_int64(0)
+        _lib.check(self._L.pdhg_take_steps_constant(self._h, int(n_steps), step_size, primal_weight, ctypes.byref(kkt),
+                                                    ctypes.byref(done)))
+        return kkt.value, done.value
+
+    def take_steps_malitsky_pock(self, n_steps, downscaling_factor, breaking_factor, interpolation_coefficient,
+                                 step_size, ratio_step_sizes, primal_weight, total_number_iterations,
+                                 cumulative_kkt_passes):
+        """pdhg_take_steps_malitsky_pock: `n_steps` take_steps in one call (an LP only).  Returns (step_size,
+        ratio_step_sizes, total_number_iterations, cumulative_kkt_passes, numerical_error, steps_done)."""
+        ss = ctypes.c_double(step_size)
+        ratio = ctypes.c_double(ratio_step_sizes)
+        it = ctypes.c_int64(total_number_iterations)
+        kkt = ctypes.c_double(cumulative_kkt_passes)
+        err = ctypes.c_int(0)
+        done = ctypes.c_int64(0)
+        _lib.check(self._L.pdhg_take_steps_malitsky_pock(
+            self._h, int(n_steps), downscaling_factor, breaking_factor, interpolation_coefficient, ctypes.byref(ss),
+            ctypes.byref(ratio), primal_weight, ctypes.byref(it), ctypes.byref(kkt), ctypes.byref(err), ctypes.byref(done)))
+        return ss.value, ratio.value, it.value, kkt.value, bool(err.value), done.value
+
+    def steps_info(self):
+        """pdhg_steps_info: [small-LP launches, multi-step launches, trials inside those, 0] of this handle so far."""
+        out = np.zeros(4, dtype=np.int64)
+        _lib.check(self._L.pdhg_steps_info(self._h, _pi(out)))
+        return out.tolist()
+
     def add_current_primal_to_average(self, weight):
         _lib.check(self._L.pdhg_add_current_primal_to_average(self._h, weight))
 
@@ -492,7 +523,7 @@ class _MemberEngine(HipPdhgEngine):
 
 class _MemberOwner:
     """What ``HipPdhgBatch`` and ``HipPdhgFleet`` share: the library ``_L``, the owning handle ``_h``, ``members``
-    (``_MemberEngine`` views, freed with the handle) and the marshalling of their ``take_steps_adaptive``."""
+    (``_MemberEngine`` views, freed with the handle) and the marshalling of their ``take_steps_*`` calls."""
 
     def close(self):
         if getattr(self, "_h", None):
@@ -522,3 +553,29 @@ class _MemberOwner:
         _lib.check(call(self._h, n_steps, float(reduction_exponent), float(growth_exponent), _pd(ss), _pd(pw), _pi(it),
                         _pd(kkt), err.ctypes.data_as(_int_p), *active, _pi(done)))
         return ss, it, kkt, err.astype(bool), done
+
+    def _member_array(self, values, dtype=np.float64):
+        return np.ascontiguousarray(np.array(np.broadcast_to(values, (len(self.members),)), dtype=dtype))
+
+    def _take_steps_constant(self, call, n_steps, step_sizes, primal_weights, cumulative_kkt_passes):
+        """``call(handle, n_steps, step sizes, primal weights, KKT passes, steps_done)`` with one array entry per member.
+        Returns arrays (cumulative_kkt_passes, steps_done)."""
+        ss, pw, kkt = (self._member_array(v) for v in (step_sizes, primal_weights, cumulative_kkt_passes))
+        done = np.zeros(len(self.members), dtype=np.int64)
+        _lib.check(call(self._h, n_steps, _pd(ss), _pd(pw), _pd(kkt), _pi(done)))
+        return kkt, done
+
+    def _take_steps_malitsky_pock(self, call, n_steps, downscaling_factor, breaking_factor, interpolation_coefficient,
+                                  step_sizes, ratio_step_sizes, primal_weights, total_number_iterations,
+                                  cumulative_kkt_passes):
+        """``call(handle, n_steps, the policy's parameters, the members' five scalar arrays, numerical_error,
+        steps_done)``.  Returns arrays (step_sizes, ratio_step_sizes, total_number_iterations, cumulative_kkt_passes,
+        numerical_error, steps_done)."""
+        ss, ratio, pw, kkt = (self._member_array(v) for v in (step_sizes, ratio_step_sizes, primal_weights,
+                                                              cumulative_kkt_passes))
+        it = self._member_array(total_number_iterations, np.int64)
+        err = np.zeros(len(self.members), dtype=np.int32)
+        done = np.zeros(len(self.members), dtype=np.int64)
+        _lib.check(call(self._h, n_steps, float(downscaling_factor), float(breaking_factor), float(interpolation_coefficient),
+                        _pd(ss), _pd(ratio), _pd(pw), _pi(it), _pd(kkt), err.ctypes.data_as(_int_p), _pi(done)))
+        return ss, ratio, it, kkt, err.astype(bool), done

@@ -3,8 +3,8 @@
 ``optimize_many(params, problems)`` returns what ``optimize(params, problems[k])`` returns, for every k.  The problems
 share nothing -- any mix of shapes, LPs and QPs.  What they share is the launch: an LP small enough for the solo
 small-LP path (csrc/small_lp_kernel.hpp: every vector in one workgroup's LDS) takes its steps between two evaluations in
-one workgroup, and ``pdhg_fleet_take_steps_adaptive`` carries one such workgroup per problem in one launch instead of one
-launch per problem on one of 256 compute units.  The members do not run in lockstep: each accepts, rejects, restarts and
+one workgroup, and ``pdhg_fleet_take_steps_adaptive`` (``_constant`` / ``_malitsky_pock`` under the two other policies)
+carries one such workgroup per problem in one launch instead of one launch per problem on one of 256 compute units.  The members do not run in lockstep: each accepts, rejects, restarts and
 terminates on its own, at the iterations ``optimize`` would.  Both drivers run the same per-problem solve object
 (``primal_dual_hybrid_gradient._Solve``).  The checks between the steps go the same way: a fleet with ``eval_points`` and
 ``trust_region_bounds`` gets the device requests of every member's check -- the termination evaluation, the
@@ -22,10 +22,11 @@ import numpy as np
 
 from . import _lib
 from .engine import _int_p, _MemberEngine, _MemberOwner, _d, _i, _pd, _pi
-from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams, _check_inputs,
-                                          _constant_step_estimate, _device_scaled_problem, _drive_solves,
-                                          _host_scaled_problem, _pack_step_states, _rescales_on_device, _Solve,
-                                          _unpack_step_states, take_steps)
+from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams,
+                                          MalitskyPockStepsizeParameters, _check_inputs, _constant_step_estimate,
+                                          _device_scaled_problem, _drive_solves, _host_scaled_problem, _pack_ratios,
+                                          _pack_step_states, _rescales_on_device, _Solve, _unpack_step_states,
+                                          take_steps)
 
 
 class HipPdhgFleet(_MemberOwner):
@@ -85,8 +86,26 @@ class HipPdhgFleet(_MemberOwner):
                                          growth_exponent, step_sizes, primal_weights, total_number_iterations,
                                          cumulative_kkt_passes)
 
+    def take_steps_constant(self, n_steps, step_sizes, primal_weights, cumulative_kkt_passes):
+        """``n_steps[k]`` constant-step take_steps of member k, for every k (0: left alone); the small LPs among them in
+        one launch.  Returns arrays (cumulative_kkt_passes, steps_done)."""
+        ns = np.array(np.broadcast_to(n_steps, (self.K,)), dtype=np.int64)
+        return self._take_steps_constant(self._L.pdhg_fleet_take_steps_constant, _pi(ns), step_sizes, primal_weights,
+                                         cumulative_kkt_passes)
+
+    def take_steps_malitsky_pock(self, n_steps, downscaling_factor, breaking_factor, interpolation_coefficient,
+                                 step_sizes, ratio_step_sizes, primal_weights, total_number_iterations,
+                                 cumulative_kkt_passes):
+        """``n_steps[k]`` Malitsky-Pock take_steps of member k (an LP), for every k (0: left alone); the small LPs among
+        them in one launch.  Returns arrays (step_sizes, ratio_step_sizes, total_number_iterations,
+        cumulative_kkt_passes, numerical_error, steps_done)."""
+        ns = np.array(np.broadcast_to(n_steps, (self.K,)), dtype=np.int64)
+        return self._take_steps_malitsky_pock(self._L.pdhg_fleet_take_steps_malitsky_pock, _pi(ns), downscaling_factor,
+                                              breaking_factor, interpolation_coefficient, step_sizes, ratio_step_sizes,
+                                              primal_weights, total_number_iterations, cumulative_kkt_passes)
+
     def info(self):
-        """dict(members, shared_launches, carried, single): the last two describe the last ``take_steps_adaptive``."""
+        """dict(members, shared_launches, carried, single): the last two describe the last ``take_steps_*`` call."""
         info = np.zeros(8, dtype=np.int64)
         _lib.check(self._L.pdhg_fleet_info(self._h, _pi(info)))
         return dict(zip(["members", "shared_launches", "carried", "single"], info[:4].tolist()))
@@ -137,22 +156,40 @@ _default_fleet_factory.takes_original_problem = True
 
 
 def _step_fleet(fleet, solves, policy, requests):
-    """The steps the members named at this round: one ``take_steps_adaptive`` of the fleet for all of them under the
-    adaptive policy, else (another policy, PDHG_PY_TAKE_STEP=1, a fleet without the native call) member by member
-    through ``take_steps``.  Returns (solve, steps taken, seconds) per request."""
-    if (isinstance(policy, AdaptiveStepsizeParams) and hasattr(fleet, "take_steps_adaptive")
-            and os.environ.get("PDHG_PY_TAKE_STEP", "0") != "1"):
+    """The steps the members named at this round: one ``take_steps_adaptive`` / ``_constant`` / ``_malitsky_pock`` of the
+    fleet for all of them, else (PDHG_PY_TAKE_STEP=1, a fleet without the policy's native call) member by member through
+    ``take_steps``.  Returns (solve, steps taken, seconds) per request."""
+    call = {AdaptiveStepsizeParams: "take_steps_adaptive", ConstantStepsizeParams: "take_steps_constant",
+            MalitskyPockStepsizeParameters: "take_steps_malitsky_pock"}.get(type(policy))
+    if call and hasattr(fleet, call) and os.environ.get("PDHG_PY_TAKE_STEP", "0") != "1":
         K = len(solves)
         slot = {id(mb): k for k, mb in enumerate(solves)}
         placed = [(slot[id(mb)], mb.state) for mb, _ in requests]
         ns = np.zeros(K, dtype=np.int64)
         for mb, steps in requests:
             ns[slot[id(mb)]] = steps
-        packed = _pack_step_states(K, placed)
+        ss, pw, it, kkt = _pack_step_states(K, placed)
         t0 = _time.time()
-        results = fleet.take_steps_adaptive(ns, policy.reduction_exponent, policy.growth_exponent, *packed)
+        if isinstance(policy, AdaptiveStepsizeParams):
+            results = fleet.take_steps_adaptive(ns, policy.reduction_exponent, policy.growth_exponent, ss, pw, it, kkt)
+            taken = _unpack_step_states(placed, *results)
+        elif isinstance(policy, ConstantStepsizeParams):
+            kkt, done = fleet.take_steps_constant(ns, ss, pw, kkt)
+            for k, st in placed:
+                st.cumulative_kkt_passes = float(kkt[k])
+            taken = [int(done[k]) for k, _ in placed]
+        else:
+            if not all(mb.is_lp for mb, _ in requests):
+                raise ValueError("Malitsky and Pock linesearch is only supported for "
+                                 "linear programming problems.")
+            ss, ratio, *results = fleet.take_steps_malitsky_pock(
+                ns, policy.downscaling_factor, policy.breaking_factor, policy.interpolation_coefficient, ss,
+                _pack_ratios(K, placed), pw, it, kkt)
+            taken = _unpack_step_states(placed, ss, *results)
+            for k, st in placed:
+                st.ratio_step_sizes = float(ratio[k])
         dt = _time.time() - t0
-        return [(mb, d, dt) for (mb, _), d in zip(requests, _unpack_step_states(placed, *results))]
+        return [(mb, d, dt) for (mb, _), d in zip(requests, taken)]
     out = []
     for mb, steps in requests:
         t0 = _time.time()
@@ -188,9 +225,10 @@ def optimize_many(params, problems, fleet_factory=None):
     Anything ``optimize`` accepts: any mix of shapes, LPs and QPs, every step-size policy, any number of problems (an
     empty list raises ``ValueError`` before any device work).  ``fleet_factory(problems) -> fleet`` builds the device
     side (default ``HipPdhgFleet``): an object with ``.members`` (one engine per problem, in order), ``close()`` and,
-    optionally, ``take_steps_adaptive`` and the pair ``eval_points`` / ``trust_region_bounds`` (the checks in shared
-    launches); a factory whose ``takes_original_problem`` is true receives the original
-    problems and every member rescales on the device, any other one receives the host-rescaled problems."""
+    optionally, ``take_steps_adaptive`` / ``take_steps_constant`` / ``take_steps_malitsky_pock`` and the pair
+    ``eval_points`` / ``trust_region_bounds`` (the checks in shared launches); a factory whose
+    ``takes_original_problem`` is true receives the original problems and every member rescales on the device, any other
+    one receives the host-rescaled problems."""
     problems = list(problems)
     if not problems:
         raise ValueError("optimize_many needs at least one problem")

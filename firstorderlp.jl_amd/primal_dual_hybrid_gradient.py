@@ -139,6 +139,14 @@ def _store_step_state(solver_state, step_size, total_number_iterations, cumulati
         solver_state.numerical_error = True
 
 
+def _pack_ratios(K, placed):
+    """ratio_step_sizes of a K-member Malitsky-Pock call, packed like ``_pack_step_states``' arrays."""
+    ratio = np.ones(K)
+    for k, st in placed:
+        ratio[k] = st.ratio_step_sizes
+    return ratio
+
+
 def _pack_step_states(K, placed):
     """(step_sizes, primal_weights, total_number_iterations, cumulative_kkt_passes) of a K-member call; the slots that
     ``placed`` does not name hold harmless values."""
@@ -246,14 +254,31 @@ def take_step(step_params, solver_state, is_lp=True):
 def take_steps(step_params, solver_state, n_steps, is_lp=True):
     """`n_steps` consecutive take_step calls -- the iterations optimize() runs between
     two termination evaluations (pdhg.jl:862-1046: nothing else happens on them).
-    With the HIP engine and the adaptive rule they are one library call
-    (pdhg_take_steps_adaptive; the same statements, so the same scalars bit for bit).
+    With the HIP engine they are one library call under every policy
+    (pdhg_take_steps_adaptive / _constant / _malitsky_pock; the same statements, so the
+    same scalars bit for bit).  PDHG_PY_TAKE_STEP=1 keeps the loop below, which is also
+    what every other engine uses.
     Stops after a step that raised numerical_error.  Returns the steps taken."""
     eng = solver_state.engine
-    if (isinstance(step_params, AdaptiveStepsizeParams) and hasattr(eng, "take_steps_adaptive")
-            and os.environ.get("PDHG_PY_TAKE_STEP", "0") != "1"):
+    native = os.environ.get("PDHG_PY_TAKE_STEP", "0") != "1"
+    if isinstance(step_params, AdaptiveStepsizeParams) and hasattr(eng, "take_steps_adaptive") and native:
         *results, done = eng.take_steps_adaptive(n_steps, *_native_step_args(step_params, solver_state))
         _store_step_state(solver_state, *results)
+        return done
+    if isinstance(step_params, ConstantStepsizeParams) and hasattr(eng, "take_steps_constant") and native:
+        solver_state.cumulative_kkt_passes, done = eng.take_steps_constant(
+            n_steps, solver_state.step_size, solver_state.primal_weight, solver_state.cumulative_kkt_passes)
+        return done
+    if isinstance(step_params, MalitskyPockStepsizeParameters) and hasattr(eng, "take_steps_malitsky_pock") and native:
+        if not is_lp:
+            raise ValueError("Malitsky and Pock linesearch is only supported for "
+                             "linear programming problems.")
+        step_size, ratio, *results, done = eng.take_steps_malitsky_pock(
+            n_steps, step_params.downscaling_factor, step_params.breaking_factor, step_params.interpolation_coefficient,
+            solver_state.step_size, solver_state.ratio_step_sizes, solver_state.primal_weight,
+            solver_state.total_number_iterations, solver_state.cumulative_kkt_passes)
+        _store_step_state(solver_state, step_size, *results)
+        solver_state.ratio_step_sizes = float(ratio)
         return done
     done = 0
     while done < n_steps:

@@ -175,6 +175,36 @@ int pdhg_take_steps_adaptive(pdhg_handle *h, int64_t n_steps, double reduction_e
                              int64_t *total_number_iterations, double *cumulative_kkt_passes,
                              int *numerical_error, int64_t *steps_done);
 
+/*
+ * The two other step-size policies, `n_steps` take_steps in one call: the statements of
+ * take_step(::ConstantStepsizeParams) (pdhg.jl:737-767) and take_step(::MalitskyPockStepsizeParameters)
+ * (pdhg.jl:555-647) around pdhg_trial_step / pdhg_trial_primal / pdhg_trial_dual / pdhg_accept, in C, on
+ * every kind of handle -- bit for bit what driving those entry points from the host language gives.  A
+ * small LP (see pdhg_layout_info: small_lp) takes batches of >= 2 in one workgroup with the vectors in
+ * LDS, like pdhg_take_steps_adaptive; medium and large problems take them launch by launch.
+ *   constant: per step one trial with theta = 1, *cumulative_kkt_passes += 1, accept with weight
+ *     step_size.  total_number_iterations is not touched.  QPs are allowed.
+ *   Malitsky-Pock: an LP only (a handle with an objective matrix returns -2, nothing is launched).  Per
+ *     take_step x' once with the step size on entry (+0.5 KKT passes), then up to 60 dual trials with
+ *     ratio = step / step_on_entry as extrapolation coefficient (each +1 iteration, +0.5 KKT passes);
+ *     the accept carries the step size on entry as weight, and while the primal average's count is 0 the
+ *     current x is added first with weight step * ratio (pdhg.jl:621-627).  60 rejections set
+ *     *numerical_error, leave *step_size and *ratio_step_sizes as they came and end the call.
+ * *steps_done counts the take_steps taken, the one that set *numerical_error included (it is not repeated),
+ * as pdhg_take_steps_adaptive does.  Null pointers return -1, n_steps < 0 returns -2, a fleet handle -1:
+ * nothing is launched.
+ */
+int pdhg_take_steps_constant(pdhg_handle *h, int64_t n_steps, double step_size, double primal_weight,
+                             double *cumulative_kkt_passes, int64_t *steps_done);
+int pdhg_take_steps_malitsky_pock(pdhg_handle *h, int64_t n_steps, double downscaling_factor,
+                                  double breaking_factor, double interpolation_coefficient,
+                                  double *step_size, double *ratio_step_sizes, double primal_weight,
+                                  int64_t *total_number_iterations, double *cumulative_kkt_passes,
+                                  int *numerical_error, int64_t *steps_done);
+/* Which path a handle's batches took so far: out[0] launches of the one-workgroup small-LP kernels (any
+ * policy), out[1] launches of the persistent multi-step kernel, out[2] trials inside those, out[3] 0. */
+int pdhg_steps_info(pdhg_handle *h, int64_t out[4]);
+
 /* add_to_primal_solution_weighted_average on the CURRENT x (pdhg.jl:621-627). */
 int pdhg_add_current_primal_to_average(pdhg_handle *h, double weight);
 
@@ -562,8 +592,23 @@ int pdhg_fleet_take_steps_adaptive(pdhg_handle *fleet, const int64_t *n_steps, d
                                    const double *primal_weight, int64_t *total_number_iterations,
                                    double *cumulative_kkt_passes, int *numerical_error,
                                    int64_t *steps_done);
+/* pdhg_take_steps_constant / pdhg_take_steps_malitsky_pock (member k, n_steps[k], ...) for every member k,
+ * bit for bit, under the rules of pdhg_fleet_take_steps_adaptive: all arrays one entry per member,
+ * n_steps[k] == 0 leaves member k and its entries alone, the small LPs that ask for >= 2 steps share one
+ * launch (two when both thread-count classes occur).  A Malitsky-Pock member whose primal average is
+ * empty takes its first step singly (the first-accept rule) and is not carried by that call; a member
+ * with an objective matrix and n_steps[k] > 0 makes the Malitsky-Pock call return -2. */
+int pdhg_fleet_take_steps_constant(pdhg_handle *fleet, const int64_t *n_steps, const double *step_size,
+                                   const double *primal_weight, double *cumulative_kkt_passes,
+                                   int64_t *steps_done);
+int pdhg_fleet_take_steps_malitsky_pock(pdhg_handle *fleet, const int64_t *n_steps,
+                                        double downscaling_factor, double breaking_factor,
+                                        double interpolation_coefficient, double *step_size,
+                                        double *ratio_step_sizes, const double *primal_weight,
+                                        int64_t *total_number_iterations, double *cumulative_kkt_passes,
+                                        int *numerical_error, int64_t *steps_done);
 /* info[0] members, info[1] shared STEP launches so far, info[2] members carried by the shared launch of
- * the last pdhg_fleet_take_steps_adaptive, info[3] members that call stepped singly; the checks in shared
+ * the last pdhg_fleet_take_steps_* call, info[3] members that call stepped singly; the checks in shared
  * launches (below): info[4] launches of the three check kernels so far, info[5] / info[6] items of the
  * last pdhg_fleet_eval_points / pdhg_fleet_trust_region_bounds carried by a shared launch / served per
  * member, info[7] the CALLER's pdhg_eval_point + pdhg_trust_region_bound calls on members so far that

@@ -269,6 +269,44 @@ function take_steps_adaptive_native!(s::HipSolverState, n_steps::Integer, reduct
   return done[]
 end
 
+"""
+`n_steps` constant-step take_steps in one ccall (pdhg_take_steps_constant; bitwise the per-step method below).
+Returns the number of take_steps done.
+"""
+function take_steps_constant_native!(s::HipSolverState, n_steps::Integer)
+  kkt = Ref{Float64}(s.cumulative_kkt_passes); done = Ref{Int64}(0)
+  check(ccall((:pdhg_take_steps_constant, LIB), Cint,
+    (Ptr{Cvoid}, Int64, Float64, Float64, Ref{Float64}, Ref{Int64}),
+    s.handle, n_steps, s.step_size, s.primal_weight, kkt, done))
+  s.cumulative_kkt_passes = kkt[]
+  return done[]
+end
+
+"""
+`n_steps` Malitsky-Pock take_steps in one ccall (pdhg_take_steps_malitsky_pock, an LP only; bitwise the per-step
+method below).  Returns the number of take_steps done, the one that raised a numerical error included.
+"""
+function take_steps_malitsky_pock_native!(s::HipSolverState, n_steps::Integer,
+                                          step_params::FirstOrderLp.MalitskyPockStepsizeParameters)
+  step = Ref{Float64}(s.step_size); ratio = Ref{Float64}(s.ratio_step_sizes)
+  its = Ref{Int64}(s.total_number_iterations)
+  kkt = Ref{Float64}(s.cumulative_kkt_passes); err = Ref{Cint}(0); done = Ref{Int64}(0)
+  check(ccall((:pdhg_take_steps_malitsky_pock, LIB), Cint,
+    (Ptr{Cvoid}, Int64, Float64, Float64, Float64, Ref{Float64}, Ref{Float64}, Float64, Ref{Int64}, Ref{Float64}, Ref{Cint}, Ref{Int64}),
+    s.handle, n_steps, step_params.downscaling_factor, step_params.breaking_factor, step_params.interpolation_coefficient, step, ratio, s.primal_weight, its, kkt, err, done))
+  s.step_size = step[]; s.ratio_step_sizes = ratio[]
+  s.total_number_iterations = its[]; s.cumulative_kkt_passes = kkt[]
+  s.numerical_error = s.numerical_error || err[] != 0
+  return done[]
+end
+
+"(small-LP launches, multi-step launches, trials inside those) of this handle so far (`pdhg_steps_info`)."
+function steps_info(s::HipSolverState)
+  out = zeros(Int64, 4)
+  check(ccall((:pdhg_steps_info, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), s.handle, out))
+  return out[1], out[2], out[3]
+end
+
 "take_step(::AdaptiveStepsizeParams, ...) -- pdhg.jl:653-731 with the vector work on the GPU."
 function FirstOrderLp.take_step(step_params::FirstOrderLp.AdaptiveStepsizeParams,
                                 problem, s::HipSolverState)
@@ -903,22 +941,26 @@ function FirstOrderLp.optimize(hp::HipPdhgParameters,
     end
 
     time_spent_doing_basic_algorithm_checkpoint = time()
-    if params.step_size_policy_params isa FirstOrderLp.AdaptiveStepsizeParams
-      # This iteration's take_step and those of the iterations up to (not including) the next one the test above fires
-      # on -- the reference does nothing else on them (pdhg.jl:862-1046) -- in ONE library call: the library takes them
-      # several per kernel launch with the step rule on the device (bitwise the per-step calls).
-      next_evaluation = (div(iteration - 1, termination_evaluation_frequency) + 1) * termination_evaluation_frequency + 1
-      if iteration < 10
-        next_evaluation = iteration + 1
-      end
-      if iteration < iteration_limit + 1
-        next_evaluation = min(next_evaluation, iteration_limit + 1)
-      end
+    # This iteration's take_step and those of the iterations up to (not including) the next one the test above fires
+    # on -- the reference does nothing else on them (pdhg.jl:862-1046) -- in ONE library call per policy: the library
+    # takes a small LP's several per kernel launch (bitwise the per-step calls).
+    next_evaluation = (div(iteration - 1, termination_evaluation_frequency) + 1) * termination_evaluation_frequency + 1
+    if iteration < 10
+      next_evaluation = iteration + 1
+    end
+    if iteration < iteration_limit + 1
+      next_evaluation = min(next_evaluation, iteration_limit + 1)
+    end
+    policy = params.step_size_policy_params
+    if policy isa FirstOrderLp.AdaptiveStepsizeParams
       iteration += take_steps_adaptive_native!(
-        solver_state, next_evaluation - iteration,
-        params.step_size_policy_params.reduction_exponent, params.step_size_policy_params.growth_exponent) - 1
+        solver_state, next_evaluation - iteration, policy.reduction_exponent, policy.growth_exponent) - 1
+    elseif policy isa FirstOrderLp.ConstantStepsizeParams
+      iteration += take_steps_constant_native!(solver_state, next_evaluation - iteration) - 1
+    elseif policy isa FirstOrderLp.MalitskyPockStepsizeParameters && FirstOrderLp.is_linear_programming_problem(original_problem)
+      iteration += take_steps_malitsky_pock_native!(solver_state, next_evaluation - iteration, policy) - 1
     else
-      FirstOrderLp.take_step(params.step_size_policy_params, original_problem, solver_state)
+      FirstOrderLp.take_step(policy, original_problem, solver_state)
     end
     time_spent_doing_basic_algorithm += time() - time_spent_doing_basic_algorithm_checkpoint
   end
@@ -1074,6 +1116,31 @@ function fleet_take_steps_adaptive(fleet::Ptr{Cvoid}, n_steps::Vector{Int64}, re
      Ptr{Int64}),
     fleet, n_steps, reduction_exponent, growth_exponent, step_size, primal_weight, total_number_iterations,
     cumulative_kkt_passes, numerical_error, steps_done))
+  return numerical_error, steps_done
+end
+
+"`n_steps[k]` constant-step take_steps of member k, for every k (`pdhg_fleet_take_steps_constant`); `cumulative_kkt_passes` is updated in place."
+function fleet_take_steps_constant(fleet::Ptr{Cvoid}, n_steps::Vector{Int64}, step_size::Vector{Float64},
+                                   primal_weight::Vector{Float64}, cumulative_kkt_passes::Vector{Float64})
+  steps_done = zeros(Int64, length(n_steps))
+  check(ccall((:pdhg_fleet_take_steps_constant, LIB), Cint,
+    (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+    fleet, n_steps, step_size, primal_weight, cumulative_kkt_passes, steps_done))
+  return steps_done
+end
+
+"`n_steps[k]` Malitsky-Pock take_steps of member k (an LP), for every k (`pdhg_fleet_take_steps_malitsky_pock`); the vectors are updated in place."
+function fleet_take_steps_malitsky_pock(fleet::Ptr{Cvoid}, n_steps::Vector{Int64}, downscaling_factor::Float64,
+                                        breaking_factor::Float64, interpolation_coefficient::Float64,
+                                        step_size::Vector{Float64}, ratio_step_sizes::Vector{Float64},
+                                        primal_weight::Vector{Float64}, total_number_iterations::Vector{Int64},
+                                        cumulative_kkt_passes::Vector{Float64})
+  K = length(n_steps)
+  numerical_error = zeros(Cint, K)
+  steps_done = zeros(Int64, K)
+  check(ccall((:pdhg_fleet_take_steps_malitsky_pock, LIB), Cint,
+    (Ptr{Cvoid}, Ptr{Int64}, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Cint}, Ptr{Int64}),
+    fleet, n_steps, downscaling_factor, breaking_factor, interpolation_coefficient, step_size, ratio_step_sizes, primal_weight, total_number_iterations, cumulative_kkt_passes, numerical_error, steps_done))
   return numerical_error, steps_done
 end
 
