@@ -15,9 +15,9 @@ static void fleet_release(pdhg_handle *h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (pdhg_handle *m : F->mem) destroy_shard(m);
-  for (void *p : {(void *)F->args_dev, (void *)F->pow_dev})
+  for (void *p : {(void *)F->args_dev, (void *)F->qargs_dev, (void *)F->pow_dev})
     if (p) (void)hipFree(p);
-  for (void *p : {(void *)F->args_host, (void *)F->pow_host, (void *)F->chk_res})
+  for (void *p : {(void *)F->args_host, (void *)F->qargs_host, (void *)F->pow_host, (void *)F->chk_res})
     if (p) (void)hipHostFree(p);
   for (FleetState::Table &T : F->chk_table) {
     if (T.dev) (void)hipFree(T.dev);
@@ -72,7 +72,8 @@ int pdhg_fleet_add(pdhg_handle *fleet, int64_t m, int64_t n, int64_t nnz, const 
 }
 
 /* pdhg_take_steps_adaptive(member k, n_steps[k], ...) for every k, the small LPs among them in ONE launch: the members
- * that are small_lp_eligible and asked for at least 2 steps go into the shared launch (host_fleet.hpp); whatever that
+ * that are small_lp_eligible -- small QPs among them with PDHG_SMALL_QP=1, in launches of the QP kernels beside the LPs'
+ * -- and asked for at least 2 steps go into the shared launch (host_fleet.hpp); whatever that
  * launch left of a member -- its trial budget ran out, or its table of powers ended inside a take_step -- and every
  * other member is stepped by pdhg_take_steps_adaptive's own per-handle loop (abi_trial.hpp), in turn. */
 int pdhg_fleet_take_steps_adaptive(pdhg_handle *fleet, const int64_t *n_steps, double reduction_exponent,

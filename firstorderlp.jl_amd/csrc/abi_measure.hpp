@@ -397,6 +397,8 @@ int pdhg_layout_describe(pdhg_handle *h, char *buf, int cap) {
              mode_name[h->bnd[0].mode], (long long)h->bnd[0].nexc, mode_name[h->bnd[1].mode], (long long)h->bnd[1].nexc);
     out += b;
   }
+  // whole batches of steps in one workgroup (small_lp_kernel.hpp); a QP belongs to the class with PDHG_SMALL_QP=1 alone
+  out += std::string(", \"small_lp\": ") + (small_lp_eligible(h) ? (h->has_q ? "\"qp\"" : "\"lp\"") : "false");
   const char *tv = getenv("PDHG_TUNE");
   out += std::string(", \"row_order\": \"") + (h->relaxed ? "relaxed" : "strict") + "\", \"timing_at_create\": " + ((tv && tv[0] == '0') ? "false" : "true") + "}";
   if (buf && cap > 0) {

@@ -2,6 +2,8 @@
 // MANY independent small LPs in one launch (small_lp_fleet_kernel, small_lp_kernel.hpp): the fleet's state and the shared
 // launch (host side).  A solo small-LP launch is dim3(1): one of 256 compute units works.  A fleet's launch carries one
 // workgroup per member; the members share nothing on the device, so each takes its steps exactly as its solo launch would.
+// Small QPs (PDHG_SMALL_QP=1) ride in launches of their own kernels (small_qp_fleet_kernel) beside the LPs', from a table
+// of their own blocks (SmallQpArgs).
 //
 // Per-member host work of a shared launch: one argument block written into a pinned table (uploaded whole, once), no
 // pow() of its own -- the members' tables of powers are windows into ONE pair indexed by the absolute
@@ -11,6 +13,8 @@ struct FleetState {
   std::vector<pdhg_handle *> mem;                               // in order of addition; owned
   SmallLpArgs *args_dev = nullptr, *args_host = nullptr;        // the argument table: device copy, pinned staging
   size_t args_cap = 0;
+  SmallQpArgs *qargs_dev = nullptr, *qargs_host = nullptr;      // the same for the QP members (the QP form's block)
+  size_t qargs_cap = 0;
   double *pow_dev = nullptr, *pow_host = nullptr;               // [2 * pow_cap]: k1^-reduction_exponent, then k1^-growth_exponent
   size_t pow_cap = 0;
   int64_t launches = 0, last_carried = 0, last_single = 0;
@@ -96,7 +100,7 @@ struct FleetCarry {
   unsigned long long seq = 0;
 };
 
-int fleet_reserve(pdhg_handle *f, size_t members, size_t span) {
+int fleet_reserve(pdhg_handle *f, size_t members, size_t qp_members, size_t span) {
   FleetState &F = *f->fleet;
   if (F.args_cap < members) {
     HIP_TRY(hipStreamSynchronize(f->stream));
@@ -108,6 +112,17 @@ int fleet_reserve(pdhg_handle *f, size_t members, size_t span) {
     HIP_TRY(hipMalloc((void **)&F.args_dev, sizeof(SmallLpArgs) * cap));
     HIP_TRY(hipHostMalloc((void **)&F.args_host, sizeof(SmallLpArgs) * cap, hipHostMallocDefault));
     F.args_cap = cap;
+  }
+  if (F.qargs_cap < qp_members) {
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    if (F.qargs_dev) (void)hipFree(F.qargs_dev);
+    if (F.qargs_host) (void)hipHostFree(F.qargs_host);
+    F.qargs_dev = F.qargs_host = nullptr;
+    F.qargs_cap = 0;
+    const size_t cap = std::max<size_t>(2 * qp_members, 64);
+    HIP_TRY(hipMalloc((void **)&F.qargs_dev, sizeof(SmallQpArgs) * cap));
+    HIP_TRY(hipHostMalloc((void **)&F.qargs_host, sizeof(SmallQpArgs) * cap, hipHostMallocDefault));
+    F.qargs_cap = cap;
   }
   if (F.pow_cap < span) {
     HIP_TRY(hipStreamSynchronize(f->stream));
@@ -123,9 +138,90 @@ int fleet_reserve(pdhg_handle *f, size_t members, size_t span) {
   return 0;
 }
 
-// The shared launch of `carry` (every entry small_lp_eligible, n >= 2): at most two kernel launches back to back -- the
-// members of up to SMALL_FEW_ROWS rows and columns with 256 threads, the others with SMALL_TPB, the solo rule -- then one
-// wait per member.  On return every member's step state holds what small_lp_steps would have left in it.
+// The parts of a shared launch, in the order of the tables: the LP members in one table, the QP members in the other; in
+// each the members of up to SMALL_FEW_ROWS rows and columns (256 threads) before the others (SMALL_TPB), the solo rule;
+// each part by descending nnz, Q's entries counted (the long members start first, the tail is short).
+struct FleetParts {
+  size_t count[2][2] = {};     // [QP][SMALL_TPB threads]
+  size_t lds[2][2] = {};       // the largest member's dynamic LDS
+};
+static int64_t fleet_member_nnz(const pdhg_handle *h) { return h->nnz + (h->has_q ? h->Q.nnz : 0); }
+static size_t fleet_qp_members(const FleetState &F, const std::vector<FleetCarry> &carry) {
+  size_t k = 0;
+  for (const FleetCarry &c : carry) k += F.mem[(size_t)c.k]->has_q ? 1 : 0;
+  return k;
+}
+
+// Orders `carry` (every c.few set), writes every member's block -- stage(c, h): its SmallLpArgs, which takes the
+// member's next sequence number -- into the table of its kind, opts the kernels of `policy` in for the parts' LDS and
+// queues the upload of the tables.
+template <class Stage>
+int fleet_stage(pdhg_handle *f, std::vector<FleetCarry> &carry, int policy, FleetParts &P, Stage stage) {
+  FleetState &F = *f->fleet;
+  // Malitsky-Pock takes LPs only (pdhg.jl; the callers have refused the call already): before anything is staged
+  if (policy == SMALL_MALITSKY_POCK && fleet_qp_members(F, carry) > 0)
+    return fail(-2, "the one-workgroup kernel has no Malitsky-Pock form for QPs");
+  std::stable_sort(carry.begin(), carry.end(), [&](const FleetCarry &a, const FleetCarry &b) {
+    const pdhg_handle *ha = F.mem[(size_t)a.k], *hb = F.mem[(size_t)b.k];
+    if (ha->has_q != hb->has_q) return hb->has_q;
+    if (a.few != b.few) return a.few;
+    return fleet_member_nnz(ha) > fleet_member_nnz(hb);
+  });
+  size_t placed[2] = {0, 0};
+  for (FleetCarry &c : carry) {
+    pdhg_handle *h = F.mem[(size_t)c.k];
+    const int qp = h->has_q ? 1 : 0, big = c.few ? 0 : 1;
+    const SmallLpArgs a = stage(c, h);
+    c.seq = a.seq;
+    if (qp) F.qargs_host[placed[1]++] = small_qp_block(h, a);
+    else F.args_host[placed[0]++] = a;
+    P.count[qp][big] += 1;
+    P.lds[qp][big] = std::max(P.lds[qp][big], small_lp_lds_bytes(h));
+  }
+  int rc;
+  for (int qp = 0; qp < 2; ++qp)
+    if (placed[qp] > 0 && (rc = small_lp_lds_limit(f->device, policy, 1, std::max(P.lds[qp][0], P.lds[qp][1]), qp != 0))) return rc;
+  if (placed[0] > 0) HIP_TRY(hipMemcpyAsync(F.args_dev, F.args_host, sizeof(SmallLpArgs) * placed[0], hipMemcpyHostToDevice, f->stream));
+  if (placed[1] > 0) HIP_TRY(hipMemcpyAsync(F.qargs_dev, F.qargs_host, sizeof(SmallQpArgs) * placed[1], hipMemcpyHostToDevice, f->stream));
+  return 0;
+}
+
+// The launches of the staged parts, back to back: at most four (LP / QP x 256 / SMALL_TPB threads), each over its stretch
+// of its table.
+int fleet_launch_parts(pdhg_handle *f, int policy, const FleetParts &P) {
+  FleetState &F = *f->fleet;
+#define FLEET_GO(KERNEL, TABLE)                                                                                    \
+  do {                                                                                                             \
+    if (big) hipLaunchKernelGGL(KERNEL<SMALL_TPB>, dim3((unsigned)cnt), dim3(SMALL_TPB), lds, f->stream, TABLE, (int)cnt);   \
+    else hipLaunchKernelGGL(KERNEL<256>, dim3((unsigned)cnt), dim3(256), lds, f->stream, TABLE, (int)cnt);                   \
+  } while (0)
+  for (int qp = 0; qp < 2; ++qp) {
+    size_t first = 0;
+    for (int big = 0; big < 2; ++big) {
+      const size_t cnt = P.count[qp][big], lds = P.lds[qp][big];
+      if (cnt == 0) continue;
+      const SmallLpArgs *lp_table = F.args_dev + (qp ? 0 : first);
+      const SmallQpArgs *qp_table = F.qargs_dev + (qp ? first : 0);
+      if (qp) {
+        if (policy == SMALL_CONSTANT) FLEET_GO(small_qp_fleet_constant_kernel, qp_table);      // (fleet_stage admits no QP under Malitsky-Pock)
+        else FLEET_GO(small_qp_fleet_kernel, qp_table);
+      } else {
+        if (policy == SMALL_MALITSKY_POCK) FLEET_GO(small_fleet_malitsky_pock_kernel, lp_table);
+        else if (policy == SMALL_CONSTANT) FLEET_GO(small_fleet_constant_kernel, lp_table);
+        else FLEET_GO(small_lp_fleet_kernel, lp_table);
+      }
+      F.launches += 1;
+      first += cnt;
+    }
+  }
+#undef FLEET_GO
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The shared launch of `carry` (every entry small_lp_eligible, n >= 2): at most four kernel launches back to back
+// (FleetParts), then one wait per member.  On return every member's step state holds what small_lp_steps would have left
+// in it.
 int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry) {
   FleetState &F = *f->fleet;
   if (carry.empty()) return 0;
@@ -145,7 +241,7 @@ int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry) {
     hi = std::max(hi, c.k1_first + c.table_len);          // one past the last
   }
   const size_t span = (size_t)(hi - lo);
-  if ((rc = fleet_reserve(f, carry.size(), span))) return rc;
+  if ((rc = fleet_reserve(f, carry.size(), fleet_qp_members(F, carry), span))) return rc;
   {
     // every entry a member can read is the host pow() steps_prepare computes; entries no member covers stay as they are
     std::vector<std::pair<int64_t, int64_t>> iv;
@@ -161,36 +257,13 @@ int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry) {
     }
     HIP_TRY(hipMemcpyAsync(F.pow_dev, F.pow_host, sizeof(double) * 2 * span, hipMemcpyHostToDevice, f->stream));
   }
-  // launch order: the 256-thread members first, each part by descending nnz (the long members start first, the tail is short)
-  std::stable_sort(carry.begin(), carry.end(), [&](const FleetCarry &a, const FleetCarry &b) {
-    if (a.few != b.few) return a.few;
-    return F.mem[(size_t)a.k]->nnz > F.mem[(size_t)b.k]->nnz;
-  });
-  size_t n_few = 0, lds_few = 0, lds_big = 0;
-  for (size_t i = 0; i < carry.size(); ++i) {
-    FleetCarry &c = carry[i];
-    pdhg_handle *h = F.mem[(size_t)c.k];
-    const size_t off = (size_t)(c.k1_first - lo);
-    F.args_host[i] = small_lp_stage(h, c.n, c.max_trials, c.table_len, c.io->step_size, c.io->primal_weight, F.pow_dev + off,
-                                    F.pow_dev + span + off);
-    c.seq = F.args_host[i].seq;
-    if (c.few) { n_few += 1; lds_few = std::max(lds_few, small_lp_lds_bytes(h)); }
-    else lds_big = std::max(lds_big, small_lp_lds_bytes(h));
-  }
-  if ((rc = small_lp_lds_limit(f->device, SMALL_ADAPTIVE, 1, std::max(lds_few, lds_big)))) return rc;
-  HIP_TRY(hipMemcpyAsync(F.args_dev, F.args_host, sizeof(SmallLpArgs) * carry.size(), hipMemcpyHostToDevice, f->stream));
-  const size_t n_big = carry.size() - n_few;
-  if (n_few > 0) {
-    hipLaunchKernelGGL(small_lp_fleet_kernel<256>, dim3((unsigned)n_few), dim3(256), lds_few, f->stream,
-                       (const SmallLpArgs *)F.args_dev, (int)n_few);
-    F.launches += 1;
-  }
-  if (n_big > 0) {
-    hipLaunchKernelGGL(small_lp_fleet_kernel<SMALL_TPB>, dim3((unsigned)n_big), dim3(SMALL_TPB), lds_big, f->stream,
-                       (const SmallLpArgs *)(F.args_dev + n_few), (int)n_big);
-    F.launches += 1;
-  }
-  HIP_TRY(hipGetLastError());
+  FleetParts P;
+  if ((rc = fleet_stage(f, carry, SMALL_ADAPTIVE, P, [&](const FleetCarry &c, pdhg_handle *h) {
+         const size_t off = (size_t)(c.k1_first - lo);
+         return small_lp_stage(h, c.n, c.max_trials, c.table_len, c.io->step_size, c.io->primal_weight, F.pow_dev + off,
+                               F.pow_dev + span + off);
+       }))) return rc;
+  if ((rc = fleet_launch_parts(f, SMALL_ADAPTIVE, P))) return rc;
   for (const FleetCarry &c : carry)
     if ((rc = small_lp_collect(F.mem[(size_t)c.k], c.seq, *c.io))) return rc;
   return 0;
@@ -210,37 +283,11 @@ int fleet_policy_launch(pdhg_handle *f, std::vector<FleetCarry> &carry) {
     if ((rc = steps_result_words(h))) return rc;
     c.few = small_lp_few_rows(h);
   }
-  if ((rc = fleet_reserve(f, carry.size(), 0))) return rc;
-  std::stable_sort(carry.begin(), carry.end(), [&](const FleetCarry &a, const FleetCarry &b) {
-    if (a.few != b.few) return a.few;
-    return F.mem[(size_t)a.k]->nnz > F.mem[(size_t)b.k]->nnz;
-  });
-  size_t n_few = 0, lds_few = 0, lds_big = 0;
-  for (size_t i = 0; i < carry.size(); ++i) {
-    FleetCarry &c = carry[i];
-    pdhg_handle *h = F.mem[(size_t)c.k];
-    F.args_host[i] = small_policy_stage(h, c.n, *c.pio);
-    c.seq = F.args_host[i].seq;
-    if (c.few) { n_few += 1; lds_few = std::max(lds_few, small_lp_lds_bytes(h)); }
-    else lds_big = std::max(lds_big, small_lp_lds_bytes(h));
-  }
-  if ((rc = small_lp_lds_limit(f->device, policy, 1, std::max(lds_few, lds_big)))) return rc;
-  HIP_TRY(hipMemcpyAsync(F.args_dev, F.args_host, sizeof(SmallLpArgs) * carry.size(), hipMemcpyHostToDevice, f->stream));
-  const size_t n_big = carry.size() - n_few;
-  const SmallLpArgs *few_table = F.args_dev, *big_table = F.args_dev + n_few;
-  if (n_few > 0) {
-    if (policy == SMALL_MALITSKY_POCK)
-      hipLaunchKernelGGL(small_fleet_malitsky_pock_kernel<256>, dim3((unsigned)n_few), dim3(256), lds_few, f->stream, few_table, (int)n_few);
-    else hipLaunchKernelGGL(small_fleet_constant_kernel<256>, dim3((unsigned)n_few), dim3(256), lds_few, f->stream, few_table, (int)n_few);
-    F.launches += 1;
-  }
-  if (n_big > 0) {
-    if (policy == SMALL_MALITSKY_POCK)
-      hipLaunchKernelGGL(small_fleet_malitsky_pock_kernel<SMALL_TPB>, dim3((unsigned)n_big), dim3(SMALL_TPB), lds_big, f->stream, big_table, (int)n_big);
-    else hipLaunchKernelGGL(small_fleet_constant_kernel<SMALL_TPB>, dim3((unsigned)n_big), dim3(SMALL_TPB), lds_big, f->stream, big_table, (int)n_big);
-    F.launches += 1;
-  }
-  HIP_TRY(hipGetLastError());
+  if ((rc = fleet_reserve(f, carry.size(), fleet_qp_members(F, carry), 0))) return rc;
+  FleetParts P;
+  if ((rc = fleet_stage(f, carry, policy, P, [&](const FleetCarry &c, pdhg_handle *h) { return small_policy_stage(h, c.n, *c.pio); })))
+    return rc;
+  if ((rc = fleet_launch_parts(f, policy, P))) return rc;
   for (const FleetCarry &c : carry)
     if ((rc = small_policy_collect(F.mem[(size_t)c.k], c.seq, *c.pio))) return rc;
   return 0;

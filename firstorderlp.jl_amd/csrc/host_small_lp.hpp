@@ -3,13 +3,21 @@
 
 // ---- small LPs: a batch of take_steps in one workgroup, vectors in LDS (small_lp_kernel.hpp) ---------------------
 int flush_pending(const Shards &L);
+// LDS of a launch: nine n-vectors and four m-vectors; a QP keeps Q x and x' - x as well
+size_t small_lp_lds_bytes(const pdhg_handle *h) { return sizeof(double) * ((h->has_q ? 11 : 9) * (size_t)h->n + 4 * (size_t)h->m); }
+
+// A QP (PDHG_SMALL_QP=1; off by default) belongs to the class when both copies of Q suit the kernel as A and A' must:
+// row sums of at most SMALL_MAX_ROW entries, plain row blocks.  PDHG_SMALL_LP=0 switches the whole class off.
 bool small_lp_eligible(pdhg_handle *h) {
   if (h->small_lp_mode < 0) {
-    const char *ev = getenv("PDHG_SMALL_LP");
-    const size_t lds = sizeof(double) * (9 * (size_t)h->n + 4 * (size_t)h->m);
-    bool on = !h->grp && !h->has_q && h->n > 0 && h->m > 0 && h->A.segs.empty() && h->At.segs.empty() && !h->A.tiled && !h->At.tiled && h->A.slabs.empty() &&
+    const char *ev = getenv("PDHG_SMALL_LP"), *qv = getenv("PDHG_SMALL_QP");
+    const size_t lds = small_lp_lds_bytes(h);
+    bool on = !h->grp && h->n > 0 && h->m > 0 && h->A.segs.empty() && h->At.segs.empty() && !h->A.tiled && !h->At.tiled && h->A.slabs.empty() &&
               h->At.slabs.empty() && h->A.max_row_nnz <= SMALL_MAX_ROW && h->At.max_row_nnz <= SMALL_MAX_ROW &&
               lds <= (size_t)144 * 1024;
+    if (h->has_q)
+      on = on && qv && qv[0] == '1' && h->Q.segs.empty() && h->Qt.segs.empty() && !h->Q.tiled && !h->Qt.tiled && h->Q.slabs.empty() &&
+           h->Qt.slabs.empty() && h->Q.max_row_nnz <= SMALL_MAX_ROW && h->Qt.max_row_nnz <= SMALL_MAX_ROW;
     if (ev) on = on && ev[0] != '0';
     h->small_lp_mode = on ? 1 : 0;
   }
@@ -18,33 +26,35 @@ bool small_lp_eligible(pdhg_handle *h) {
 
 // The opt-in for the launch's dynamic LDS (beyond 64 KiB), per device and kernel instance; it only ever grows
 // (ensure_lds_limit's reasoning).  `policy`: SMALL_ADAPTIVE / _CONSTANT / _MALITSKY_POCK; `which`: 0 the solo
-// instantiations, 1 the fleet's.
-int small_lp_lds_limit(int device, int policy, int which, size_t lds) {
-  static size_t limit[64][3][2] = {};
+// instantiations, 1 the fleet's; `qp`: the QP form's kernels.
+int small_lp_lds_limit(int device, int policy, int which, size_t lds, bool qp = false) {
+  static size_t limit[64][3][2][2] = {};
   static std::mutex mu;
   std::lock_guard<std::mutex> lock(mu);
-  size_t &cur = limit[device & 63][policy][which];
+  size_t &cur = limit[device & 63][policy][which][qp ? 1 : 0];
   if (cur < lds) {
 #define SMALL_LDS_OPT_IN(KERNEL)                                                                                               \
   do {                                                                                                                         \
     HIP_TRY(hipFuncSetAttribute((const void *)KERNEL<SMALL_TPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
     HIP_TRY(hipFuncSetAttribute((const void *)KERNEL<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));              \
   } while (0)
-    switch (policy * 2 + which) {
-      case SMALL_ADAPTIVE * 2 + 0: SMALL_LDS_OPT_IN(small_lp_steps_kernel); break;
-      case SMALL_ADAPTIVE * 2 + 1: SMALL_LDS_OPT_IN(small_lp_fleet_kernel); break;
-      case SMALL_CONSTANT * 2 + 0: SMALL_LDS_OPT_IN(small_lp_constant_kernel); break;
-      case SMALL_CONSTANT * 2 + 1: SMALL_LDS_OPT_IN(small_fleet_constant_kernel); break;
-      case SMALL_MALITSKY_POCK * 2 + 0: SMALL_LDS_OPT_IN(small_lp_malitsky_pock_kernel); break;
-      default: SMALL_LDS_OPT_IN(small_fleet_malitsky_pock_kernel); break;
+    switch ((policy * 2 + which) * 2 + (qp ? 1 : 0)) {
+      case (SMALL_ADAPTIVE * 2 + 0) * 2: SMALL_LDS_OPT_IN(small_lp_steps_kernel); break;
+      case (SMALL_ADAPTIVE * 2 + 1) * 2: SMALL_LDS_OPT_IN(small_lp_fleet_kernel); break;
+      case (SMALL_CONSTANT * 2 + 0) * 2: SMALL_LDS_OPT_IN(small_lp_constant_kernel); break;
+      case (SMALL_CONSTANT * 2 + 1) * 2: SMALL_LDS_OPT_IN(small_fleet_constant_kernel); break;
+      case (SMALL_MALITSKY_POCK * 2 + 0) * 2: SMALL_LDS_OPT_IN(small_lp_malitsky_pock_kernel); break;
+      case (SMALL_MALITSKY_POCK * 2 + 1) * 2: SMALL_LDS_OPT_IN(small_fleet_malitsky_pock_kernel); break;
+      case (SMALL_ADAPTIVE * 2 + 0) * 2 + 1: SMALL_LDS_OPT_IN(small_qp_steps_kernel); break;
+      case (SMALL_ADAPTIVE * 2 + 1) * 2 + 1: SMALL_LDS_OPT_IN(small_qp_fleet_kernel); break;
+      case (SMALL_CONSTANT * 2 + 0) * 2 + 1: SMALL_LDS_OPT_IN(small_qp_constant_kernel); break;
+      default: SMALL_LDS_OPT_IN(small_qp_fleet_constant_kernel); break;      // (no QP reaches here under Malitsky-Pock: policy_handle_check, fleet_stage)
     }
 #undef SMALL_LDS_OPT_IN
     cur = lds;
   }
   return 0;
 }
-
-size_t small_lp_lds_bytes(const pdhg_handle *h) { return sizeof(double) * (9 * (size_t)h->n + 4 * (size_t)h->m); }
 
 // 256 threads up to this many rows / columns, SMALL_TPB beyond (small_lp_kernel.hpp)
 bool small_lp_few_rows(const pdhg_handle *h) {
@@ -72,6 +82,14 @@ SmallLpArgs small_lp_stage(pdhg_handle *h, int n, int max_trials, int table_len,
   return a;
 }
 
+// The QP form's block of a staged launch: the same fields and both copies of the objective matrix
+SmallQpArgs small_qp_block(const pdhg_handle *h, const SmallLpArgs &a) {
+  SmallQpArgs q{};
+  static_cast<SmallLpArgs &>(q) = a;
+  q.Q = h->Q.view(); q.Qt = h->Qt.view();
+  return q;
+}
+
 // Wait for launch `seq` of h and take its results into the handle's bookkeeping and the step state (steps_collect).
 int small_lp_collect(pdhg_handle *h, unsigned long long seq, StepIO &io) {
   double r[STEPS_RES_K];
@@ -91,11 +109,15 @@ int small_lp_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   int max_trials = 0, table_len = 0;
   if ((rc = steps_prepare(h, n, io, &max_trials, &table_len))) return rc;
   const size_t lds = small_lp_lds_bytes(h);
-  if ((rc = small_lp_lds_limit(h->device, SMALL_ADAPTIVE, 0, lds))) return rc;
+  if ((rc = small_lp_lds_limit(h->device, SMALL_ADAPTIVE, 0, lds, h->has_q))) return rc;
   const SmallLpArgs a = small_lp_stage(h, n, max_trials, table_len, io.step_size, io.primal_weight, h->steps_pow_dev,
                                        h->steps_pow_dev + table_len);
   const auto c1 = std::chrono::steady_clock::now();
-  if (small_lp_few_rows(h)) hipLaunchKernelGGL(small_lp_steps_kernel<256>, dim3(1), dim3(256), lds, h->stream, a);
+  if (h->has_q) {
+    const SmallQpArgs q = small_qp_block(h, a);
+    if (small_lp_few_rows(h)) hipLaunchKernelGGL(small_qp_steps_kernel<256>, dim3(1), dim3(256), lds, h->stream, q);
+    else hipLaunchKernelGGL(small_qp_steps_kernel<SMALL_TPB>, dim3(1), dim3(SMALL_TPB), lds, h->stream, q);
+  } else if (small_lp_few_rows(h)) hipLaunchKernelGGL(small_lp_steps_kernel<256>, dim3(1), dim3(256), lds, h->stream, a);
   else hipLaunchKernelGGL(small_lp_steps_kernel<SMALL_TPB>, dim3(1), dim3(SMALL_TPB), lds, h->stream, a);
   HIP_TRY(hipGetLastError());
   const auto c2 = std::chrono::steady_clock::now();
@@ -160,11 +182,15 @@ int small_policy_steps(pdhg_handle *h, int64_t n_steps, PolicyIO &io) {
   if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
   if ((rc = steps_result_words(h))) return rc;
   const size_t lds = small_lp_lds_bytes(h);
-  if ((rc = small_lp_lds_limit(h->device, io.policy, 0, lds))) return rc;
+  if ((rc = small_lp_lds_limit(h->device, io.policy, 0, lds, h->has_q))) return rc;
   const SmallLpArgs a = small_policy_stage(h, small_policy_launch_steps(io.policy, n_steps), io);
   const bool few = small_lp_few_rows(h);
   const auto c1 = std::chrono::steady_clock::now();
-  if (io.policy == SMALL_MALITSKY_POCK) {
+  if (h->has_q) {                           // (the constant policy: Malitsky-Pock has refused the handle, policy_handle_check)
+    const SmallQpArgs q = small_qp_block(h, a);
+    if (few) hipLaunchKernelGGL(small_qp_constant_kernel<256>, dim3(1), dim3(256), lds, h->stream, q);
+    else hipLaunchKernelGGL(small_qp_constant_kernel<SMALL_TPB>, dim3(1), dim3(SMALL_TPB), lds, h->stream, q);
+  } else if (io.policy == SMALL_MALITSKY_POCK) {
     if (few) hipLaunchKernelGGL(small_lp_malitsky_pock_kernel<256>, dim3(1), dim3(256), lds, h->stream, a);
     else hipLaunchKernelGGL(small_lp_malitsky_pock_kernel<SMALL_TPB>, dim3(1), dim3(SMALL_TPB), lds, h->stream, a);
   } else {

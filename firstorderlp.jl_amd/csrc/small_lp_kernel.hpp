@@ -24,7 +24,20 @@
 // size on entry, then up to 60 dual trials (xbar with the ratio as extrapolation coefficient, the dual half, A'y', two
 // double-double sums, malitsky_pock_rule on thread 0).  Their launches end between take_steps only.
 // tests/test_gpu_step_policies.py: bitwise against the host loops in C and in Python, and against the oracle.
+//
+// SMALL QPs (PDHG_SMALL_QP=1; MPC horizons, QP nodes of a branch and bound): the same body in its QP form, a third template
+// argument, behind kernels of their own names (small_qp_*; the LP instantiations above keep theirs and compile to what
+// they were).  A QP step is the LP step plus Q x in the gradient, Q' dx and one more double-double sum
+// (pdhg.jl:536-541, saddle_point.jl:1093-1100; launch_primal / launch_q_interaction on the per-launch path): two more
+// n-vectors in LDS (qx, dx: 11n + 4m doubles), Q and Q' streamed row by row like A and A'.  qx = Q x is computed at the
+// start of the launch and after every accept (x does not move on a rejection, so the per-launch path's product of every
+// trial has the same bits); dx . (Q' dx) does not depend on y' and rides on the dual phase, reduced together with dy^2
+// (two quantities there, three in the A'y' phase: block_sum_dd holds three).  The constant policy needs qx alone;
+// Malitsky-Pock refuses QPs (pdhg.jl, policy_handle_check).  tests/test_gpu_small_qp.py: bitwise against one launch per
+// trial and against the oracle.
 #pragma once
+
+#include <type_traits>
 
 namespace {
 
@@ -50,6 +63,12 @@ struct SmallLpArgs {
   double ratio, downscaling_factor, breaking_factor, interpolation_coefficient;
 };
 
+// The QP form's block: the LP fields and both copies of the objective matrix.  (A block of its own: the LP kernels'
+// argument segment and their fleet table's stride stay what they were.)
+struct SmallQpArgs : SmallLpArgs {
+  CsrView Q, Qt;                          // CSR(Q), CSR(Q') (n rows each)
+};
+
 // one row's sum: products added strictly left to right, eight entries requested at a time
 __device__ __forceinline__ double small_row_sum(const CsrView &M, int r, const double *xs) {
   int k = M.rowptr[r];
@@ -69,8 +88,9 @@ __device__ __forceinline__ double small_row_sum(const CsrView &M, int r, const d
 
 // The whole launch of one LP: what a workgroup does with one argument block, whoever handed it over -- the solo kernel
 // (the block by value) or the fleet kernel (its entry of a table in device memory).
-template <int THREADS, int POLICY = SMALL_ADAPTIVE>
-__device__ __forceinline__ void small_lp_steps_body(const SmallLpArgs &a) {
+template <int THREADS, int POLICY = SMALL_ADAPTIVE, bool QP = false>
+__device__ __forceinline__ void small_lp_steps_body(const std::conditional_t<QP, SmallQpArgs, SmallLpArgs> &a) {
+  static_assert(!(QP && POLICY == SMALL_MALITSKY_POCK), "Malitsky and Pock linesearch is only supported for LPs");
   extern __shared__ double lds[];
   __shared__ double red[6][THREADS / WAVE];
   __shared__ double s_dec[3];
@@ -79,6 +99,7 @@ __device__ __forceinline__ void small_lp_steps_body(const SmallLpArgs &a) {
   double *xs = lds, *xn = xs + n, *xb = xn + n, *at = xb + n, *atn = at + n;
   double *cs = atn + n, *lbs = cs + n, *ubs = lbs + n, *sx = ubs + n;
   double *ys = sx + n, *yn = ys + m, *bs = yn + m, *sy = bs + m;
+  [[maybe_unused]] double *qx = sy + m, *dxs = qx + n;       // QP form alone: Q x of the iterate, x' - x of the trial
   for (int j = tid; j < n; j += THREADS) {
     xs[j] = a.x[j]; at[j] = a.aty[j]; cs[j] = a.c[j]; lbs[j] = a.lb[j]; ubs[j] = a.ub[j]; sx[j] = a.sum_x[j];
   }
@@ -92,6 +113,10 @@ __device__ __forceinline__ void small_lp_steps_body(const SmallLpArgs &a) {
     for (int j = tid; j < n; j += THREADS) { const double t = xs[j] * a.pend_w; sx[j] = sx[j] + t; }
     for (int r = tid; r < m; r += THREADS) { const double t = ys[r] * a.pend_w; sy[r] = sy[r] + t; }
   }
+  if constexpr (QP) {                     // qx = Q x (launch_primal's product): one thread per row, left to right
+    for (int j = tid; j < n; j += THREADS) qx[j] = small_row_sum(a.Q, j, xs);
+    __syncthreads();
+  }
   int steps = 0, trials = 0, num_err = 0, mid = 0;
   if constexpr (POLICY == SMALL_ADAPTIVE) {
     while (steps < a.n_steps && (trials < a.max_trials || mid) && trials < a.table_len) {
@@ -102,12 +127,23 @@ __device__ __forceinline__ void small_lp_steps_body(const SmallLpArgs &a) {
       // ---- K1 + K2: x' = proj(x - tau (c - A'y)), xbar = x' + (x' - x)        (primal_one, vector_kernels.hpp)
       for (int j = tid; j < n; j += THREADS) {
         double v, b2;
-        primal_one<false, true>(xs[j], cs[j], at[j], 0.0, lbs[j], ubs[j], tau, 1.0, v, b2);
+        if constexpr (QP) {
+          primal_one<true, true>(xs[j], cs[j], at[j], qx[j], lbs[j], ubs[j], tau, 1.0, v, b2);
+          dxs[j] = v - xs[j];                         // (diff_body)
+        } else {
+          primal_one<false, true>(xs[j], cs[j], at[j], 0.0, lbs[j], ubs[j], tau, 1.0, v, b2);
+        }
         xn[j] = v; xb[j] = b2;
       }
       __syncthreads();
       // ---- K3 + K4: y' = proj(y + sigma (b - A xbar)), sum dy^2                 (row_epilogue<MODE_DUAL>)
       Acc3 acc = acc3_zero();
+      if constexpr (QP) {                             // dx . (Q' dx): launch_q_interaction's product and dot_body's sum
+        for (int j = tid; j < n; j += THREADS) {
+          const double s = small_row_sum(a.Qt, j, dxs);
+          dd_add(acc.hi[1], acc.lo[1], s * dxs[j]);
+        }
+      }
       for (int r = tid; r < m; r += THREADS) {
         const double s = small_row_sum(a.A, r, xb);
         const double yo = ys[r];
@@ -119,8 +155,9 @@ __device__ __forceinline__ void small_lp_steps_body(const SmallLpArgs &a) {
         const double dy = v - yo;
         dd_add(acc.hi[0], acc.lo[0], dy * dy);
       }
-      block_sum_dd<1, THREADS>(acc, red);          // (ends with the totals on thread 0; a barrier inside)
+      block_sum_dd<QP ? 2 : 1, THREADS>(acc, red);  // (ends with the totals on thread 0; a barrier inside)
       const double dy2 = acc.hi[0] + acc.lo[0];
+      [[maybe_unused]] const double dxqdx = acc.hi[1] + acc.lo[1];
       __syncthreads();
       // ---- K5 + K6: A'y' and the interaction sums                                  (row_epilogue<MODE_ATY>)
       Acc3 acc3 = acc3_zero();
@@ -137,7 +174,7 @@ __device__ __forceinline__ void small_lp_steps_body(const SmallLpArgs &a) {
       if (tid == 0) {
         double raw[5];
         raw[0] = acc3.hi[0] + acc3.lo[0]; raw[1] = acc3.hi[1] + acc3.lo[1]; raw[2] = dy2; raw[3] = acc3.hi[2] + acc3.lo[2];
-        raw[4] = 0.0;
+        raw[4] = QP ? 0.5 * dxqdx : 0.0;
         const StepRule rule = adaptive_step_rule(raw, a.primal_weight, step, pw_r, pw_g);
         s_dec[0] = (double)rule.accept; s_dec[1] = (double)rule.numerical_error; s_dec[2] = rule.next_step;
       }
@@ -156,6 +193,9 @@ __device__ __forceinline__ void small_lp_steps_body(const SmallLpArgs &a) {
         const double wgt = s_st[1];
         for (int j = tid; j < n; j += THREADS) { const double t = xs[j] * wgt; sx[j] = sx[j] + t; }
         for (int r = tid; r < m; r += THREADS) { const double t = ys[r] * wgt; sy[r] = sy[r] + t; }
+        if constexpr (QP) {                           // Q x of the new iterate (every thread has finished reading xn)
+          for (int j = tid; j < n; j += THREADS) qx[j] = small_row_sum(a.Q, j, xs);
+        }
         steps += 1;
       }
       __syncthreads();
@@ -181,7 +221,8 @@ __device__ __forceinline__ void small_lp_steps_body(const SmallLpArgs &a) {
     for (; steps < a.n_steps; ++steps) {
       for (int j = tid; j < n; j += THREADS) {
         double v, b2;
-        primal_one<false, true>(xs[j], cs[j], at[j], 0.0, lbs[j], ubs[j], tau, 1.0, v, b2);
+        if constexpr (QP) primal_one<true, true>(xs[j], cs[j], at[j], qx[j], lbs[j], ubs[j], tau, 1.0, v, b2);
+        else primal_one<false, true>(xs[j], cs[j], at[j], 0.0, lbs[j], ubs[j], tau, 1.0, v, b2);
         xn[j] = v; xb[j] = b2;
       }
       __syncthreads();
@@ -200,6 +241,7 @@ __device__ __forceinline__ void small_lp_steps_body(const SmallLpArgs &a) {
         atn[j] = small_row_sum(a.T, j, yn);
         const double w = xn[j] * step;
         sx[j] = sx[j] + w;
+        if constexpr (QP) qx[j] = small_row_sum(a.Q, j, xn);      // Q x of the next iterate (x' is whole since the first barrier)
       }
       double *t0 = xs; xs = xn; xn = t0;
       double *t1 = ys; ys = yn; yn = t1;
@@ -332,6 +374,29 @@ __global__ __launch_bounds__(THREADS) void small_fleet_malitsky_pock_kernel(cons
   if ((int)blockIdx.x >= count) return;
   const SmallLpArgs a = table[blockIdx.x];
   small_lp_steps_body<THREADS, SMALL_MALITSKY_POCK>(a);
+}
+
+// The QP form (PDHG_SMALL_QP=1): the same body behind kernels of their own names, solo and fleet, for the adaptive and
+// the constant policy.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void small_qp_steps_kernel(SmallQpArgs a) {
+  small_lp_steps_body<THREADS, SMALL_ADAPTIVE, true>(a);
+}
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void small_qp_fleet_kernel(const SmallQpArgs *__restrict__ table, int count) {
+  if ((int)blockIdx.x >= count) return;
+  const SmallQpArgs a = table[blockIdx.x];
+  small_lp_steps_body<THREADS, SMALL_ADAPTIVE, true>(a);
+}
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void small_qp_constant_kernel(SmallQpArgs a) {
+  small_lp_steps_body<THREADS, SMALL_CONSTANT, true>(a);
+}
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void small_qp_fleet_constant_kernel(const SmallQpArgs *__restrict__ table, int count) {
+  if ((int)blockIdx.x >= count) return;
+  const SmallQpArgs a = table[blockIdx.x];
+  small_lp_steps_body<THREADS, SMALL_CONSTANT, true>(a);
 }
 
 }  // namespace

@@ -4,7 +4,10 @@
 share nothing -- any mix of shapes, LPs and QPs.  What they share is the launch: an LP small enough for the solo
 small-LP path (csrc/small_lp_kernel.hpp: every vector in one workgroup's LDS) takes its steps between two evaluations in
 one workgroup, and ``pdhg_fleet_take_steps_adaptive`` (``_constant`` / ``_malitsky_pock`` under the two other policies)
-carries one such workgroup per problem in one launch instead of one launch per problem on one of 256 compute units.  The members do not run in lockstep: each accepts, rejects, restarts and
+carries one such workgroup per problem in one launch instead of one launch per problem on one of 256 compute units.
+With ``PDHG_SMALL_QP=1`` in the environment (off by default) a small QP -- ``11n + 4m`` doubles of LDS, rows of ``Q`` and
+``Q'`` of at most 256 entries -- belongs to that class too and rides in launches of the QP kernels beside the LPs'; without
+it a QP member is stepped by its own launches inside the same call.  The members do not run in lockstep: each accepts, rejects, restarts and
 terminates on its own, at the iterations ``optimize`` would.  Both drivers run the same per-problem solve object
 (``primal_dual_hybrid_gradient._Solve``).  The checks between the steps go the same way: a fleet with ``eval_points`` and
 ``trust_region_bounds`` gets the device requests of every member's check -- the termination evaluation, the
@@ -223,7 +226,9 @@ def optimize_many(params, problems, fleet_factory=None):
     """``optimize(params, problems[k])`` for every k, side by side: a list of ``SaddlePointOutput`` in input order.
 
     Anything ``optimize`` accepts: any mix of shapes, LPs and QPs, every step-size policy, any number of problems (an
-    empty list raises ``ValueError`` before any device work).  ``fleet_factory(problems) -> fleet`` builds the device
+    empty list raises ``ValueError`` before any device work).  Small LPs share the launches of their steps; small QPs do
+    with ``PDHG_SMALL_QP=1`` in the environment (the library partitions the members: no argument here), and are stepped
+    member by member otherwise -- the results are the same bits either way.  ``fleet_factory(problems) -> fleet`` builds the device
     side (default ``HipPdhgFleet``): an object with ``.members`` (one engine per problem, in order), ``close()`` and,
     optionally, ``take_steps_adaptive`` / ``take_steps_constant`` / ``take_steps_malitsky_pock`` and the pair
     ``eval_points`` / ``trust_region_bounds`` (the checks in shared launches); a factory whose

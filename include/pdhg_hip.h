@@ -20,7 +20,7 @@
  *  - fp64 throughout; kernels are built with -ffp-contract=off so elementwise
  *    updates round exactly like the reference's unfused Julia broadcasts.
  *
- * Environment variables (read when a handle is created unless noted).  These 27 are the
+ * Environment variables (read when a handle is created unless noted).  These 28 are the
  * library's run-time knobs; every other PDHG_* name in the sources is a development
  * variable (tuning constants, negative-result paths, fault injection) and is IGNORED unless
  * PDHG_DEV=1 is set as well (tests/conftest.py and tools/ set it).
@@ -45,6 +45,11 @@
  *   PDHG_COOP            1 | 0                         one persistent kernel per trial (csrc/trial_kernel.hpp)
  *   PDHG_DEVICE_LOOP     1 | 0                         several take_steps per launch of the persistent kernel
  *   PDHG_SMALL_LP        1 | 0                         whole batches of steps in one workgroup (csrc/small_lp_kernel.hpp)
+ *   PDHG_SMALL_QP        0 | 1                         small QPs in that class too (Q and Q' of rows <= 256 entries, 11 n + 4 m doubles
+ *                                                      <= 144 KiB): solo, and in a fleet's shared launches beside the LPs.  Read when the
+ *                                                      class of a handle is decided (first batch of steps, pdhg_layout_info, after
+ *                                                      pdhg_set_objective_matrix), where PDHG_SMALL_LP is read; PDHG_SMALL_LP=0 switches
+ *                                                      the whole class off.  Same bits either way
  *   PDHG_TR_COOP         1 | 0                         a trust-region search as one persistent launch
  *   PDHG_COOP_TRACE      0 | 1                         phase-boundary clock stamps in the persistent kernels (pdhg_trial_timeline)
  *   PDHG_RCCL_LIB        (unset) | <path>              the RCCL library to bind at run time
@@ -469,7 +474,9 @@ int pdhg_layout_info(pdhg_handle *h, int64_t info[16]);
  * this text to say which variant it ran.  "bounds": how primal_kernel reads lb / ub on this handle --
  * {"lb": {"mode": "const" | "sparse" | "dense", "exceptions": k}, "ub": ...}: one bit pattern and nothing read, a
  * default plus k exceptions (at most n / 4), or the arrays (k = 0); derived from the arrays whenever they are written
- * (create, pdhg_rescale), the same bits in every mode.  Writes at most cap - 1 characters + NUL into buf (buf may be
+ * (create, pdhg_rescale), the same bits in every mode.  "small_lp": whether batches of steps run in the one-workgroup
+ * kernel on this handle (pdhg_layout_info's small_lp bit) -- "lp", "qp" (a QP of the class, with PDHG_SMALL_QP=1 alone)
+ * or false; present for every handle.  Writes at most cap - 1 characters + NUL into buf (buf may be
  * NULL); returns the full length of the text, or < 0 on error.  (abi 11) */
 int pdhg_layout_describe(pdhg_handle *h, char *buf, int cap);
 /* Diagnostics: order-sensitive 64-bit checksums of every device array of the two layouts
