@@ -38,7 +38,7 @@ EXPORTS = [
     "pdhg_partition_rows", "pdhg_create_dist_rows", "pdhg_rccl_info", "pdhg_host_issue_stats",
     "pdhg_measure_launch_overhead", "pdhg_selftest_wave_sums", "pdhg_layout_checksums",
     "pdhg_create_batch", "pdhg_batch_member", "pdhg_batch_trial_step", "pdhg_batch_accept",
-    "pdhg_batch_take_steps_adaptive",
+    "pdhg_batch_take_steps_adaptive", "pdhg_batch_set_objective_matrix",
     "pdhg_create_fleet", "pdhg_fleet_add", "pdhg_fleet_take_steps_adaptive", "pdhg_fleet_info",
     "pdhg_fleet_eval_points", "pdhg_fleet_trust_region_bounds",
     "pdhg_take_steps_constant", "pdhg_take_steps_malitsky_pock", "pdhg_steps_info",
@@ -225,6 +225,8 @@ def lib():
                                     i32, _vp]
     L.pdhg_batch_member.restype = i32
     L.pdhg_batch_member.argtypes = [_vp, i32, ctypes.POINTER(_vp)]
+    L.pdhg_batch_set_objective_matrix.restype = i32
+    L.pdhg_batch_set_objective_matrix.argtypes = [_vp, i64, _ip, _ip, _dp, i32]
     L.pdhg_batch_trial_step.restype = i32
     L.pdhg_batch_trial_step.argtypes = [_vp, _dp, _dp, d, _int_p, _dp]
     L.pdhg_batch_accept.restype = i32

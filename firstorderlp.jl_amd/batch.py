@@ -1,14 +1,15 @@
-"""Batched PDHG solves of LPs that share one constraint matrix.
+"""Batched PDHG solves of LPs, or of QPs that share the objective matrix as well, over one constraint matrix.
 
 ``optimize_batch(params, problems)`` returns what ``optimize(params, problems[k])`` returns, for every k, while the
 batch reads the matrix once per trial for all members (``pdhg_batch_trial_step``: member-interleaved iterates,
-csrc/batch_kernels.hpp).  The members run in lockstep on accepted steps: one batch iteration is one ``take_step``
+csrc/batch_kernels.hpp); a QP batch reads the objective matrix and its transpose once per trial as well.  The members run in lockstep on accepted steps: one batch iteration is one ``take_step``
 of every active member; evaluations, restarts and primal-weight updates happen per member at the iterations
 ``optimize`` would use, with the same helpers; a member that terminates leaves the batch.  Both drivers run the same
 per-problem solve object (``primal_dual_hybrid_gradient._Solve``): only the stepping between evaluations differs.
 
 ``HipPdhgBatch`` is the device side: one ``pdhg_handle`` that owns the matrix plus K member handles that borrow it
-(``.members``: ``HipPdhgEngine`` views -- every single-LP method works on them).
+(``.members``: ``HipPdhgEngine`` views -- every single-LP method works on them).  With ``objective_matrix`` the members
+are QPs that borrow one objective matrix too (``pdhg_batch_set_objective_matrix``).
 """
 import ctypes
 import os
@@ -33,10 +34,11 @@ class _BatchMember(_MemberEngine):
 
 
 class HipPdhgBatch(_MemberOwner):
-    """K LPs with one constraint matrix on one GPU (``pdhg_create_batch``)."""
+    """K LPs with one constraint matrix on one GPU (``pdhg_create_batch``); with ``objective_matrix`` (n x n, the same
+    for every member) K QPs."""
 
     def __init__(self, constraint_matrix, objective_vectors, right_hand_sides, variable_lower_bounds,
-                 variable_upper_bounds, num_equalities, device_id=-1, stream=None):
+                 variable_upper_bounds, num_equalities, device_id=-1, stream=None, objective_matrix=None):
         self._L = _lib.lib()
         A = sp.csc_matrix(constraint_matrix)
         self.m, self.n = int(A.shape[0]), int(A.shape[1])
@@ -58,10 +60,28 @@ class HipPdhgBatch(_MemberOwner):
         self._h = h
         self.K = K
         self.members = []
+        try:
+            self.set_objective_matrix(objective_matrix)
+        except Exception:
+            self.close()
+            raise
         for k in range(K):
             mh = ctypes.c_void_p()
             _lib.check(self._L.pdhg_batch_member(self._h, k, ctypes.byref(mh)))
             self.members.append(_BatchMember._wrap(self._L, mh, self.m, self.n))
+
+    def set_objective_matrix(self, objective_matrix):
+        """One objective matrix for every member (``pdhg_batch_set_objective_matrix``); ``None`` or no stored entry
+        leaves the batch as it is, stored entries that are all 0.0 make it an LP batch (again)."""
+        if objective_matrix is None:
+            return
+        Q = sp.csc_matrix(objective_matrix)
+        if Q.shape != (self.n, self.n):
+            raise ValueError(f"the objective matrix has shape {Q.shape}, not {(self.n, self.n)}")
+        if Q.nnz == 0:
+            return
+        qc, qr, qv = _i(Q.indptr), _i(Q.indices), _d(Q.data)
+        _lib.check(self._L.pdhg_batch_set_objective_matrix(self._h, len(qv), _pi(qc), _pi(qr), _pd(qv), 0))
 
     @classmethod
     def from_problems(cls, problems, **kw):
@@ -69,7 +89,8 @@ class HipPdhgBatch(_MemberOwner):
         p0 = problems[0]
         return cls(p0.constraint_matrix, [p.objective_vector for p in problems],
                    [p.right_hand_side for p in problems], [p.variable_lower_bound for p in problems],
-                   [p.variable_upper_bound for p in problems], p0.num_equalities, **kw)
+                   [p.variable_upper_bound for p in problems], p0.num_equalities,
+                   objective_matrix=_shared_q(p0), **kw)
 
     takes_original_problem = True
 
@@ -113,8 +134,21 @@ class HipPdhgBatch(_MemberOwner):
                                          cumulative_kkt_passes, a.ctypes.data_as(_int_p))
 
 
+def _shared_q(problem):
+    """A problem's objective matrix in canonical CSC form (duplicates summed, indices sorted), or None for an LP: no
+    matrix, no stored entry, or stored entries that are all 0.0."""
+    Q = problem.objective_matrix
+    if Q is None or Q.nnz == 0:
+        return None
+    Q = sp.csc_matrix(Q, copy=True)
+    Q.sum_duplicates()
+    Q.sort_indices()
+    return Q if np.any(Q.data != 0) else None
+
+
 def check_batch(problems, params=None):
-    """The batch's preconditions, checked before any device work (ValueError)."""
+    """The batch's preconditions, checked before any device work (ValueError): 1..32 problems, no Malitsky-Pock, one
+    constraint matrix, one ``num_equalities``, and either LPs throughout or QPs with one objective matrix."""
     problems = list(problems)
     if not 1 <= len(problems) <= MAX_BATCH:
         raise ValueError(f"optimize_batch takes 1..{MAX_BATCH} problems, not {len(problems)}")
@@ -122,10 +156,19 @@ def check_batch(problems, params=None):
         raise ValueError("optimize_batch supports the adaptive and constant step-size policies, not Malitsky-Pock")
     A0 = sp.csc_matrix(problems[0].constraint_matrix)
     A0.sort_indices()
+    Q0 = _shared_q(problems[0])
     for k, p in enumerate(problems):
-        Q = p.objective_matrix
-        if Q is not None and Q.nnz > 0 and np.any(sp.csc_matrix(Q).data != 0):
-            raise ValueError(f"problem {k} is a QP: optimize_batch takes LPs only")
+        Q = _shared_q(p) if k else Q0
+        if (Q is None) != (Q0 is None):
+            raise ValueError(f"problem {k} is {'an LP' if Q is None else 'a QP'}, problem 0 "
+                             f"{'an LP' if Q0 is None else 'a QP'}: a batch holds LPs only or QPs that share one objective matrix")
+        if Q is not None and k:
+            if Q.shape != Q0.shape:
+                raise ValueError(f"problem {k}'s objective matrix has shape {Q.shape}, problem 0's {Q0.shape}")
+            if not (np.array_equal(Q.indptr, Q0.indptr) and np.array_equal(Q.indices, Q0.indices)):
+                raise ValueError(f"problem {k}'s objective matrix has another sparsity pattern than problem 0's")
+            if not np.array_equal(Q.data, Q0.data):
+                raise ValueError(f"problem {k}'s objective matrix has other values than problem 0's")
         if int(p.num_equalities) != int(problems[0].num_equalities):
             raise ValueError(f"problem {k} has num_equalities {p.num_equalities}, problem 0 {problems[0].num_equalities}")
         if k == 0:
@@ -214,11 +257,18 @@ def _take_steps(batch, members, n_steps, policy):
 def optimize_batch(params, problems, batch_factory=None):
     """``optimize(params, problems[k])`` for every k, as one batch: a list of ``SaddlePointOutput`` in input order.
 
-    The problems must be LPs that share the constraint matrix (shape, pattern, values) and ``num_equalities``;
+    The problems must share the constraint matrix (shape, pattern, values) and ``num_equalities``, and be LPs
+    throughout or QPs that share the objective matrix as well (model-predictive control, a portfolio frontier, a
+    ridge or elastic-net path: c, b and the bounds differ, Q and A do not);
     ``batch_factory(problems) -> batch`` builds the device side (default ``HipPdhgBatch``; a factory whose
     ``takes_original_problem`` is true receives the original problems and rescales on the device, any other one
-    receives the host-rescaled problems).  Malitsky-Pock, QPs, an empty list or more than 32 problems raise
-    ``ValueError`` before any device work."""
+    receives the host-rescaled problems, whose scaled objective matrices are one matrix again).  Malitsky-Pock, a mix
+    of LPs and QPs, QPs with different objective matrices, an empty list or more than 32 problems raise ``ValueError``
+    before any device work.
+
+    Measured on one MI355X (README, "Batched solves"; ``profiles/batch_qp_throughput.txt``): at K = 8 a QP batch of
+    ``generators.random_qp_family`` runs 1.19x the solo QP handle's member-iterations/s at 10M x 10M and 1.48x at
+    1M x 1M; at 10M x 10M, K = 16 is no gain (0.98x)."""
     problems = check_batch(problems, params)
     _check_inputs(params, problems)
     policy = params.step_size_policy_params

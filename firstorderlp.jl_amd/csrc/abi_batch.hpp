@@ -1,13 +1,16 @@
 // abi_batch.hpp -- part of the single translation unit pdhg_hip.hip (included there, inside its extern "C" block).
-// C ABI: batched solves of K LPs that share one constraint matrix (batch_kernels.hpp holds the kernels).
+// C ABI: batched solves of K LPs -- or K QPs with one objective matrix -- that share one constraint matrix
+// (batch_kernels.hpp holds the kernels).
 //
 // A batch is a pdhg_handle that owns the matrix and its layouts (built once, as pdhg_create builds them) and K member
 // handles.  A member is an ordinary pdhg_handle with its own vectors whose A / At BORROW the batch's layouts (`owner`
 // set): every single-LP entry point works on it unchanged, on the batch's stream; pdhg_destroy skips it and the batch
 // frees it.  The persistent one-launch trial (trial_kernel.hpp) keeps per-layout counters, so it stays off on members
 // and on the batch handle; the other launch paths give the same bits.
+// pdhg_batch_set_objective_matrix makes the batch a QP batch: Q / Qt are built on the batch handle and lent to the members
+// the same way (the batch frees them, destroy_shard leaves a member's alone), every member gets its own qx and tmp_n2.
 
-// one of the two products of a batched trial: A X̄ (dual epilogue) or A' Y' (A'y epilogue)
+// one of the products of a batched trial: A X̄ (dual epilogue), A' Y' (A'y epilogue); a QP batch: Q X and Q' DX as well
 struct BatchProduct {
   int rows = 0, grid = 0, slots = 0, long_thr = 0;
   int nlong = 0, nchunks = 0, long_grid = 0, chunk_grid = 0;
@@ -22,6 +25,11 @@ struct BatchState {
   std::vector<pdhg_handle *> mem;
   BatchProduct PA, PT;
   double *X = nullptr, *Y = nullptr;
+  // a QP batch (the batch handle's has_q): Q X (no sums, no partials), Q' DX, x' - x member-interleaved like X, and where
+  // the members' qx are (qx_dev[k])
+  BatchProduct PQ, PQt;
+  double *DX = nullptr;
+  double **qx_dev = nullptr;
   BatchMemberDev *mdev = nullptr, *mhost = nullptr;
   int *act_dev = nullptr, *act_host = nullptr;
   double *res_dev = nullptr, *res_host = nullptr;
@@ -34,11 +42,29 @@ static void batch_free_product(BatchProduct &P) {
   P = BatchProduct{};
 }
 
+// Back to an LP batch: the members give their borrowed copies of Q / Qt back (they keep qx and tmp_n2), the batch frees
+// the layouts and what the two Q products needed.  The stream is idle.
+static void batch_drop_q(pdhg_handle *h) {
+  BatchState &B = *h->bat;
+  for (pdhg_handle *m : B.mem) {
+    m->Q = CsrDev(); m->Qt = CsrDev();
+    m->has_q = false;
+  }
+  free_csr_dev(h->Q); free_csr_dev(h->Qt);
+  h->has_q = false;
+  batch_free_product(B.PQ);
+  batch_free_product(B.PQt);
+  if (B.DX) (void)hipFree(B.DX);
+  if (B.qx_dev) (void)hipFree(B.qx_dev);
+  B.DX = nullptr; B.qx_dev = nullptr;
+}
+
 static void batch_release(pdhg_handle *h) {
   BatchState *B = h->bat;
   if (!B) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  batch_drop_q(h);
   for (pdhg_handle *m : B->mem) destroy_shard(m);
   batch_free_product(B->PA);
   batch_free_product(B->PT);
@@ -174,6 +200,68 @@ int pdhg_create_batch(pdhg_handle **out, int count, int64_t m, int64_t n, int64_
   return 0;
 }
 
+/* The objective matrix of every member (CSC like pdhg_set_objective_matrix's): the batch becomes a QP batch, or -- when
+ * every stored value is 0.0 -- an LP batch again.  May be called at any time between trials; the members keep their iterates. */
+int pdhg_batch_set_objective_matrix(pdhg_handle *batch, int64_t q_nnz, const int64_t *q_colptr, const int64_t *q_rowval,
+                                    const double *q_nzval, int index_base) {
+  if (!batch_of(batch)) return fail(-1, "pdhg_batch_set_objective_matrix: not a batch handle");
+  if (q_nnz < 0 || !q_colptr || (q_nnz > 0 && (!q_rowval || !q_nzval))) return fail(-1, "null input array");
+  pdhg_handle *h = batch;
+  BatchState &B = *h->bat;
+  bool all_zero = true;
+  for (int64_t k = 0; k < q_nnz; ++k) if (q_nzval[k] != 0.0) all_zero = false;
+  std::vector<int> t_rowptr, rowptr;
+  ivec t_col, col;
+  dvec t_val, val;
+  int rc = 0;
+  if (!all_zero) {
+    rc = csc_to_both(h->n, h->n, q_nnz, q_colptr, q_rowval, q_nzval, index_base, t_rowptr, t_col, t_val, rowptr, col, val);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  batch_drop_q(h);
+  h->state_version += 1; h->matrix_version += 1;
+  for (pdhg_handle *m : B.mem) {
+    // the launch paths were decided for the problem without (or with another) Q: decide again at the next trial
+    // (the persistent one-launch trial stays off on a member: coop_mode is 0)
+    m->graph_mode = -1;
+    m->small_lp_mode = -1;
+    graph_destroy(m->tgraph[0]); graph_destroy(m->tgraph[1]);
+    m->state_version += 1; m->matrix_version += 1;
+  }
+  if (all_zero) return 0;          // iszero(objective_matrix): LP path (pdhg.jl:536)
+  auto build = [&]() -> int {
+    int r2;
+    if ((r2 = build_csr_dev(h->Q, (int)h->n, (int)h->n, rowptr, col, val, h->remap))) return r2;
+    if ((r2 = build_csr_dev(h->Qt, (int)h->n, (int)h->n, t_rowptr, t_col, t_val, h->remap))) return r2;
+    const int long_thr = h->relaxed ? RELAXED_MIN_ROW : BLOCK_NNZ;
+    if ((r2 = batch_build_product(B.PQ, h->Q, B.shift, long_thr))) return r2;
+    if ((r2 = batch_build_product(B.PQt, h->Qt, B.shift, long_thr))) return r2;
+    const int64_t Kp = (int64_t)1 << B.shift;
+    if ((r2 = alloc_zero(&B.PQt.part, 2 * Kp * B.PQt.slots))) return r2;
+    if ((r2 = alloc_zero(&B.DX, h->n * Kp))) return r2;
+    double *qx[BATCH_MAX] = {};
+    for (int k = 0; k < B.K; ++k) {
+      pdhg_handle *m = B.mem[(size_t)k];
+      if (!m->qx && (r2 = alloc_zero(&m->qx, m->n))) return r2;
+      if (!m->tmp_n2 && (r2 = alloc_zero(&m->tmp_n2, m->n))) return r2;
+      qx[k] = m->qx;
+    }
+    HIP_TRY(hipMalloc((void **)&B.qx_dev, sizeof(double *) * BATCH_MAX));
+    HIP_TRY(hipMemcpy(B.qx_dev, qx, sizeof(double *) * BATCH_MAX, hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    return 0;
+  };
+  if ((rc = build())) { batch_drop_q(h); return rc; }
+  h->has_q = true;
+  for (pdhg_handle *m : B.mem) {   // struct copies: the same device arrays (pdhg_rescale scales them in place)
+    m->Q = h->Q; m->Qt = h->Qt;
+    m->has_q = true;
+  }
+  return 0;
+}
+
 int pdhg_batch_member(pdhg_handle *batch, int k, pdhg_handle **member) {
   if (!member) return fail(-1, "member == NULL");
   *member = nullptr;
@@ -211,7 +299,30 @@ static int batch_trial(pdhg_handle *h, const double *step_size, const double *pr
   HIP_TRY(hipMemcpyAsync(B.act_dev, B.act_host, sizeof(int) * (size_t)na, hipMemcpyHostToDevice, h->stream));
   BatchArgs a{B.mdev, B.act_dev, mask, B.K, B.shift, B.X, B.Y};
   const int n = (int)h->n, m = (int)h->m;
-  hipLaunchKernelGGL(batch_primal_kernel, dim3(ew_grid(n), na), dim3(TPB), 0, h->stream, n, a);
+  const bool qp = h->has_q;
+  // Q X into the members' qx or dx . (Q' DX) into P.part, from what aq.X holds: the short rows, then the long-row pair
+  auto q_product = [&](const CsrDev &D, BatchProduct &P, bool qdx, const BatchArgs &aq) {
+    if (qdx) hipLaunchKernelGGL((batch_spmv_kernel<BATCH_MODE_QDX, double *const *>), dim3(P.grid), dim3(TPB), 0, h->stream, P.rows,
+                                D.rowptr, D.col, D.val, P.long_thr, aq, P.part, P.slots, (double *const *)B.qx_dev);
+    else hipLaunchKernelGGL((batch_spmv_kernel<MODE_PLAIN, double *const *>), dim3(P.grid), dim3(TPB), 0, h->stream, P.rows, D.rowptr,
+                            D.col, D.val, P.long_thr, aq, P.part, P.slots, (double *const *)B.qx_dev);
+    if (P.nlong == 0) return;
+    hipLaunchKernelGGL(batch_long_partial_kernel, dim3(P.chunk_grid), dim3(TPB), 0, h->stream, P.nchunks, (const int2 *)P.chunks,
+                       (const int *)D.col, (const double *)D.val, 0, aq, P.cpart);
+    if (qdx) hipLaunchKernelGGL((batch_long_final_kernel<BATCH_MODE_QDX, double *const *>), dim3(P.long_grid), dim3(TPB), 0, h->stream,
+                                P.nlong, (const int *)P.long_row, (const int *)P.long_cptr, (const double *)P.cpart, aq, P.part,
+                                P.slots, P.grid, (double *const *)B.qx_dev);
+    else hipLaunchKernelGGL((batch_long_final_kernel<MODE_PLAIN, double *const *>), dim3(P.long_grid), dim3(TPB), 0, h->stream,
+                            P.nlong, (const int *)P.long_row, (const int *)P.long_cptr, (const double *)P.cpart, aq, P.part,
+                            P.slots, P.grid, (double *const *)B.qx_dev);
+  };
+  if (qp) {       // launch_primal's Q x, recomputed on every trial like there
+    hipLaunchKernelGGL(batch_pack_kernel, dim3(ew_grid(n), na), dim3(TPB), 0, h->stream, n, a);
+    q_product(h->Q, B.PQ, false, a);
+    hipLaunchKernelGGL(batch_primal_qp_kernel, dim3(ew_grid(n), na), dim3(TPB), 0, h->stream, n, a, (double *const *)B.qx_dev, B.DX);
+  } else {
+    hipLaunchKernelGGL(batch_primal_kernel, dim3(ew_grid(n), na), dim3(TPB), 0, h->stream, n, a);
+  }
   auto product = [&](const CsrDev &D, BatchProduct &P, bool dual) {
     if (dual) hipLaunchKernelGGL(batch_spmv_kernel<MODE_DUAL>, dim3(P.grid), dim3(TPB), 0, h->stream, P.rows, D.rowptr, D.col, D.val,
                                  P.long_thr, a, P.part, P.slots);
@@ -227,8 +338,17 @@ static int batch_trial(pdhg_handle *h, const double *step_size, const double *pr
   };
   if (m > 0) product(h->A, B.PA, true);
   if (n > 0) product(h->At, B.PT, false);
-  hipLaunchKernelGGL(batch_final_kernel, dim3(na), dim3(TPB), 0, h->stream, a, (const double *)B.PA.part, m > 0 ? B.PA.slots : 0,
-                     (const double *)B.PT.part, n > 0 ? B.PT.slots : 0, B.res_dev);
+  if (qp) {       // launch_q_interaction's Q' dx and its dot with dx
+    BatchArgs aq = a;
+    aq.X = B.DX;
+    q_product(h->Qt, B.PQt, true, aq);
+    hipLaunchKernelGGL((batch_final_kernel<const double *, int>), dim3(na), dim3(TPB), 0, h->stream, a, (const double *)B.PA.part,
+                       m > 0 ? B.PA.slots : 0, (const double *)B.PT.part, n > 0 ? B.PT.slots : 0, B.res_dev,
+                       (const double *)B.PQt.part, B.PQt.slots);
+  } else {
+    hipLaunchKernelGGL(batch_final_kernel<>, dim3(na), dim3(TPB), 0, h->stream, a, (const double *)B.PA.part, m > 0 ? B.PA.slots : 0,
+                       (const double *)B.PT.part, n > 0 ? B.PT.slots : 0, B.res_dev);
+  }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(B.res_host, B.res_dev, sizeof(double) * 5 * (size_t)B.K, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));

@@ -214,7 +214,7 @@ int pdhg_set_objective_matrix(pdhg_handle *h0, int64_t q_nnz, const int64_t *q_c
                               const int64_t *q_rowval, const double *q_nzval, int index_base) {
   int rc = check_handle(h0);
   if (rc) return rc;
-  if (h0->owner || h0->bat) return fail(-1, "pdhg_set_objective_matrix: batches hold LPs only");
+  if (h0->owner || h0->bat) return fail(-1, "pdhg_set_objective_matrix: not on a batch or its members (a QP batch: pdhg_batch_set_objective_matrix on the batch handle)");
   const Shards L = shards_of(h0);
   bump_version(L);
   bool all_zero = true;

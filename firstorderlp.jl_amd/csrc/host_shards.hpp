@@ -660,8 +660,8 @@ void destroy_shard(pdhg_handle *h) {
       else fprintf(stderr, "    second-stage reduction published at %6.2f us\n", t[12]);
     }
   }
-  if (!h->owner) { free_csr_dev(h->A); free_csr_dev(h->At); }   // a batch member borrows its batch's layouts
-  free_csr_dev(h->Q); free_csr_dev(h->Qt);
+  // a batch member borrows its batch's layouts (a QP batch's Q / Qt as well: the batch frees them once)
+  if (!h->owner) { free_csr_dev(h->A); free_csr_dev(h->At); free_csr_dev(h->Q); free_csr_dev(h->Qt); }
   for (CsrDev &D : h->Achunk) free_csr_dev(D);
   if (h->chunk_carry) (void)hipFree(h->chunk_carry);
   if (h->xchunk) (void)hipFree(h->xchunk);

@@ -7,7 +7,7 @@ cannot be replayed without Julia; these restate the *models*, not the streams.
 import numpy as np
 import scipy.sparse as sp
 
-from .quadratic_programming import linear_programming_problem
+from .quadratic_programming import QuadraticProgrammingProblem, linear_programming_problem
 
 
 def random_lp(m, n, nnz_per_row=10, seed=12345):
@@ -43,6 +43,34 @@ def random_lp(m, n, nnz_per_row=10, seed=12345):
     r[at_lower] = rng.random(int(at_lower.sum()))
     c = A.T @ y0 + r
     return linear_programming_problem(lb, ub, c, 0.0, A.tocsc(), b, num_eq)
+
+
+def random_qp_family(m, n, K, seed, nnz_per_row=10):
+    """K convex QPs that share the constraint AND the objective matrix (``optimize_batch``'s QP form): ``random_lp``'s
+    problem plus ``Q = B'B + diag`` (B: n/3 x n with three entries per row, diag from 0.05 to 0.5: symmetric, positive
+    definite).  Every member has its own objective vector, right-hand side (the inequalities' moved further into the
+    feasible side, so ``random_lp``'s x0 stays feasible) and finite upper bounds."""
+    base = random_lp(m, n, nnz_per_row, seed)
+    rng = np.random.default_rng([int(seed), 1])
+    rows_b = max(n // 3, 1)
+    B = sp.csr_matrix((rng.standard_normal(3 * rows_b), (np.repeat(np.arange(rows_b), 3), rng.integers(0, n, 3 * rows_b))),
+                      shape=(rows_b, n))
+    Q = (B.T @ B + sp.diags(np.linspace(0.05, 0.5, n))).tocsc()
+    Q = ((Q + Q.T) * 0.5).tocsc()      # symmetric to the last bit
+    Q.sum_duplicates()
+    Q.sort_indices()
+    num_eq = base.num_equalities
+    finite = np.isfinite(base.variable_upper_bound)
+    out = []
+    for k in range(int(K)):
+        c = base.objective_vector + (0.1 * rng.standard_normal(n) if k else 0.0)
+        b = base.right_hand_side.copy()
+        if k:
+            b[num_eq:] -= 0.1 * rng.random(m - num_eq)
+        ub = np.where(finite, base.variable_upper_bound + k, np.inf)
+        out.append(QuadraticProgrammingProblem(base.variable_lower_bound.copy(), ub, Q, c, 0.0, base.constraint_matrix, b,
+                                               num_eq))
+    return out
 
 
 def barabasi_albert_edges(num_nodes, degree, seed=0, batch=4096):

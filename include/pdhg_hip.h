@@ -525,7 +525,8 @@ int pdhg_selftest_wave_sums(pdhg_handle *h, int64_t seed, int64_t out[2]);
  * ---- batched solves: K LPs that share one constraint matrix ----------------------------------
  * No reference counterpart (the reference solves one LP per call); every member runs the reference's
  * take_step (src/primal_dual_hybrid_gradient.jl:653-767) on its own LP.  Members share the matrix
- * (shape, pattern, values) and num_equalities; each has its own c, b, lb, ub.
+ * (shape, pattern, values) and num_equalities; each has its own c, b, lb, ub.  With
+ * pdhg_batch_set_objective_matrix the members are QPs that share the objective matrix as well.
  *
  * pdhg_create_batch: `count` (1..32) members, vectors member-major: c[count*n], b[count*m],
  * lb[count*n], ub[count*n]; the matrix as in pdhg_create, held once.  nnz must stay below 2^31.
@@ -543,6 +544,16 @@ int pdhg_create_batch(pdhg_handle **out, int count, int64_t m, int64_t n, int64_
  * the evaluation branch, trust-region bounds) except pdhg_rescale and pdhg_set_objective_matrix,
  * which return -1.  pdhg_destroy on a member does nothing: members live and die with the batch. */
 int pdhg_batch_member(pdhg_handle *batch, int k, pdhg_handle **member);
+/* The objective matrix Q (n x n, CSC; the arguments of pdhg_set_objective_matrix) of EVERY member: the batch becomes a
+ * QP batch.  Q and Q' are built once on the batch handle and borrowed by the members like the constraint matrix, so
+ * every single-handle entry point works on a member as on a QP handle; pdhg_rescale on the batch scales Q with the
+ * constraint matrix (D^-1 Q D^-1).  The batched trial then forms Q x and dx'Q dx for all active members from one pass
+ * over Q and one over Q' (out[5k + 4] = 0.5 dx'Q dx), bitwise pdhg_trial_step on a QP handle under the row limits of
+ * pdhg_batch_trial_step, applied to the rows of Q and Q' too.  When every stored value is 0.0 the batch is (again) an
+ * LP batch.  Only a batch handle is accepted (-1 otherwise); the members keep their iterates, and the call may come
+ * after the batch has stepped.  pdhg_set_objective_matrix itself refuses a batch and its members. */
+int pdhg_batch_set_objective_matrix(pdhg_handle *batch, int64_t q_nnz, const int64_t *q_colptr,
+                                    const int64_t *q_rowval, const double *q_nzval, int index_base);
 /* One trial for every member k with active[k] != 0: out[5k .. 5k+4] = what pdhg_trial_step(member k,
  * step_size[k], primal_weight[k], theta) returns, and the same x', y', A'y' in member k's shadow
  * buffers.  Members not active are neither read nor written.  Bitwise pdhg_trial_step for rows

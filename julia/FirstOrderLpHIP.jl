@@ -1022,7 +1022,8 @@ end
 # ---- batched solves: K LPs that share one constraint matrix (include/pdhg_hip.h) ----------------------------
 """K problems with one constraint matrix as a batch (`pdhg_create_batch`): returns (batch handle, member handles).
 The members borrow the batch's matrix; every single-LP call above works on them (wrap one in a `HipSolverState`-like
-holder without a finalizer: `pdhg_destroy` on a member does nothing, `destroy_batch` frees the batch and its members)."""
+holder without a finalizer: `pdhg_destroy` on a member does nothing, `destroy_batch` frees the batch and its members).
+A nonzero `objective_matrix` of problem 1 is taken as every member's (`pdhg_batch_set_objective_matrix`): a QP batch."""
 function create_batch(problems::Vector{FirstOrderLp.QuadraticProgrammingProblem}; device_id::Integer = -1)
   K = length(problems)
   A = problems[1].constraint_matrix
@@ -1037,6 +1038,12 @@ function create_batch(problems::Vector{FirstOrderLp.QuadraticProgrammingProblem}
      Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Cint, Ptr{Cvoid}),
     h, K, m, n, length(A.nzval), A.colptr, A.rowval, A.nzval, 1, c, b, lb, ub,
     problems[1].num_equalities, device_id, C_NULL))
+  Q = problems[1].objective_matrix
+  if length(Q.nzval) > 0
+    check(ccall((:pdhg_batch_set_objective_matrix, LIB), Cint,
+      (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint),
+      h[], length(Q.nzval), Q.colptr, Q.rowval, Q.nzval, 1))
+  end
   members = Ptr{Cvoid}[]
   for k in 0:K-1
     mh = Ref{Ptr{Cvoid}}(C_NULL)

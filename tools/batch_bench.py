@@ -6,11 +6,19 @@ batched trial (a separate loop of pdhg_batch_trial_step).  Every timed call retu
 default is relaxed).
 
     python tools/batch_bench.py [--configs pagerank,l1svm,random] [--ks 1,2,4,8,16] [--steps 300] [--warmup 50]
+                                [--qp] [--qp-shape 10000000x10000000] [--against OTHER_CHECKOUT] [--reps 3]
                                 [--out profiles/batch_throughput.txt]
 
 Configurations: "pagerank" = personalized PageRank on the 1M-node PageRank LP (BASELINE configs[2]), one Dirichlet
 teleport vector per member; "l1svm" = L1-SVM regularization path on the rcv1-like data (configs[3]), weights 0.25 ..
 4; "random" = the 10M x 10M, 100M-nnz random LP (configs[4]) with per-member c and b.
+
+--qp adds the QP leg (rows "random+Q"): ``generators.random_qp_family`` at --qp-shape (default: the random config's
+shape), QPs that share Q = B'B + diag as well as A, against the solo QP engine on member 0 in the same run.
+
+--against OTHER_CHECKOUT (a built checkout of another commit, e.g. the parent) runs the LP legs --reps times with that
+checkout's own tools/batch_bench.py and with this one's, alternating, each in a fresh process, and prints per config and
+K the median member-it/s of both and the spread (worst - best) / best of each side's repetitions.
 """
 import argparse
 import os
@@ -43,6 +51,12 @@ def members(config, K, seed=0):
         out.append(linear_programming_problem(p.variable_lower_bound, p.variable_upper_bound, c, 0.0,
                                               p.constraint_matrix, b, p.num_equalities))
     return out
+
+
+def qp_members(shape, K):
+    from firstorderlp_jl_amd.generators import random_qp_family
+    m, n = (int(v) for v in shape.lower().split("x"))
+    return random_qp_family(m, n, K, 12345)
 
 
 def solo_rate(p, steps, warmup):
@@ -83,6 +97,48 @@ def batch_rates(problems, steps, warmup, trials=20):
         batch.close()
 
 
+def _table_rows(path):
+    """{(config, K): member-it/s} of a table this tool wrote."""
+    out = {}
+    with open(path) as fh:
+        for line in fh:
+            t = line.split()
+            if len(t) == 7 and t[1].isdigit():
+                out[(t[0], int(t[1]))] = float(t[2])
+    return out
+
+
+def against(args):
+    """The LP legs with another checkout's tool and library and with this one's, alternating, a fresh process each."""
+    import subprocess
+    import tempfile
+    sides = (("other", os.path.abspath(args.against)), ("this", ROOT))
+    runs = {name: [] for name, _ in sides}
+    for r in range(args.reps):
+        for name, root in sides:
+            with tempfile.NamedTemporaryFile(suffix=".txt") as tmp:
+                subprocess.check_call([sys.executable, os.path.join(root, "tools", "batch_bench.py"), "--configs", args.configs,
+                                       "--ks", args.ks, "--steps", str(args.steps), "--warmup", str(args.warmup),
+                                       "--out", tmp.name], cwd=root, stdout=subprocess.DEVNULL)
+                runs[name].append(_table_rows(tmp.name))
+            print(f"# repetition {r + 1} of {args.reps}, {name}: done", flush=True)
+    lines = [f"# tools/batch_bench.py --against {args.against} --configs {args.configs} --ks {args.ks} --steps {args.steps} "
+             f"--warmup {args.warmup} --reps {args.reps}  (PDHG_ROW_ORDER={os.environ.get('PDHG_ROW_ORDER', 'relaxed')})",
+             "# member-it/s: median of the repetitions; spread = (worst - best) / best of one side's repetitions",
+             f"{'config':<10} {'K':>3} {'other':>12} {'spread':>7} {'this':>12} {'spread':>7} {'this/other':>10}"]
+    for key in sorted(runs["this"][0], key=lambda k: (args.configs.split(",").index(k[0]), k[1])):
+        col = {}
+        for name, _ in sides:
+            v = sorted(run[key] for run in runs[name])
+            col[name] = (float(np.median(v)), (v[-1] - v[0]) / v[-1])
+        lines.append(f"{key[0]:<10} {key[1]:>3} {col['other'][0]:>12.1f} {col['other'][1]:>7.3f} {col['this'][0]:>12.1f} "
+                     f"{col['this'][1]:>7.3f} {col['this'][0] / col['other'][0]:>10.3f}")
+    print("\n".join(lines), flush=True)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="pagerank,l1svm,random")
@@ -90,7 +146,13 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--qp", action="store_true", help="the QP leg as well (rows random+Q)")
+    ap.add_argument("--qp-shape", default="10000000x10000000", help="m x n of the QP leg's family")
+    ap.add_argument("--against", default=None, help="another built checkout: its LP legs and this one's, alternating")
+    ap.add_argument("--reps", type=int, default=3, help="repetitions per side of --against")
     args = ap.parse_args(argv)
+    if args.against:
+        return against(args)
     import folp_loader
     folp_loader.load()
     ks = [int(k) for k in args.ks.split(",")]
@@ -99,8 +161,11 @@ def main(argv=None):
              f"{'config':<10} {'K':>3} {'member-it/s':>12} {'solo it/s':>10} {'ratio':>7} {'ms/batched trial':>17} "
              f"{'trials/step':>11}"]
     print("\n".join(lines), flush=True)
-    for config in args.configs.split(","):
-        probs = members(config, max(ks))
+    legs = [c for c in args.configs.split(",") if c] + (["random+Q"] if args.qp else [])
+    if args.qp:
+        lines.insert(1, f"# random+Q: random_qp_family at {args.qp_shape}; solo it/s = the solo QP engine on member 0")
+    for config in legs:
+        probs = qp_members(args.qp_shape, max(ks)) if config == "random+Q" else members(config, max(ks))
         solo = solo_rate(probs[0], args.steps, args.warmup)
         for K in ks:
             rate, ms_trial, tps = batch_rates(probs[:K], args.steps, args.warmup)
