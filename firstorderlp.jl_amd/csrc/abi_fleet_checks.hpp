@@ -1,17 +1,26 @@
 // abi_fleet_checks.hpp -- part of the single translation unit pdhg_hip.hip (included there, after abi_fleet.hpp).
 // C ABI: a fleet's CHECKS in shared launches (fleet_check_kernels.hpp): pdhg_eval_point of many members in one call,
 // trust-region problems of many members in one call.  A member that suits the one-workgroup kernels rides in the shared
-// launch; every other one is served by its own pdhg_eval_point / pdhg_trust_region_bound inside the same call, member
-// after member (pdhg_fleet_take_steps_adaptive's convention).  Either way the result is also left in the member
+// launch -- a small QP too, with PDHG_SMALL_QP=1, in launches of the QP kernels beside the LPs'; every other one is
+// served by its own pdhg_eval_point / pdhg_trust_region_bound inside the same call, member after member
+// (pdhg_fleet_take_steps_adaptive's convention).  Either way the result is also left in the member
 // (host_fleet.hpp: fleet_store_eval / fleet_store_tr), so the member's own call with the same arguments answers from it.
 
 // Does the member ride in the shared check launches?  An LP on one handle, not profiled, n + m within the one-workgroup
 // trust-region kernel's reach, no row of A or A' beyond SMALL_MAX_ROW entries (small_row_sum's order is launch_spmv's up
 // to there), plain CSR layouts, and the evaluation reductions publishing into pinned memory.  Independent of
 // small_lp_eligible: the step kernel keeps nine vectors in LDS, these kernels at most three.
+// A QP with PDHG_SMALL_QP=1 alone (read per call, like the other switches here), when CSR(Q) suits small_row_sum as A must.
+// Q' is not read by a check: a long column of Q keeps a member out of the step class, not out of this one.
 static bool fleet_check_eligible(pdhg_handle *h) {
   const char *se = dev_env("PDHG_SMALL_EVAL"), *pf = dev_env("PDHG_EVAL_PREFETCH");
-  return check_handle(h) == 0 && !h->grp && !h->has_q && !h->profile && h->n + h->m >= 1 && h->n + h->m <= TRS_MAX &&
+  if (check_handle(h) != 0) return false;
+  if (h->has_q) {
+    const char *qv = getenv("PDHG_SMALL_QP");
+    if (!(qv && qv[0] == '1' && h->Q.max_row_nnz <= SMALL_MAX_ROW && h->Q.segs.empty() && !h->Q.tiled && h->Q.slabs.empty() && h->Q.rowptr))
+      return false;
+  }
+  return !h->grp && !h->profile && h->n + h->m >= 1 && h->n + h->m <= TRS_MAX &&
          h->A.max_row_nnz <= SMALL_MAX_ROW && h->At.max_row_nnz <= SMALL_MAX_ROW && h->A.segs.empty() && h->At.segs.empty() &&
          !h->A.tiled && !h->At.tiled && h->A.slabs.empty() && h->At.slabs.empty() && h->A.rowptr && h->At.rowptr &&
          eval_host_word() && !(se && se[0] == '0') && !(pf && pf[0] == '0') && dev_env("PDHG_NO_EVAL_CACHE") == nullptr;
@@ -34,7 +43,12 @@ static int fleet_check_table(pdhg_handle *f, int which, size_t items, size_t byt
 }
 
 // one (member, point) of a call: the point's vectors and where its products live
-struct FleetPointRef { const double *px, *py; double *ax, *aty; };
+struct FleetPointRef { const double *px, *py; double *ax, *aty, *qx; };
+// the point items of a call: the LP members' and the QP members', each a launch of its kernel from its table
+struct FleetPointItems {
+  std::vector<FleetPointArgs> lp;
+  std::vector<FleetQpPointArgs> qp;
+};
 
 // The freshness marks of the members a call stages points of, as they were before.  fleet_stage_point marks a cache fresh
 // at once -- a later item of the same call at the same point of the same member must find it so -- but nothing has filled
@@ -59,8 +73,9 @@ struct FleetMarks {
 
 // select_point + point_products of one eligible member, as bookkeeping: the buffers of `point`, the caches marked fresh
 // exactly as point_products marks them, and -- when the average has to be materialised or the products are stale -- an
-// item for fleet_point_products_kernel.  (products == false: the average only, for the evaluation's distances.)
-static int fleet_stage_point(pdhg_handle *h, int point, bool products, std::vector<FleetPointArgs> &items, FleetPointRef *ref,
+// item for fleet_point_products_kernel -- for a QP, with Q x into ev_cqx[k] (allocated on first use, which makes the
+// products stale), for fleet_qp_point_products_kernel.  (products == false: the average only, for the evaluation's distances.)
+static int fleet_stage_point(pdhg_handle *h, int point, bool products, FleetPointItems &items, FleetPointRef *ref,
                              FleetMarks &marks) {
   int rc = ev_alloc(h);
   if (rc) return rc;
@@ -90,14 +105,23 @@ static int fleet_stage_point(pdhg_handle *h, int point, bool products, std::vect
       stale = h->ev_rkey != key;
       h->ev_rkey = key;
     }
+    if (h->has_q && !h->ev_cqx[k]) {
+      if ((rc = alloc_zero(&h->ev_cqx[k], h->n))) return rc;
+      stale = true;
+    }
     a.do_products = stale ? 1 : 0;
-    h->pt_x = px; h->pt_y = py; h->pt_ax = h->ev_cax[k]; h->pt_aty = h->ev_caty[k]; h->pt_qx = nullptr;
+    h->pt_x = px; h->pt_y = py; h->pt_ax = h->ev_cax[k]; h->pt_aty = h->ev_caty[k]; h->pt_qx = h->has_q ? h->ev_cqx[k] : nullptr;
   }
-  if (ref) *ref = FleetPointRef{px, py, h->ev_cax[k], h->ev_caty[k]};
+  if (ref) *ref = FleetPointRef{px, py, h->ev_cax[k], h->ev_caty[k], h->has_q ? h->ev_cqx[k] : nullptr};
   if (a.do_div || a.do_products) {
     a.A = h->A.view(); a.T = h->At.view();
     a.px = px; a.py = py; a.ax = h->ev_cax[k]; a.aty = h->ev_caty[k];
-    items.push_back(a);
+    if (h->has_q) {
+      FleetQpPointArgs q{};
+      static_cast<FleetPointArgs &>(q) = a;
+      q.Q = h->Q.view(); q.qx = h->ev_cqx[k];
+      items.qp.push_back(q);
+    } else items.lp.push_back(a);
   }
   return 0;
 }
@@ -115,6 +139,15 @@ static int fleet_check_launch(pdhg_handle *f, int which, const std::vector<Item>
                      (int)items.size());
   HIP_TRY(hipGetLastError());
   F.chk_launches += 1;
+  return 0;
+}
+
+// the point launches of a call: an empty part issues nothing; every cache marked fresh is filled once both have been issued
+static int fleet_point_launches(pdhg_handle *f, const FleetPointItems &items, FleetMarks &marks) {
+  int rc;
+  if ((rc = fleet_check_launch(f, 0, items.lp, fleet_point_products_kernel, TPB, 0))) return rc;
+  if ((rc = fleet_check_launch(f, 3, items.qp, fleet_qp_point_products_kernel, TPB, 0))) return rc;
+  marks.issued = true;
   return 0;
 }
 
@@ -170,8 +203,9 @@ int pdhg_fleet_eval_points(pdhg_handle *fleet, const int *points, double *out) {
   std::stable_sort(carried.begin(), carried.end(), [&](const Carried &a, const Carried &b) {
     return F.mem[(size_t)a.k]->n + F.mem[(size_t)a.k]->m > F.mem[(size_t)b.k]->n + F.mem[(size_t)b.k]->m;
   });
-  std::vector<FleetPointArgs> pitems;
+  FleetPointItems pitems;
   std::vector<FleetEvalArgs> eitems;
+  std::vector<FleetQpEvalArgs> qeitems;
   FleetMarks marks;
   for (Carried &c : carried) {
     pdhg_handle *h = F.mem[(size_t)c.k];
@@ -190,11 +224,17 @@ int pdhg_fleet_eval_points(pdhg_handle *fleet, const int *points, double *out) {
     a.partials = h->ev_partials; a.scal = h->scal_dev;
     a.host_out = h->ev_host;
     a.seq = c.seq = ++h->ev_seq;
-    eitems.push_back(a);
+    if (h->has_q) {
+      FleetQpEvalArgs q{};
+      static_cast<FleetEvalArgs &>(q) = a;
+      q.pt_qx = pt.qx;
+      qeitems.push_back(q);
+    } else eitems.push_back(a);
   }
-  if ((rc = fleet_check_launch(fleet, 0, pitems, fleet_point_products_kernel, TPB, 0))) return rc;
-  marks.issued = true;
+  // at most four launches: the LP members' points, the QP members', the LP evaluations, the QP evaluations
+  if ((rc = fleet_point_launches(fleet, pitems, marks))) return rc;
   if ((rc = fleet_check_launch(fleet, 1, eitems, fleet_eval_kernel, TPB, 0))) return rc;
+  if ((rc = fleet_check_launch(fleet, 4, qeitems, fleet_qp_eval_kernel, TPB, 0))) return rc;
   for (const Carried &c : carried) {
     pdhg_handle *h = F.mem[(size_t)c.k];
     double r[28];
@@ -266,7 +306,7 @@ int pdhg_fleet_trust_region_bounds(pdhg_handle *fleet, int count, const int *mem
       memset(F.chk_res, 0, cap * words * sizeof(double));
       F.chk_res_cap = cap;
     }
-    std::vector<FleetPointArgs> pitems;
+    FleetPointItems pitems;
     std::vector<TrSmallArgs> titems;
     FleetMarks marks;
     size_t lds = 0;
@@ -279,7 +319,7 @@ int pdhg_fleet_trust_region_bounds(pdhg_handle *fleet, int count, const int *mem
       if ((rc = fleet_stage_point(h, points[i], true, pitems, &pt, marks))) return rc;
       TrSmallArgs a{};
       a.n = (int)h->n; a.m = (int)h->m; a.ne = (int)h->num_eq; a.range = ranges[i]; a.approximate = approximate[i] ? 1 : 0;
-      a.px = pt.px; a.py = pt.py; a.aty = pt.aty; a.qx = nullptr; a.ax = pt.ax;
+      a.px = pt.px; a.py = pt.py; a.aty = pt.aty; a.qx = pt.qx; a.ax = pt.ax;
       a.c = h->c; a.b = h->b; a.lb = h->lb; a.ub = h->ub;
       a.wp = primal_weight_norm[i]; a.wd = dual_weight_norm[i]; a.radius = radii[i];
       a.host_out = F.chk_res + j * words;
@@ -288,8 +328,8 @@ int pdhg_fleet_trust_region_bounds(pdhg_handle *fleet, int count, const int *mem
       lds = std::max(lds, sizeof(double) * 3 * (size_t)(h->n + h->m));
     }
     if ((rc = fleet_tr_lds_limit(fleet->device, lds))) return rc;
-    if ((rc = fleet_check_launch(fleet, 0, pitems, fleet_point_products_kernel, TPB, 0))) return rc;
-    marks.issued = true;
+    // at most three launches: the LP members' points, the QP members', one trust-region launch for all problems
+    if ((rc = fleet_point_launches(fleet, pitems, marks))) return rc;
     if ((rc = fleet_check_launch(fleet, 2, titems, fleet_tr_kernel, TRS_TPB, lds))) return rc;
     for (size_t j = 0; j < carried.size(); ++j) {
       const int i = carried[j];

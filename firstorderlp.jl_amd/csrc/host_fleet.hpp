@@ -20,7 +20,7 @@ struct FleetState {
   int64_t launches = 0, last_carried = 0, last_single = 0;
   // the checks in shared launches (abi_fleet_checks.hpp): one argument table per kernel (device copy, pinned staging), the
   // fleet-owned result words of the trust-region items (EV_HOST_SLOTS + 2 doubles per item) and their sequence number
-  struct Table { void *dev = nullptr, *host = nullptr; size_t cap = 0; } chk_table[3];     // point products, evaluation, trust region
+  struct Table { void *dev = nullptr, *host = nullptr; size_t cap = 0; } chk_table[5];     // point products, evaluation, trust region; QP point products, QP evaluation
   double *chk_res = nullptr;
   size_t chk_res_cap = 0;
   unsigned long long chk_seq = 0;

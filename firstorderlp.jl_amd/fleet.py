@@ -13,6 +13,8 @@ terminates on its own, at the iterations ``optimize`` would.  Both drivers run t
 ``trust_region_bounds`` gets the device requests of every member's check -- the termination evaluation, the
 objective-bound estimates, the restart test -- in shared launches, one workgroup per member or trust-region problem
 (csrc/fleet_check_kernels.hpp), and each member then reads its own result; the restarts themselves stay per member.
+Under the same ``PDHG_SMALL_QP=1`` the shared check launches carry QP members as well (rows of ``Q`` of at most 256
+entries; the library decides per call, nothing changes here).
 
 ``HipPdhgFleet`` is the device side: one fleet handle that owns K ordinary member handles on one stream (``.members``:
 ``HipPdhgEngine`` views -- every single-LP method works on them, ``rescale`` included: a member's matrix is its own).

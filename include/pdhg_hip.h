@@ -49,7 +49,10 @@
  *                                                      <= 144 KiB): solo, and in a fleet's shared launches beside the LPs.  Read when the
  *                                                      class of a handle is decided (first batch of steps, pdhg_layout_info, after
  *                                                      pdhg_set_objective_matrix), where PDHG_SMALL_LP is read; PDHG_SMALL_LP=0 switches
- *                                                      the whole class off.  Same bits either way
+ *                                                      the whole class off.  A fleet's shared check launches
+ *                                                      (pdhg_fleet_eval_points, pdhg_fleet_trust_region_bounds) carry a QP under the
+ *                                                      same switch, read there at every call: n + m <= 4096, rows of A, A' and Q
+ *                                                      <= 256 entries (Q' is not read by a check).  Same bits either way
  *   PDHG_TR_COOP         1 | 0                         a trust-region search as one persistent launch
  *   PDHG_COOP_TRACE      0 | 1                         phase-boundary clock stamps in the persistent kernels (pdhg_trial_timeline)
  *   PDHG_RCCL_LIB        (unset) | <path>              the RCCL library to bind at run time
@@ -627,7 +630,7 @@ int pdhg_fleet_take_steps_malitsky_pock(pdhg_handle *fleet, const int64_t *n_ste
                                         int *numerical_error, int64_t *steps_done);
 /* info[0] members, info[1] shared STEP launches so far, info[2] members carried by the shared launch of
  * the last pdhg_fleet_take_steps_* call, info[3] members that call stepped singly; the checks in shared
- * launches (below): info[4] launches of the three check kernels so far, info[5] / info[6] items of the
+ * launches (below): info[4] launches of the check kernels so far, info[5] / info[6] items of the
  * last pdhg_fleet_eval_points / pdhg_fleet_trust_region_bounds carried by a shared launch / served per
  * member, info[7] the CALLER's pdhg_eval_point + pdhg_trust_region_bound calls on members so far that
  * were NOT answered from a result a fleet call had stored (the calls by which a fleet call itself serves
@@ -641,8 +644,12 @@ int pdhg_fleet_info(pdhg_handle *fleet, int64_t info[8]);
  * round trips per member.  These two calls take the requests of many members at once.  A member rides
  * in the shared launches (one workgroup per member or problem; at most one launch for the stale A x /
  * A'y products and one for the work itself) when it is an LP, not profiled, n + m <= 4096 and no row of
- * A or A' holds more than 256 entries; every other member (a QP, a larger or longer-rowed LP) is served
- * inside the same call by its own pdhg_eval_point / pdhg_trust_region_bound, member after member.
+ * A or A' holds more than 256 entries.  With PDHG_SMALL_QP=1 in the environment at the call a QP rides
+ * too when it meets the same conditions and no row of Q holds more than 256 entries (Q' is not read), in
+ * launches of the QP kernels beside the LPs': the stale products, Q x among them, and the evaluations
+ * take one launch each per kind.  Every other member (a QP without the switch, a larger or longer-rowed
+ * problem) is served inside the same call by its own pdhg_eval_point / pdhg_trust_region_bound, member
+ * after member.
  * Every row of `out` is bit for bit what the single-handle call on that member returns.
  *
  * Both calls also LEAVE their results in the member: a following pdhg_eval_point(member, point, ...) or
@@ -657,10 +664,12 @@ int pdhg_fleet_info(pdhg_handle *fleet, int64_t info[8]);
  * (-1), PDHG_POINT_AVERAGE while the average is empty (-1), a range outside 0..2 (-1), a member without
  * pdhg_set_original_problem (-1, evaluation only). */
 /* pdhg_eval_point(member k, points[k], out + 24 k) for every member k; points[k] == -1: member k and
- * its row of out are left alone. */
+ * its row of out are left alone.  At most four launches: the LP members' stale products, the QP
+ * members', the LP evaluations, the QP evaluations; a part without items issues nothing. */
 int pdhg_fleet_eval_points(pdhg_handle *fleet, const int *points /* [K] */, double *out /* [24 * K] */);
 /* pdhg_trust_region_bound(member[i], points[i], primal_weight_norm[i], dual_weight_norm[i], radii[i],
- * ranges[i], approximate[i], out + 8 i) for i < count; a member may appear in several items. */
+ * ranges[i], approximate[i], out + 8 i) for i < count; a member may appear in several items.  At most
+ * three launches: the LP members' stale products, the QP members', one for all trust-region problems. */
 int pdhg_fleet_trust_region_bounds(pdhg_handle *fleet, int count, const int *member, const int *points,
                                    const double *primal_weight_norm, const double *dual_weight_norm,
                                    const double *radii, const int *ranges, const int *approximate,

@@ -2,10 +2,12 @@
 single-LP engine and a Python loop of optimize.
 
     python tools/fleet_bench.py [--shapes netlib27x32,netlib56x97,random1000x800] [--ks 1,8,64,256,1024] [--steps 256]
-                                [--reps 5] [--solve-ks 1,8,64,256] [--out profiles/fleet_throughput.txt]
+                                [--reps 5] [--solve-ks 1,8,64,256] [--qp] [--out profiles/fleet_throughput.txt]
 
 Members: `random_lp(m, n)` of the shape, a distinct seed per member ("netlib27x32", "netlib56x97": the shapes of the
 reference's smallest Netlib runs, BASELINE configs[1]; "random1000x800": near the upper end of what one workgroup holds).
+`--qp`: the same LPs plus Q = B'B + diag, as tools/policy_steps_bench.py --qp builds them (run it with PDHG_SMALL_QP=1 to
+have the fleet carry them in its shared step and check launches; without, they are stepped and checked member by member).
 
 Stepping: one fleet of max(ks) members per shape; the K-member measurement passes n_steps = 0 for the others.  A timed
 call takes `steps` take_steps of every member (the call returns after every member's results have arrived, so the wall
@@ -29,6 +31,7 @@ optimize_many time and the spread; `--check-kernels` adds the kernel durations o
 """
 import argparse
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -43,10 +46,22 @@ sys.path.insert(0, ROOT)
 SHAPES = {"netlib27x32": (27, 32, 4), "netlib56x97": (56, 97, 4), "random1000x800": (1000, 800, 10)}
 
 
-def members(shape, K):
+def members(shape, K, qp=False):
     from firstorderlp_jl_amd.generators import random_lp
     m, n, per_row = SHAPES[shape]
-    return [random_lp(m, n, per_row, seed=7000 + k) for k in range(K)]
+    lps = [random_lp(m, n, per_row, seed=7000 + k) for k in range(K)]
+    if not qp:
+        return lps
+    import scipy.sparse as sp
+    from firstorderlp_jl_amd.quadratic_programming import QuadraticProgrammingProblem
+    out = []
+    for k, p in enumerate(lps):
+        B = sp.random(max(n // 3, 1), n, density=3.0 / n, format="csr", random_state=8000 + k)
+        Q = (B.T @ B + sp.diags(np.linspace(0.0, 0.5, n))).tocsc()
+        Q.sort_indices()
+        out.append(QuadraticProgrammingProblem(p.variable_lower_bound, p.variable_upper_bound, Q, p.objective_vector, 0.0,
+                                               p.constraint_matrix, p.right_hand_side, p.num_equalities))
+    return out
 
 
 def _start(problems):
@@ -101,11 +116,11 @@ def fleet_call_seconds(fleet, problems, ks, steps, reps):
     return out
 
 
-def child_launch(shape, K, steps):
+def child_launch(shape, K, steps, qp=False):
     """What the profiled child runs: a fleet of K members, a warm-up call and three calls of `steps` steps."""
     import folp_loader
     pkg = folp_loader.load()
-    problems = members(shape, K)
+    problems = members(shape, K, qp)
     fleet = pkg.HipPdhgFleet.from_problems(problems, device_id=0)
     try:
         ss, pw, it, kkt = _start(problems)
@@ -115,9 +130,10 @@ def child_launch(shape, K, steps):
         fleet.close()
 
 
-def kernel_us(shape, K, steps, timeout=300):
-    """Average duration (us) of small_lp_fleet_kernel in a `rocprofv3 --kernel-trace --stats` run of a child of its own,
-    or a string saying why there is none."""
+def kernel_us(shape, K, steps, qp=False, timeout=300):
+    """Average duration (us) of small_lp_fleet_kernel (--qp: small_qp_fleet_kernel) in a `rocprofv3 --kernel-trace --stats`
+    run of a child of its own, or a string saying why there is none."""
+    kernel = "small_qp_fleet_kernel" if qp else "small_lp_fleet_kernel"
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from rocprof_summary import summarize
     rp = shutil.which("rocprofv3")
@@ -125,13 +141,13 @@ def kernel_us(shape, K, steps, timeout=300):
         return "rocprofv3 not on PATH"
     work = tempfile.mkdtemp(prefix="pdhg_fleet_prof_", dir="/tmp")
     try:
-        cmd = [rp, "--kernel-trace", "--stats", "-d", work, "--", sys.executable, os.path.abspath(__file__), "--child", shape, str(K), str(steps)]
+        cmd = [rp, "--kernel-trace", "--stats", "-d", work, "--", sys.executable, os.path.abspath(__file__), "--child", shape, str(K), str(steps)] + (["--qp"] if qp else [])
         r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), timeout=timeout, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
         if r.returncode != 0:
             return f"profiled child failed ({r.returncode}): {r.stderr.decode(errors='replace')[-200:]}"
-        rows = [k for k in summarize(work) if "small_lp_fleet_kernel" in k["name"]]
+        rows = [k for k in summarize(work) if kernel in k["name"]]
         if not rows:
-            return "no small_lp_fleet_kernel in the trace"
+            return f"no {kernel} in the trace"
         # (the calls of one instantiation are the warm-up and three timed-like calls: their average)
         return max(k["avg_us"] for k in rows)
     except subprocess.TimeoutExpired:
@@ -208,14 +224,18 @@ def whole_solves(problems, K, loop_cap, iteration_limit, with_loop=True):
     return K / many, in_checks / many, n_loop / loop, n_loop, differ, info[0]
 
 
-def child_solve(shape, K, iteration_limit):
+def child_solve(shape, K, iteration_limit, qp=False):
     """What the profiled child of --check-kernels runs: one optimize_many of K members."""
     from firstorderlp_jl_amd import optimize_many
-    optimize_many(solve_params(iteration_limit), members(shape, K))
+    optimize_many(solve_params(iteration_limit), members(shape, K, qp))
 
 
-def check_kernels_us(shape, K, iteration_limit, timeout=400):
-    """{kernel: (calls, average us)} of the three check kernels in a `rocprofv3 --kernel-trace --stats` run of a child of
+CHECK_KERNELS = ("fleet_point_products_kernel", "fleet_eval_kernel", "fleet_tr_kernel", "small_lp_fleet_kernel",
+                 "fleet_qp_point_products_kernel", "fleet_qp_eval_kernel", "small_qp_fleet_kernel")
+
+
+def check_kernels_us(shape, K, iteration_limit, qp=False, timeout=400):
+    """{kernel: (calls, average us)} of the check kernels (and the shared step kernels) in a `rocprofv3 --kernel-trace --stats` run of a child of
     its own, or a string saying why there is none."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from rocprof_summary import summarize
@@ -225,15 +245,16 @@ def check_kernels_us(shape, K, iteration_limit, timeout=400):
     work = tempfile.mkdtemp(prefix="pdhg_fleet_prof_", dir="/tmp")
     try:
         cmd = [rp, "--kernel-trace", "--stats", "-d", work, "--", sys.executable, os.path.abspath(__file__), "--child-solve", shape, str(K),
-               str(iteration_limit)]
+               str(iteration_limit)] + (["--qp"] if qp else [])
         r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), timeout=timeout, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
         if r.returncode != 0:
             return f"profiled child failed ({r.returncode}): {r.stderr.decode(errors='replace')[-200:]}"
         out = {}
         for k in summarize(work):
-            for name in ("fleet_point_products_kernel", "fleet_eval_kernel", "fleet_tr_kernel", "small_lp_fleet_kernel"):
-                if name in k["name"]:
-                    out[k["name"].split("(")[0]] = (k.get("calls"), k["avg_us"])
+            # (a traced name is "[void ](anonymous namespace)::kernel[<256>](arguments)": the kernel and its template arguments)
+            hit = re.search(r"\b(" + "|".join(CHECK_KERNELS) + r")(<[^>]*>)?\(", k["name"])
+            if hit:
+                out[hit.group(1) + (hit.group(2) or "")] = (k.get("calls"), k["avg_us"])
         return out or "no check kernel in the trace"
     except subprocess.TimeoutExpired:
         return f"profiled child timed out after {timeout} s"
@@ -255,21 +276,23 @@ def main(argv=None):
     ap.add_argument("--out", default=None)
     ap.add_argument("--solve-reps", type=int, default=1, help="repeat every whole-solve measurement; report the best and the spread")
     ap.add_argument("--check-kernels", action="store_true", help="kernel durations of the check kernels (a rocprofv3 run of its own)")
+    ap.add_argument("--qp", action="store_true", help="QP members: the shape's LPs plus Q = B'B + diag (PDHG_SMALL_QP=1 lets the fleet carry them)")
     ap.add_argument("--child", nargs=3, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child-solve", nargs=3, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     import folp_loader
     pkg = folp_loader.load()
     if args.child:
-        child_launch(args.child[0], int(args.child[1]), int(args.child[2]))
+        child_launch(args.child[0], int(args.child[1]), int(args.child[2]), args.qp)
         return
     if args.child_solve:
-        child_solve(args.child_solve[0], int(args.child_solve[1]), int(args.child_solve[2]))
+        child_solve(args.child_solve[0], int(args.child_solve[1]), int(args.child_solve[2]), args.qp)
         return
     ks = [int(k) for k in args.ks.split(",") if k]
     solve_ks = [int(k) for k in args.solve_ks.split(",") if k]
     lines = [f"# tools/fleet_bench.py --shapes {args.shapes} --ks {args.ks} --steps {args.steps} --reps {args.reps} "
-             f"--solve-ks {args.solve_ks} --loop-cap {args.loop_cap} --iteration-limit {args.iteration_limit} --solve-reps {args.solve_reps}",
+             f"--solve-ks {args.solve_ks} --loop-cap {args.loop_cap} --iteration-limit {args.iteration_limit} --solve-reps {args.solve_reps}"
+             + (f" --qp    (PDHG_SMALL_QP={os.environ.get('PDHG_SMALL_QP', 'unset')})" if args.qp else ""),
              "# stepping: one call = `steps` take_steps of each of K members; best of `reps` calls; wall time includes the device",
              f"{'shape':<15} {'K':>5} {'call ms':>9} {'member-it/s':>12} {'solo call ms':>12} {'solo it/s':>10} {'ratio':>7}"]
     print("\n".join(lines), flush=True)
@@ -280,7 +303,7 @@ def main(argv=None):
 
     shapes = args.shapes.split(",")
     for shape in shapes if ks else []:
-        problems = members(shape, max(ks))
+        problems = members(shape, max(ks), args.qp)
         solo = solo_call_seconds(problems[0], args.steps, args.reps)
         fleet = pkg.HipPdhgFleet.from_problems(problems, device_id=0)
         try:
@@ -297,7 +320,7 @@ def main(argv=None):
             emit(f"# {shape}: members that stopped on a numerical error in a timed call (those calls are not counted): {stopped}")
         if not args.no_profile:
             K = min(args.profile_k, max(ks))
-            us = kernel_us(shape, K, args.steps)
+            us = kernel_us(shape, K, args.steps, args.qp)
             if isinstance(us, str):
                 emit(f"# {shape}: kernel duration of the shared launch at K = {K}: not measured ({us})")
             elif K in calls:
@@ -313,7 +336,7 @@ def main(argv=None):
         emit(f"{'shape':<15} {'K':>5} {'many solves/s':>13} {'loop solves/s':>13} {'ratio':>7} {'share in checks':>15} {'loop over':>9}"
              f"   (many solves/s: best of {args.solve_reps}; check_info() of the fleet at the end of the solve)")
     for shape in shapes if solve_ks else []:
-        problems = members(shape, max(solve_ks))
+        problems = members(shape, max(solve_ks), args.qp)
         for K in solve_ks:
             many, share, loop, n_loop, differ, info = whole_solves(problems, K, args.loop_cap, args.iteration_limit)
             rates = [many]
@@ -329,7 +352,7 @@ def main(argv=None):
                  + (f"   # {differ} solves differ from optimize's" if differ else ""))
         if args.check_kernels:
             K = min(args.profile_k, max(solve_ks))
-            got = check_kernels_us(shape, K, args.iteration_limit)
+            got = check_kernels_us(shape, K, args.iteration_limit, args.qp)
             if isinstance(got, str):
                 emit(f"# {shape}: check kernels at K = {K}: not measured ({got})")
             else:
