@@ -397,6 +397,13 @@ int pdhg_layout_describe(pdhg_handle *h, char *buf, int cap) {
              mode_name[h->bnd[0].mode], (long long)h->bnd[0].nexc, mode_name[h->bnd[1].mode], (long long)h->bnd[1].nexc);
     out += b;
   }
+  {
+    // how the C take_step loops update the running averages launch by launch (the handle's sum_x_alt ... pair_drops)
+    char b[192];
+    snprintf(b, sizeof b, ", \"average_update\": {\"form\": \"%s\", \"paired_accepts\": %lld, \"dropped_stagings\": %lld}",
+             (h->lazy_accept && pair_eligible(h)) ? "paired" : "single", (long long)h->pair_accepts, (long long)h->pair_drops);
+    out += b;
+  }
   // whole batches of steps in one workgroup (small_lp_kernel.hpp); a QP belongs to the class with PDHG_SMALL_QP=1 alone
   out += std::string(", \"small_lp\": ") + (small_lp_eligible(h) ? (h->has_q ? "\"qp\"" : "\"lp\"") : "false");
   const char *tv = getenv("PDHG_TUNE");

@@ -4,9 +4,11 @@
 // ---- the trial step -----------------------------------------------------------------
 
 // Single GPU: K1+K2, K3+K4, K5+K6 (fused epilogues), second-stage reduction.
-static int trial_dual_single(pdhg_handle *h, double step_size, double primal_weight, double out[5]) {
+// stage / stage_w: the paired average update (launch_dual)
+static int trial_dual_single(pdhg_handle *h, double step_size, double primal_weight, double out[5], bool stage = false,
+                             double stage_w = 0.0) {
   int rc;
-  if ((rc = launch_dual(h, primal_weight * step_size))) return rc;
+  if ((rc = launch_dual(h, primal_weight * step_size, stage, stage_w))) return rc;
   if ((rc = launch_aty_fused(h))) return rc;
   int qcount = 0;
   if ((rc = launch_q_interaction(h, &qcount))) return rc;
@@ -429,12 +431,23 @@ static int trial_dispatch(pdhg_handle *h, const TrialArgs &a, double out[5]) {
     if (group_coop_eligible(L) && (rc = group_coop_trial(L, a, out)) != 1) return rc;       // 1: not run / timed out, repeat below
     return group_trial(L, a, out);
   }
+  drop_staging(h);            // whatever path this trial takes, it rewrites the x' / y' a live staging was made from
   // (pdhg_trial_dual here: Malitsky-Pock retries, xbar + the dual half)
   if (coop_eligible(h) && (rc = coop_trial(h, a, out)) != 1) return rc;   // 1: as above
   if (a.primal && graph_eligible(h)) return graph_trial(h, a, out);
   // (check_handle has made the handle's device current)
-  if ((rc = a.primal ? launch_primal(h, a.step_size / a.primal_weight, a.theta, true) : launch_xbar(h, a.theta))) return rc;
-  return trial_dual_single(h, a.step_size, a.primal_weight, out);
+  // Launch by launch.  The paired average update: a whole trial from a caller that knows its accept's weight, with the
+  // previous accept's term pending on both sums, carries both terms into the alternate sums and leaves pend_* alone.
+  const bool stage = a.primal && a.know_w && h->lazy_accept && h->pend_x && h->pend_y && pair_eligible(h);
+  if (stage && (rc = ensure_pair_buffers(h))) return rc;
+  if ((rc = a.primal ? launch_primal(h, a.step_size / a.primal_weight, a.theta, true, stage, a.accept_w) : launch_xbar(h, a.theta))) return rc;
+  return trial_dual_single(h, a.step_size, a.primal_weight, out, stage, a.accept_w);
+}
+
+// pdhg_trial_step for the C take_step loops, which know the weight their accept will pass
+static int trial_step_weighted(pdhg_handle *h, double step_size, double primal_weight, double theta, double accept_w, double out[5]) {
+  RoctxRange roctx_range("pdhg_trial_step");
+  return trial_dispatch(h, TrialArgs{step_size, primal_weight, theta, true, true, accept_w}, out);
 }
 
 int pdhg_trial_dual(pdhg_handle *h, double step_size, double primal_weight, double theta, double out[5]) {
@@ -452,6 +465,29 @@ int pdhg_accept(pdhg_handle *h0, double avg_weight) {
   int rc = check_handle(h0, !(trial_stays_off_member_streams(h0) && h0->lazy_accept && !h0->pend_x && !h0->pend_y));
   if (rc) return rc;
   const Shards L = shards_of(h0);
+  // A live staging made for exactly this weight (its bits): the alternate sums ARE the sums after this accept -- swap
+  // them in and queue nothing.  Looked at before flush_pending, which would settle the pending term with a launch.
+  if (h0->staged) {
+    uint64_t wa, wb;
+    memcpy(&wa, &avg_weight, sizeof wa); memcpy(&wb, &h0->staged_w, sizeof wb);
+    if (wa == wb) {
+      pdhg_handle *h = h0;
+      h->staged = false;
+      h->pair_accepts += 1;
+      std::swap(h->sum_x, h->sum_x_alt);
+      std::swap(h->sum_y, h->sum_y_alt);
+      // both terms are in: the pending one (its count and weight were added by the accept that left it) and this one
+      h->pend_x = h->pend_y = false;
+      bump_version(L);
+      std::swap(h->x, h->x_next);
+      std::swap(h->y, h->y_next);
+      std::swap(h->aty, h->aty_next);
+      h->sum_x_count += 1; h->sum_y_count += 1;
+      h->sum_x_weights += avg_weight; h->sum_y_weights += avg_weight;
+      return 0;
+    }
+    drop_staging(h0);
+  }
   if ((rc = flush_pending(L))) return rc;   // two accepts without a trial in between
   bump_version(L);
   FOR_SHARDS(L, h) {
@@ -490,7 +526,7 @@ static int take_step_adaptive_from(pdhg_handle *h, StepIO &io) {
   for (bool done = false; !done;) {
     io.iterations += 1;
     double raw[5];
-    int rc = pdhg_trial_step(h, io.step_size, io.primal_weight, 1.0, raw);
+    int rc = trial_step_weighted(h, io.step_size, io.primal_weight, 1.0, step_on_entry, raw);
     if (rc) return failed(rc);
     const StepRule rule = step_after_trial(io, raw);
     if (rule.numerical_error) break;
@@ -571,7 +607,7 @@ int pdhg_take_steps_adaptive(pdhg_handle *h, int64_t n_steps, double reduction_e
 int pdhg_add_current_primal_to_average(pdhg_handle *h0, double weight);
 static int take_step_constant_one(pdhg_handle *h, PolicyIO &io) {
   double raw[5];
-  if (int rc = pdhg_trial_step(h, io.step_size, io.primal_weight, 1.0, raw)) return rc;
+  if (int rc = trial_step_weighted(h, io.step_size, io.primal_weight, 1.0, io.step_size, raw)) return rc;
   io.kkt_passes += 1;
   return pdhg_accept(h, io.step_size);
 }
@@ -727,6 +763,7 @@ int pdhg_reset_average(pdhg_handle *h0) {
     HIP_TRY(hipMemsetAsync(h->sum_x, 0, sizeof(double) * (size_t)std::max<int64_t>(h->n, 1), h->stream));
     HIP_TRY(hipMemsetAsync(h->sum_y, 0, sizeof(double) * (size_t)std::max<int64_t>(h->m, 1), h->stream));
     h->pend_x = h->pend_y = false;          // a deferred update belongs to the sums being discarded
+    drop_staging(h);                        // ... and so does a staged one
     h->sum_x_count = h->sum_y_count = 0;
     h->sum_x_weights = h->sum_y_weights = 0.0;
   }

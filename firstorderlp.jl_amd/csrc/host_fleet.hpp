@@ -232,6 +232,7 @@ int fleet_launch(pdhg_handle *f, std::vector<FleetCarry> &carry) {
   int64_t lo = INT64_MAX, hi = 0;
   for (FleetCarry &c : carry) {
     pdhg_handle *h = F.mem[(size_t)c.k];
+    drop_staging(h);      // (the launch consumes the pending term)
     if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
     if ((rc = steps_result_words(h))) return rc;
     steps_budget(c.n, &c.max_trials, &c.table_len);
@@ -279,6 +280,7 @@ int fleet_policy_launch(pdhg_handle *f, std::vector<FleetCarry> &carry) {
   int rc;
   for (FleetCarry &c : carry) {
     pdhg_handle *h = F.mem[(size_t)c.k];
+    drop_staging(h);      // (the launch consumes the pending term)
     if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
     if ((rc = steps_result_words(h))) return rc;
     c.few = small_lp_few_rows(h);

@@ -590,6 +590,8 @@ int create_shard(pdhg_handle **out, int64_t m, int64_t n, int64_t nnz,
   h->relaxed = !(env && !strcmp(env, "strict"));
   env = getenv("PDHG_LAZY_ACCEPT");       // 0: pdhg_accept runs K7 itself (one more launch and n + m more words per iteration)
   h->lazy_accept = !(env && env[0] == '0');
+  env = dev_env("PDHG_PAIR_AVG");         // 0: no paired average updates (pdhg_hip.hip: pair_eligible)
+  h->pair_wanted = !(env && env[0] == '0');
   if (stream) { h->stream = (hipStream_t)stream; h->own_stream = false; }
   else {
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
@@ -668,7 +670,7 @@ void destroy_shard(pdhg_handle *h) {
   for (hipEvent_t ev : h->ev_ag) if (ev) (void)hipEventDestroy(ev);
   if (h->ev_xbar) (void)hipEventDestroy(h->ev_xbar);
   double *bufs[] = {h->c, h->b, h->lb, h->ub, h->x, h->x_next, h->xbar, h->y, h->y_next,
-                    h->aty, h->aty_next, h->sum_x, h->sum_y, h->qx, h->tmp_n, h->tmp_n2,
+                    h->aty, h->aty_next, h->sum_x, h->sum_y, h->sum_x_alt, h->sum_y_alt, h->qx, h->tmp_n, h->tmp_n2,
                     h->tmp_m, h->pA, h->pAt, h->pQ, h->scal_dev, h->scal_all, h->dn_buf, h->dm_buf,
                     h->E, h->Dv, h->c_o, h->b_o, h->lb_o,
                     h->ub_o, h->x_r, h->y_r, h->px_avg, h->py_avg, h->ev_ax, h->ev_aty, h->tr_g,

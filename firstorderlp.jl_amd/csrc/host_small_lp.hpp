@@ -104,6 +104,7 @@ int small_lp_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   if (!small_lp_eligible(h)) return 1;
   HIP_TRY(hipSetDevice(h->device));
   int rc;
+  drop_staging(h);      // (the launch consumes the pending term)
   if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
   const int n = (int)std::min<int64_t>(n_steps, 1 << 20);
   int max_trials = 0, table_len = 0;
@@ -179,6 +180,7 @@ int small_policy_steps(pdhg_handle *h, int64_t n_steps, PolicyIO &io) {
   if (!small_lp_eligible(h)) return 1;
   HIP_TRY(hipSetDevice(h->device));
   int rc;
+  drop_staging(h);      // (the launch consumes the pending term)
   if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
   if ((rc = steps_result_words(h))) return rc;
   const size_t lds = small_lp_lds_bytes(h);

@@ -296,6 +296,7 @@ static bool device_loop_for(pdhg_handle *h) {
 int coop_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   if (io.device_loop < 0) io.device_loop = device_loop_for(h) ? 1 : 0;
   if (!io.device_loop || h->profile || !coop_eligible(h) || h->has_q || !h->lazy_accept || h->pend_x != h->pend_y) return 1;
+  drop_staging(h);      // (the launch consumes the pending term)
   int rc = coop_prepare(h);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));

@@ -215,7 +215,7 @@ int graph_build(pdhg_handle *h, pdhg_handle::TrialGraph &G, double tau, double t
   HIP_TRY(graph_add_kernel(G.graph, &G.n_primal, {}, (const void *)primal_kernel<false, true>, a.primal_grid, dim3(TPB),
                            a.n, (const double *)h->x, (const double *)h->c, (const double *)h->aty, nullq,
                            bound_view(h, 0), bound_view(h, 1), tau, theta, h->x_next, h->xbar,
-                           h->pend_w, h->pend_x ? h->sum_x : (double *)nullptr));
+                           h->pend_w, h->pend_x ? h->sum_x : (double *)nullptr, 0.0, (double *)nullptr));
   // K3+K4 on CSR(A), K5+K6 on CSR(A'): the stream kernel (or its column-slab passes, a
   // chain) and the long-row pair are independent branches
   std::vector<hipGraphNode_t> dual_done, aty_done;
@@ -264,7 +264,7 @@ int graph_trial(pdhg_handle *h, const TrialArgs &ta, double out[5]) {
       HIP_TRY(graph_set_kernel(G->exec, G->n_primal, (const void *)primal_kernel<false, true>, a.primal_grid, dim3(TPB),
                                a.n, (const double *)h->x, (const double *)h->c, (const double *)h->aty, nullq,
                                bound_view(h, 0), bound_view(h, 1), tau, theta, h->x_next, h->xbar,
-                               h->pend_w, h->pend_x ? h->sum_x : (double *)nullptr));
+                               h->pend_w, h->pend_x ? h->sum_x : (double *)nullptr, 0.0, (double *)nullptr));
       G->tau = tau; G->theta = theta; G->bounds_version = h->bounds_version;
       G->add_x = h->pend_x; G->add_wx = h->pend_w;
     }
@@ -322,6 +322,7 @@ int sync_all(const Shards &L) {
 // iterate that is current now.  Called by every entry point other than the trial itself.
 int flush_pending(const Shards &L) {
   FOR_SHARDS(L, h) {
+    drop_staging(h);          // the pending term goes into the sums themselves: alternates made from them are stale
     if (!h->pend_x && !h->pend_y) continue;
     ProfScope ps(h, PDHG_K_ACCEPT);
     const int64_t o = h->clo;

@@ -97,6 +97,18 @@ struct pdhg_handle {
   // (flush_pending).  pend_x / pend_y: the sums do not contain pend_w * (x | y) yet.
   bool pend_x = false, pend_y = false, lazy_accept = true;
   double pend_w = 0.0;
+  // Paired form of the lazy accept (plain handles whose A is in the sweep layout, launch by launch: pair_eligible): the
+  // first trial after an accept carries TWO terms -- the pending one and, in advance, its own x' / y' with the weight its
+  // accept will have (the C take_step loops know it) -- into sum_x_alt / sum_y_alt, beside the sums, which stay
+  // untouched.  staged: the alternates hold (sum + pend_w * (x | y)) + staged_w * (x' | y') for the x' / y' in
+  // x_next / y_next; pend_x / pend_y are still set and mean what they always mean.  pdhg_accept with that weight
+  // swaps the buffers and queues nothing; whatever else settles, discards or consumes the pending update first drops
+  // the staging (drop_staging), and the alternates are simply overwritten by the next one.
+  double *sum_x_alt = nullptr, *sum_y_alt = nullptr;     // n, m doubles; allocated by the first staging trial
+  bool staged = false;
+  double staged_w = 0.0;
+  bool pair_wanted = true;                               // PDHG_PAIR_AVG=0 (development variable, read at create): the single form
+  int64_t pair_accepts = 0, pair_drops = 0;              // accepts that were a swap; stagings that were not accepted
   double sum_x_weights = 0.0, sum_y_weights = 0.0;
 
   double *pA = nullptr;   // partials of the A kernel (1 quantity)
@@ -558,9 +570,30 @@ BoundView bound_view(const pdhg_handle *h, int k) {
   return v;
 }
 
+// ---- the paired form of the lazy accept (the handle's sum_x_alt ... pair_drops say what it is) ----
+// May this handle's trials stage?  Looked at per trial: an objective matrix or a fleet can arrive after create.  The
+// sweep kernel alone knows the paired epilogue, so every row of A must end there (no long rows, no row segments).
+bool pair_eligible(const pdhg_handle *h) {
+  return h->pair_wanted && !h->grp && !h->bat && !h->owner && !h->fleet && !h->fleet_of && !h->has_q && h->A.tiled &&
+         h->A.segs.empty() && h->A.nlong == 0 && h->A.grid > 0 && h->n > 0 && h->clo == 0 && h->cn == h->n;
+}
+// a staging that will not become the sums (the alternates are scratch until the next one)
+void drop_staging(pdhg_handle *h) {
+  if (h->staged) { h->staged = false; h->pair_drops += 1; }
+}
+int ensure_pair_buffers(pdhg_handle *h) {
+  int rc;
+  if (!h->sum_x_alt && (rc = alloc_zero(&h->sum_x_alt, h->n))) return rc;
+  if (!h->sum_y_alt && (rc = alloc_zero(&h->sum_y_alt, h->m))) return rc;
+  return 0;
+}
+
 // K1+K2 on this shard's column slice (the whole vector for a plain handle).
 // QP: Q is replicated and acts on the full x (kept full on every shard).
-int launch_primal(pdhg_handle *h, double tau, double theta, bool write_xbar) {
+// stage (trial_dispatch alone asks for it; pend_x is set): the paired form -- sum_x is read, sum_x_alt written with the
+// pending term and x' * stage_w, and pend_x stays as it is.
+int launch_primal(pdhg_handle *h, double tau, double theta, bool write_xbar, bool stage = false, double stage_w = 0.0) {
+  if (!stage) drop_staging(h);
   ProfScope ps(h, PDHG_K_PRIMAL);
   if (h->has_q) {
     EpiArgs e{};
@@ -577,12 +610,13 @@ int launch_primal(pdhg_handle *h, double tau, double theta, bool write_xbar) {
 #define PK(HQ, WX)                                                                           \
   hipLaunchKernelGGL((primal_kernel<HQ, WX>), dim3(grid), dim3(TPB), 0, h->stream, n,        \
                      h->x + o, h->c + o, h->aty + o, h->has_q ? h->qx + o : nullptr, lbv, ubv, tau, theta, \
-                     h->x_next + o, h->xbar + o, h->pend_w, h->pend_x ? h->sum_x + o : nullptr)
+                     h->x_next + o, h->xbar + o, h->pend_w, h->pend_x ? h->sum_x + o : nullptr, stage_w,   \
+                     stage ? h->sum_x_alt : (double *)nullptr)
   if (h->has_q) { if (write_xbar) PK(true, true); else PK(true, false); }
   else          { if (write_xbar) PK(false, true); else PK(false, false); }
 #undef PK
   HIP_TRY(hipGetLastError());
-  h->pend_x = false;
+  if (!stage) h->pend_x = false;
   return 0;
 }
 
@@ -598,6 +632,10 @@ int launch_xbar(pdhg_handle *h, double theta) {
 struct TrialArgs {
   double step_size, primal_weight, theta;
   bool primal;      // K1+K2 first (pdhg_trial_step); false: xbar only (pdhg_trial_dual)
+  // the C take_step loops know the weight their accept will pass (trial_step_weighted, abi_trial.hpp): a trial that
+  // may stage the paired average update.  The public entry points do not know it.
+  bool know_w = false;
+  double accept_w = 0.0;
 };
 
 // the dual step fused into A xbar (K3+K4), with the deferred sum_y update when one is pending; the dy^2 block partials
@@ -635,10 +673,16 @@ FinalSpec trial_final_spec(const pdhg_handle *h, int n_int, int n_dy, int q_coun
   return sp;
 }
 
-int launch_dual(pdhg_handle *h, double sigma) {
+// stage (pend_y is set; the launch_primal before it staged too): sum_y is read, sum_y_alt written with the pending term
+// and y' * stage_w, pend_y stays, and the staging is live once the launch is queued.
+int launch_dual(pdhg_handle *h, double sigma, bool stage = false, double stage_w = 0.0) {
+  if (!stage) drop_staging(h);
   ProfScope ps(h, PDHG_K_SPMV_DUAL);
-  const int rc = launch_spmv<MODE_DUAL, 0>(h, h->A, h->xbar, dual_epilogue(h, sigma));
-  if (!rc) h->pend_y = false;
+  EpiArgs e = dual_epilogue(h, sigma);
+  if (stage) { e.sum_y_out = h->sum_y_alt; e.avg_w2 = stage_w; }
+  const int rc = launch_spmv<MODE_DUAL, 0>(h, h->A, h->xbar, e);
+  if (!rc && !stage) h->pend_y = false;
+  if (!rc && stage) { h->staged = true; h->staged_w = stage_w; }
   return rc;
 }
 

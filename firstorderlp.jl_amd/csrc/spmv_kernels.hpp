@@ -39,6 +39,10 @@ struct EpiArgs {
   // MODE_DUAL: the deferred K7 of the previous accept, sum_y += avg_w * y (nullptr: none)
   double *sum_y;
   double avg_w;
+  // the paired form (spmv_tiled_kernel<MODE_DUAL, .> alone reads these; nullptr: none): sum_y is read, not written, and
+  // sum_y_out = (sum_y + avg_w * y) + avg_w2 * y' is what the sums are once this trial is accepted with weight avg_w2
+  double *sum_y_out;
+  double avg_w2;
 };
 
 template <bool COH>
@@ -65,16 +69,20 @@ __device__ __forceinline__ EpiOps epi_load(const EpiArgs &e, int r) {
   }
   return o;
 }
-template <int MODE, bool COH = false>
+// PAIR: the instance may meet the paired form of the deferred average update (EpiArgs::sum_y_out); without it the text
+// is what it was
+template <int MODE, bool COH = false, bool PAIR = false>
 __device__ __forceinline__ void epi_apply(const EpiArgs &e, int r, double s, const EpiOps &o, Acc3 &acc) {
   if (MODE == MODE_PLAIN) {
     e.out[r] = s;
   } else if (MODE == MODE_DUAL) {
     // compute_dual_gradient: b .- A*x              saddle_point.jl:1102-1107
     const double yo = o.a;
+    double sy = 0.0;
     if (e.sum_y) {
       const double t = yo * e.avg_w;
-      stc<COH>(e.sum_y + r, o.c + t);
+      sy = o.c + t;
+      if (!PAIR || !e.sum_y_out) stc<COH>(e.sum_y + r, sy);
     }
     const double dg = o.b - s;
     // next_dual = y .+ (pw*step) .* dual_gradient   pdhg.jl:489-490
@@ -83,6 +91,10 @@ __device__ __forceinline__ void epi_apply(const EpiArgs &e, int r, double s, con
     // project_dual!: only inequality rows           saddle_point.jl:110-117
     if (r >= e.num_eq) yn = jl_max(yn, 0.0);
     stc<COH>(e.y_next + r, yn);
+    if (PAIR && e.sum_y_out) {
+      const double u = yn * e.avg_w2;
+      e.sum_y_out[r] = sy + u;
+    }
     const double dy = yn - yo;                       // pdhg.jl:535
     dd_add(acc.hi[0], acc.lo[0], dy * dy);
   } else {
@@ -95,10 +107,10 @@ __device__ __forceinline__ void epi_apply(const EpiArgs &e, int r, double s, con
     dd_add(acc.hi[2], acc.lo[2], dd * dd);
   }
 }
-template <int MODE, bool COH = false>
+template <int MODE, bool COH = false, bool PAIR = false>
 __device__ __forceinline__ void row_epilogue(const EpiArgs &e, int r, double s,
                                              Acc3 &acc) {
-  epi_apply<MODE, COH>(e, r, s, epi_load<MODE, COH>(e, r), acc);
+  epi_apply<MODE, COH, PAIR>(e, r, s, epi_load<MODE, COH>(e, r), acc);
 }
 
 template <int MODE>
@@ -815,7 +827,8 @@ __global__ __launch_bounds__(TW_WPB * WAVE) void spmv_tiled_kernel(
     }
   }
   const int nrows = rr.y - rr.x;
-  for (int r = lane; r < nrows; r += WAVE) row_epilogue<MODE>(e, rr.x + r, acc[r], acc3);
+  // (the one kernel whose MODE_DUAL epilogue knows the paired average update: launch_dual alone sets e.sum_y_out)
+  for (int r = lane; r < nrows; r += WAVE) row_epilogue<MODE, false, MODE == MODE_DUAL>(e, rr.x + r, acc[r], acc3);
   constexpr int NQ = ModeNQ<MODE>::value;
   if (NQ > 0) {
     block_sum_dd<NQ, TW_THREADS>(acc3, red);

@@ -96,19 +96,23 @@ template <bool HAS_Q, bool WRITE_XBAR, bool COH = false, int LBM = BND_DENSE, in
 __device__ __forceinline__ void primal_body(
     int n, const double *x, const double *c, const double *aty, const double *qx,
     const BoundView &lb, const BoundView &ub, double tau, double theta, double *x_next, double *xbar,
-    double avg_w, double *sum_x, int bid, int nb) {
+    double avg_w, double *sum_x, int bid, int nb, double avg_w2 = 0.0, double *sum_x_out = nullptr) {
   // sum_x != nullptr: the accept of the previous iteration left its K7 to this kernel
   // (sum_x += avg_w * x, x being the iterate accepted then; same two roundings)
+  // sum_x_out != nullptr (only with sum_x): the paired form -- sum_x is read, not written, and
+  // sum_x_out = (sum_x + avg_w * x) + avg_w2 * x' holds what the sums are once THIS trial is accepted with weight avg_w2
+  // (the same additions in the same order as two single updates: pdhg_accept then swaps the buffers)
   const int npair = n >> 1;
   const int stride = nb * TPB;
   for (int p = bid * TPB + threadIdx.x; p < npair; p += stride) {
     const double2 xv = reinterpret_cast<const double2 *>(x)[p];
+    double2 sv = {0.0, 0.0};
     if (sum_x) {
-      double2 sv = reinterpret_cast<double2 *>(sum_x)[p];
+      sv = reinterpret_cast<double2 *>(sum_x)[p];
       const double t0 = xv.x * avg_w, t1 = xv.y * avg_w;
       sv.x = sv.x + t0;
       sv.y = sv.y + t1;
-      reinterpret_cast<double2 *>(sum_x)[p] = sv;
+      if (!sum_x_out) reinterpret_cast<double2 *>(sum_x)[p] = sv;
     }
     const double2 cv = reinterpret_cast<const double2 *>(c)[p];
     double2 av;
@@ -125,17 +129,29 @@ __device__ __forceinline__ void primal_body(
       reinterpret_cast<double2 *>(x_next)[p] = xn;
       if (WRITE_XBAR) reinterpret_cast<double2 *>(xbar)[p] = xb;
     }
+    if (sum_x_out) {
+      const double u0 = xn.x * avg_w2, u1 = xn.y * avg_w2;
+      sv.x = sv.x + u0;
+      sv.y = sv.y + u1;
+      reinterpret_cast<double2 *>(sum_x_out)[p] = sv;
+    }
   }
   if ((n & 1) && bid == 0 && threadIdx.x == 0) {
     const int j = n - 1;
     double xn, xb;
+    double sv = 0.0;
     if (sum_x) {
       const double t = x[j] * avg_w;
-      sum_x[j] = sum_x[j] + t;
+      sv = sum_x[j] + t;
+      if (!sum_x_out) sum_x[j] = sv;
     }
     primal_one<HAS_Q, WRITE_XBAR>(x[j], c[j], ldc<COH>(aty + j), HAS_Q ? qx[j] : 0.0, bound_at(lb, j), bound_at(ub, j), tau, theta, xn, xb);
     x_next[j] = xn;
     if (WRITE_XBAR) xbar[j] = xb;
+    if (sum_x_out) {
+      const double u = xn * avg_w2;
+      sum_x_out[j] = sv + u;
+    }
   }
 }
 
@@ -145,9 +161,10 @@ __global__ __launch_bounds__(TPB) void primal_kernel(
     const double *__restrict__ aty, const double *__restrict__ qx,
     BoundView lb, BoundView ub, double tau,
     double theta, double *__restrict__ x_next, double *__restrict__ xbar,
-    double avg_w, double *__restrict__ sum_x) {
+    double avg_w, double *__restrict__ sum_x, double avg_w2, double *__restrict__ sum_x_out) {
 #define PDHG_PB(L, U)                                                                                                   \
-  primal_body<HAS_Q, WRITE_XBAR, false, L, U>(n, x, c, aty, qx, lb, ub, tau, theta, x_next, xbar, avg_w, sum_x, blockIdx.x, gridDim.x)
+  primal_body<HAS_Q, WRITE_XBAR, false, L, U>(n, x, c, aty, qx, lb, ub, tau, theta, x_next, xbar, avg_w, sum_x, blockIdx.x, gridDim.x, \
+                                              avg_w2, sum_x_out)
   switch (lb.mode * 3 + ub.mode) {        // launch-uniform: one loop per pair of modes, no test inside it
     case BND_DENSE * 3 + BND_CONST: PDHG_PB(BND_DENSE, BND_CONST); break;
     case BND_DENSE * 3 + BND_SPARSE: PDHG_PB(BND_DENSE, BND_SPARSE); break;
