@@ -233,6 +233,9 @@ int pdhg_set_objective_matrix(pdhg_handle *h0, int64_t q_nnz, const int64_t *q_c
     if (h->gsync) { (void)hipFree(h->gsync); h->gsync = nullptr; }
     if (h->coop_trace) { (void)hipFree(h->coop_trace); h->coop_trace = nullptr; }
     h->coop_mode = -1; h->coop_launches = 0; h->coop_epoch = 0;
+    // (the multi-step kernel's XCD-local census was taken for the old grid)
+    if (h->lsync) { (void)hipFree(h->lsync); h->lsync = nullptr; }
+    h->local_mode = -1;
     h->graph_mode = -1;
     h->small_lp_mode = -1;
     graph_destroy(h->tgraph[0]); graph_destroy(h->tgraph[1]);

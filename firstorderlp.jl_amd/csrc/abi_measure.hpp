@@ -424,7 +424,7 @@ int pdhg_layout_info(pdhg_handle *h, int64_t info[16]) {
   info[15] = ((h->A.tiled && h->A.var_tiles) || (!h->A.segs.empty() && h->A.segs.front().tiled && h->A.segs.front().var_tiles) ? 1 : 0) +
              ((h->At.tiled && h->At.var_tiles) || (!h->At.segs.empty() && h->At.segs.front().tiled && h->At.segs.front().var_tiles) ? 2 : 0) +
              (small_lp_eligible(h) ? 4 : 0) +
-             (!h->grp && !h->has_q && !small_lp_eligible(h) && check_handle(h) == 0 && device_loop_for(h) && coop_eligible(h) ? 8 : 0) +
+             (!h->grp && !small_lp_eligible(h) && check_handle(h) == 0 && device_loop_for(h) && coop_eligible(h) ? 8 : 0) +   // (a QP: with PDHG_DEVICE_LOOP=1 alone)
              (h->local_mode == 1 && h->local_launches > 0 ? 16 : 0);      // the multi-step kernel runs in its XCD-local mode
   // a matrix held as row segments (64-bit extents, layout.hpp) reports the sums over its segments, the first segment's
   // tile width, and the segment counts in bits 8-15 (A) and 16-23 (A') of info[15]

@@ -670,7 +670,7 @@ void destroy_shard(pdhg_handle *h) {
   for (hipEvent_t ev : h->ev_ag) if (ev) (void)hipEventDestroy(ev);
   if (h->ev_xbar) (void)hipEventDestroy(h->ev_xbar);
   double *bufs[] = {h->c, h->b, h->lb, h->ub, h->x, h->x_next, h->xbar, h->y, h->y_next,
-                    h->aty, h->aty_next, h->sum_x, h->sum_y, h->sum_x_alt, h->sum_y_alt, h->qx, h->tmp_n, h->tmp_n2,
+                    h->aty, h->aty_next, h->sum_x, h->sum_y, h->sum_x_alt, h->sum_y_alt, h->qx, h->qx2, h->tmp_n, h->tmp_n2,
                     h->tmp_m, h->pA, h->pAt, h->pQ, h->scal_dev, h->scal_all, h->dn_buf, h->dm_buf,
                     h->E, h->Dv, h->c_o, h->b_o, h->lb_o,
                     h->ub_o, h->x_r, h->y_r, h->px_avg, h->py_avg, h->ev_ax, h->ev_aty, h->tr_g,

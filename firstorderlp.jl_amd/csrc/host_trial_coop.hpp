@@ -280,6 +280,8 @@ static bool device_loop_for(pdhg_handle *h) {
   // per-trial launches (tests/test_gpu_device_loop.py) and faster on every grid measured but one tie: L1-SVM 19.7k ->
   // 23.4k it/s, random 100K 22.5k -> 28.6k, 3000 x 2500 32.7k -> 52.7k (trial_kernel.hpp, profiles/r03_trial_kernel.txt).
   // PDHG_DEVICE_LOOP=0 / 1: never / whenever eligible; PDHG_DEVICE_LOOP_MAX_WGS: largest grid it is the default for.
+  // A QP (steps_kernel's QP form) enters with PDHG_DEVICE_LOOP=1 alone: unset, it goes launch by launch as before
+  // (profiles/steps_qp_throughput.txt has what the default would have to be decided on).
   const char *dl_env = getenv("PDHG_DEVICE_LOOP");
   bool device_loop = dl_env && dl_env[0] == '1';
   if (!dl_env && !h->profile && !h->has_q && coop_eligible(h)) {
@@ -295,7 +297,7 @@ static bool device_loop_for(pdhg_handle *h) {
 // launched (the multi-step kernel is not wanted for this call, or the handle does not suit it).
 int coop_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   if (io.device_loop < 0) io.device_loop = device_loop_for(h) ? 1 : 0;
-  if (!io.device_loop || h->profile || !coop_eligible(h) || h->has_q || !h->lazy_accept || h->pend_x != h->pend_y) return 1;
+  if (!io.device_loop || h->profile || !coop_eligible(h) || !h->lazy_accept || h->pend_x != h->pend_y) return 1;
   drop_staging(h);      // (the launch consumes the pending term)
   int rc = coop_prepare(h);
   if (rc) return rc;
@@ -319,7 +321,22 @@ int coop_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   h->A.coop_uses -= 1; h->At.coop_uses -= 1;       // (trial_product counted one use: the launch's own count comes back with the results)
   a.uses_a = a.A.uses; a.uses_t = a.T.uses;
   a.pA = h->pA; a.pAt = h->pAt; a.pA_slots = h->A.slots(); a.pAt_stride = h->pAt_stride;
-  const FinalSpec sp = trial_final_spec(h, h->At.slots(), h->A.slots(), 0, h->A.slots(), nullptr);
+  const bool qp = h->has_q;
+  if (qp) {
+    // the QP form keeps Q x for the iterate and for the trial point (qx / qx2 flip with x); the first trial's Q x is
+    // this product, ahead of the launch in stream order -- the bits of trial_kernel's phase -1
+    if (!h->qx2 && (rc = alloc_zero(&h->qx2, h->n))) return rc;
+    EpiArgs qe{};
+    qe.out = h->qx;
+    if ((rc = launch_spmv<MODE_PLAIN, 2>(h, h->Q, h->x, qe))) return rc;
+    a.Q = trial_product(h, h->Q, nullptr, none);
+    a.Qt = trial_product(h, h->Qt, nullptr, none);
+    h->Q.coop_uses -= 1; h->Qt.coop_uses -= 1;
+    a.uses_q = a.Q.uses; a.uses_qt = a.Qt.uses;
+    a.qxa = h->qx; a.qxb = h->qx2;
+    a.dx = h->tmp_n; a.qtdx = h->tmp_n2; a.pq = h->pQ; a.q_blocks = h->ew_grid_n;
+  }
+  const FinalSpec sp = trial_final_spec(h, h->At.slots(), h->A.slots(), qp ? h->ew_grid_n : 0, h->A.slots(), nullptr);
   memcpy(h->steps_pow_host + 2 * (size_t)table_len, &sp, sizeof sp);        // staged behind the pow tables (pinned)
   HIP_TRY(hipMemcpyAsync(&h->steps_ctl->sp, h->steps_pow_host + 2 * (size_t)table_len, sizeof sp, hipMemcpyHostToDevice, h->stream));
   a.primal_weight = io.primal_weight; a.step_size = io.step_size;
@@ -346,7 +363,9 @@ int coop_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   a.trace = h->coop_trace;
   for (int x = 0; x < 8; ++x) a.xcd_cnt[x] = h->coop_xcd_cnt[x];
   const auto c1 = std::chrono::steady_clock::now();
-  if (local) hipLaunchKernelGGL(steps_kernel<true>, dim3(8 * h->coop_grid), dim3(TPB), 0, h->stream, a);
+  if (local && qp) hipLaunchKernelGGL((steps_kernel<true, true>), dim3(8 * h->coop_grid), dim3(TPB), 0, h->stream, a);
+  else if (qp) hipLaunchKernelGGL((steps_kernel<false, true>), dim3(h->coop_grid), dim3(TPB), 0, h->stream, a);
+  else if (local) hipLaunchKernelGGL(steps_kernel<true>, dim3(8 * h->coop_grid), dim3(TPB), 0, h->stream, a);
   else hipLaunchKernelGGL(steps_kernel<false>, dim3(h->coop_grid), dim3(TPB), 0, h->stream, a);
   HIP_TRY(hipGetLastError());
   const auto c2 = std::chrono::steady_clock::now();
@@ -361,7 +380,12 @@ int coop_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   else h->coop_epoch = (unsigned long long)r[10];
   h->A.coop_uses += (unsigned long long)trials + (aborted ? 1ull : 0ull);
   h->At.coop_uses += (unsigned long long)trials + (aborted ? 1ull : 0ull);
+  if (qp) {
+    h->Q.coop_uses += (unsigned long long)trials + (aborted ? 1ull : 0ull);
+    h->Qt.coop_uses += (unsigned long long)trials + (aborted ? 1ull : 0ull);
+  }
   if (flip) { std::swap(h->x, h->x_next); std::swap(h->y, h->y_next); std::swap(h->aty, h->aty_next); }
+  if (flip && qp) std::swap(h->qx, h->qx2);
   h->pend_x = h->pend_y = r[4] != 0.0;
   h->pend_w = r[5];
   if (trials > 0 || aborted) h->state_version += 1;     // (bump_version of a single handle)

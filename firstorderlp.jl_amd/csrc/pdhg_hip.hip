@@ -90,6 +90,7 @@ struct pdhg_handle {
   double *aty = nullptr, *aty_next = nullptr;  // n+1 each (slot n: exchange scalar)
   double *sum_x = nullptr, *sum_y = nullptr;
   double *qx = nullptr, *tmp_n = nullptr, *tmp_n2 = nullptr, *tmp_m = nullptr;
+  double *qx2 = nullptr;  // the multi-step kernel's QP form: Q x of the trial point (swapped with qx on an accepted flip; allocated on first use)
   int64_t sum_x_count = 0, sum_y_count = 0;
   // Lazy accept: pdhg_accept swaps the iterates and leaves K7 (sum += w * iterate) to the
   // kernels of the next trial, which read x and y anyway (primal_kernel, the dual epilogue);

@@ -32,6 +32,10 @@ namespace {
 #ifndef PDHG_STEPS_LP_BATCH
 #define PDHG_STEPS_LP_BATCH 8      // (L1-SVM, 856 slots per quantity: 22.8-23.2k it/s with 4, 23.1-23.4k with 6, 23.4-23.5k with 8)
 #endif
+// the QP form's second stage (final_reduce_qp): load pairs of the fifth quantity requested ahead per lane
+#ifndef PDHG_STEPS_QP_PRE
+#define PDHG_STEPS_QP_PRE 1       // (3 costs 24 more bytes of scratch per lane and is no faster: 3000 x 2500 41.4-41.8k it/s with 1, 39.7-40.3k
+#endif                            //  with 3; L1-SVM + Q, 448 partials, a tie: profiles/steps_qp_throughput.txt)
 
 // One fused SpMV of the trial: a stream layout (row blocks + long-row chunks) with its epilogue
 struct TrialProduct {
@@ -296,6 +300,12 @@ struct StepsKernelArgs {
   int local_g;                                    // > 0: XCD-local mode -- the launch is 8 x local_g workgroups, those on XCD local_home work
   unsigned local_home;
   unsigned long long local_ticket_base;            // tickets drawn by earlier launches (local_g each)
+  // QP form (steps_kernel<., true> alone reads these; they stand at the end so that the LP forms' argument offsets stay)
+  TrialProduct Q, Qt;                             // static parts, as A and T
+  double *qxa, *qxb;                              // Q x of the iterate and of the trial point: flips with x
+  double *dx, *qtdx, *pq;                         // x' - x, Q'dx, the block partials of dx . (Q'dx)
+  int q_blocks;
+  unsigned long long uses_q, uses_qt;
 };
 
 // result words (grid_sync.hpp: STEPS_RES_K values, checksum at [STEPS_RES_CAP], sequence number behind it):
@@ -306,7 +316,22 @@ constexpr int STEPS_RES_WORDS = STEPS_RES_CAP + 2;
 
 // LOCAL: the XCD-local mode as its own instantiation (the all-XCD kernel sits at its register limit: as a run-time flag
 // the mode cost it 92 more bytes of scratch per lane)
-template <bool LOCAL>
+//
+// QP: the QP form, again instantiations of their own (PDHG_DEVICE_LOOP=1 alone reaches them; `if constexpr`, so the LP
+// forms keep their text).  Per trial it computes what one trial_kernel QP launch and the host's rule compute, in THREE
+// barriers where trial_kernel's schedule (a phase -1 for Q x with a barrier of its own) and the decision barrier would
+// make four: Q x is kept for the iterate AND for the trial point (qxa / qxb flip with x on an accept).  Q x' joins
+// A xbar and Q'dx in phase 1 -- x' is whole after the first barrier -- so the next trial's primal step finds its Q x
+// there after an accept, and after a rejection x has not moved and the kept Q x has the bits a recomputation would
+// have.  The first trial's Q x is the host's product launch ahead in stream order.
+//   phase 0  x', xbar (primal_body<true, true, true>), dx = x' - x (same element mapping: a thread reads its own x')
+//   phase 1  y' from A xbar; Q'dx; Q x'          -- three products, walked one after another with product_phase(w, nwg)
+//   phase 2  A'y' and the three sums; the partials of dx . (Q'dx), q_blocks of them by dot_body
+//   leaders  five sums (final_reduce_qp), the fifth halved, the rule
+// Coherent (ldc<true>) on top of the LP form's loads: Q x in the primal step (written by phase 1 of an earlier trial on
+// other compute units), dx and x' in the gathers of the two Q products, Q'dx and dx in dot_body.  In the XCD-local mode
+// as well: L1 is per compute unit.  x and x' in diff_pairs_body stay plain: the thread wrote them itself.
+template <bool LOCAL, bool QP = false>
 __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(StepsKernelArgs a) {
   __shared__ double prod[BLOCK_NNZ];
   __shared__ double red[6][TPB / WAVE];
@@ -317,7 +342,7 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
   // the pending average update, [3] / [4] the averages' weight sums
   __shared__ double s_st[5];
   __shared__ double s_pow[2];
-  __shared__ double s_res8[8];
+  __shared__ double s_res8[QP ? 14 : 8];
   int w = blockIdx.x, nwg = gridDim.x;
   constexpr bool local = LOCAL;
   if (local) {
@@ -360,6 +385,11 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
       pw_r = a.pow_red[trials]; pw_g = a.pow_growth[trials];
     }
     // ---- phase 0: x' and xbar (+ the deferred sum_x update of the previous accept)
+    if constexpr (QP) {
+      primal_body<true, true, true>(a.n, x, a.c, aty, flip ? a.qxb : a.qxa, bound_dense(a.lb), bound_dense(a.ub), tau, 1.0, xn, a.xbar,
+                                    pend_w, pend ? a.sum_x : nullptr, w, nwg);
+      diff_pairs_body(a.n, xn, x, a.dx, w, nwg);
+    } else
     primal_body<false, true, true>(a.n, x, a.c, aty, nullptr, bound_dense(a.lb), bound_dense(a.ub), tau, 1.0, xn, a.xbar, pend_w,
                                    pend ? a.sum_x : nullptr, w, nwg);
     product_prefetch(a.A, f, w, nwg);
@@ -377,6 +407,24 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
       if (pend) { e.sum_y = a.sum_y; e.avg_w = pend_w; }
       product_phase<MODE_DUAL, true>(a.A, a.xbar, e, a.uses_a + (unsigned long long)trials, a.relaxed, f, prod, red, w, nwg);
     }
+    if constexpr (QP) {                                      // Q'dx and Q x': independent of A xbar, same phase
+      Prefetched none;
+      none.kind = 0;
+      EpiArgs e{};
+      e.out = a.qtdx;
+      // The grid holds max(Q, A + Q') items, not the phase's A + Q' + Q: Q''s row blocks start at the workgroup after A's
+      // last one and Q's after those (rotated workgroup numbers; a multiple of eight under the XCD remap, so every XCD
+      // keeps its eighth).  Walked from workgroup 0 like A, the first workgroups had three items and the last none:
+      // phase 1 took 12.2 us on its slowest workgroup against a mean of 4.1 (3000 x 2500, 24 workgroups).  Slots and
+      // tickets are indexed by item: the bits do not depend on who works on it.
+      int wq = w - a.A.grid % nwg;
+      wq += wq < 0 ? nwg : 0;
+      product_phase<MODE_PLAIN, true>(a.Qt, a.dx, e, a.uses_qt + (unsigned long long)trials, a.relaxed, none, prod, red, wq, nwg);
+      e.out = flip ? a.qxa : a.qxb;
+      wq -= a.Qt.grid % nwg;
+      wq += wq < 0 ? nwg : 0;
+      product_phase<MODE_PLAIN, true>(a.Q, xn, e, a.uses_q + (unsigned long long)trials, a.relaxed, none, prod, red, wq, nwg);
+    }
     pend = 0;
     product_prefetch(a.T, f, w, nwg);
     PDHG_STAMP(3);
@@ -390,6 +438,12 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
       e.x = x; e.x_next = xn; e.aty = aty; e.aty_next = atyn;
       e.partials = a.pAt; e.stride = a.pAt_stride; e.lo_offset = 3 * a.pAt_stride;
       product_phase<MODE_ATY, true>(a.T, yn, e, a.uses_t + (unsigned long long)trials, a.relaxed, f, prod, red, w, nwg);
+    }
+    if constexpr (QP) {                                      // partials of dx . (Q'dx), block by block as dot_kernel does
+      for (int b = w; b < a.q_blocks; b += nwg) {
+        __syncthreads();
+        dot_body<true>(a.n, a.qtdx, a.dx, a.pq, b, a.q_blocks, red, true);
+      }
     }
     PDHG_STAMP(5);
     // ---- third barrier; its XCD leaders reduce and decide, and the decision IS the release: three words in the
@@ -441,6 +495,8 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
       // one wave per quantity (an LP has four).  The general form (final_reduce_body) was kept beside it as a dev
       // option through round 3: its per-thread index arithmetic is loop-invariant, was hoisted in front of the trial loop
       // and cost 60 of the kernel's spilled registers although it never ran.
+      if constexpr (QP) final_reduce_qp<PDHG_STEPS_LP_BATCH, PDHG_STEPS_QP_PRE>(a.ctl->sp, res, s_res8);
+      else
       final_reduce_lp<PDHG_STEPS_LP_BATCH>(a.ctl->sp, res, s_res8);
       if (threadIdx.x == 0) {
         res[4] *= 0.5;

@@ -89,7 +89,8 @@ __device__ __forceinline__ double bound_at(const BoundView &b, int j) {
 }
 
 // Workgroup `bid` of `nb` (grid-stride; elementwise, so the distribution does not matter for the bits).
-// COH: A'y was written by other compute units since this one last read it (multi-step trial kernel): coherent loads
+// COH: A'y -- and, for a QP, Q x -- was written by other compute units since this one last read it (multi-step trial
+// kernel): coherent loads
 // LBM / UBM: the modes of lb / ub, known at compile time (primal_kernel dispatches on them once per launch; shard
 // slices and the persistent kernels pass DENSE views: the loads they always had)
 template <bool HAS_Q, bool WRITE_XBAR, bool COH = false, int LBM = BND_DENSE, int UBM = BND_DENSE>
@@ -121,7 +122,10 @@ __device__ __forceinline__ void primal_body(
     const double2 lv = bound_pair<LBM>(lb, p);
     const double2 uv = bound_pair<UBM>(ub, p);
     double2 qv = {0.0, 0.0};
-    if (HAS_Q) qv = reinterpret_cast<const double2 *>(qx)[p];
+    if (HAS_Q) {
+      if (COH) { qv.x = ldc<true>(qx + 2 * p); qv.y = ldc<true>(qx + 2 * p + 1); }
+      else qv = reinterpret_cast<const double2 *>(qx)[p];
+    }
     double2 xn, xb;
     primal_one<HAS_Q, WRITE_XBAR>(xv.x, cv.x, av.x, qv.x, lv.x, uv.x, tau, theta, xn.x, xb.x);
     primal_one<HAS_Q, WRITE_XBAR>(xv.y, cv.y, av.y, qv.y, lv.y, uv.y, tau, theta, xn.y, xb.y);
@@ -145,7 +149,7 @@ __device__ __forceinline__ void primal_body(
       sv = sum_x[j] + t;
       if (!sum_x_out) sum_x[j] = sv;
     }
-    primal_one<HAS_Q, WRITE_XBAR>(x[j], c[j], ldc<COH>(aty + j), HAS_Q ? qx[j] : 0.0, bound_at(lb, j), bound_at(ub, j), tau, theta, xn, xb);
+    primal_one<HAS_Q, WRITE_XBAR>(x[j], c[j], ldc<COH>(aty + j), HAS_Q ? ldc<COH>(qx + j) : 0.0, bound_at(lb, j), bound_at(ub, j), tau, theta, xn, xb);
     x_next[j] = xn;
     if (WRITE_XBAR) xbar[j] = xb;
     if (sum_x_out) {
@@ -298,11 +302,13 @@ __global__ __launch_bounds__(TPB) void interaction_kernel(
 }
 
 // dot(a, b) partials (QP term), double-double: block `bid` of `nb` writes partials[bid] (hi) and partials[nb + bid] (lo)
+// COH: a and b were rewritten by other compute units since this one last read them (multi-step trial kernel)
+template <bool COH = false>
 __device__ __forceinline__ void dot_body(int n, const double *a, const double *b, double *partials, int bid, int nb,
                                          double (*red)[TPB / WAVE], bool agent_store) {
   Acc3 acc = acc3_zero();
   const int stride = nb * TPB;
-  for (int j = bid * TPB + threadIdx.x; j < n; j += stride) dd_add(acc.hi[0], acc.lo[0], a[j] * b[j]);
+  for (int j = bid * TPB + threadIdx.x; j < n; j += stride) dd_add(acc.hi[0], acc.lo[0], ldc<COH>(a + j) * ldc<COH>(b + j));
   block_sum_dd<1, TPB>(acc, red);
   if (threadIdx.x == 0) {
     if (agent_store) {
@@ -459,6 +465,60 @@ __device__ __forceinline__ void final_reduce_lp(const FinalSpec &sp, double (&re
 #pragma unroll
     for (int k = 0; k < 4; ++k) res[k] = lds8[k] + lds8[4 + k];
     res[4] = 0.0;
+  }
+}
+
+// The same for a QP: wave q adds quantity q as above, and the fifth quantity, dx . (Q'dx), is added the way
+// final_reduce_body adds it -- waves 0, 1, 2 are its three virtual waves (strided per-lane sums in index order, the wave
+// tree, the three totals left to right) -- so its bits are that function's by construction.  Its first B4 load pairs
+// per lane (all of them up to B4 * 3 * WAVE partials, n <= 147 456) are requested in front of the wave's own quantity.
+// lds14: 14 doubles of LDS.
+template <int B, int B4>
+__device__ __forceinline__ void final_reduce_qp(const FinalSpec &sp, double (&res)[5], double *lds14) {
+  const int wid = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  const double *p4 = sp.ptr[4], *pl4 = sp.ptr_lo[4];
+  const int cnt4 = wid < 3 ? sp.count[4] : 0, i4 = wid * WAVE + lane;
+  double h4[B4], l4[B4];
+#pragma unroll
+  for (int u = 0; u < B4; ++u) {
+    const int i = i4 + u * 3 * WAVE;
+    h4[u] = i < cnt4 ? p4[i] : 0.0;
+    l4[u] = i < cnt4 ? pl4[i] : 0.0;
+  }
+  const double *p = sp.ptr[wid], *pl = sp.ptr_lo[wid];
+  const int cnt = sp.count[wid];
+  double hi = 0.0, lo = 0.0;
+  for (int base = 0; base < cnt; base += B * WAVE) {         // wave-uniform trip count
+    double h[B], l[B];
+#pragma unroll
+    for (int u = 0; u < B; ++u) {
+      const int i = base + lane + u * WAVE;
+      h[u] = i < cnt ? p[i] : 0.0;
+      l[u] = i < cnt ? pl[i] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < B; ++u)
+      if (base + lane + u * WAVE < cnt) dd_add_dd(hi, lo, h[u], l[u]);
+  }
+  wave_sum_dd(hi, lo);
+  if (lane == WAVE - 1) { lds14[wid] = hi; lds14[4 + wid] = lo; }
+  if (wid < 3) {                                              // wave-uniform
+    hi = 0.0; lo = 0.0;
+#pragma unroll
+    for (int u = 0; u < B4; ++u)
+      if (i4 + u * 3 * WAVE < cnt4) dd_add_dd(hi, lo, h4[u], l4[u]);
+    for (int i = i4 + B4 * 3 * WAVE; i < cnt4; i += 3 * WAVE) dd_add_dd(hi, lo, p4[i], pl4[i]);
+    wave_sum_dd(hi, lo);
+    if (lane == WAVE - 1) { lds14[8 + wid] = hi; lds14[11 + wid] = lo; }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) res[k] = lds14[k] + lds14[4 + k];
+    double h = lds14[8], l = lds14[11];
+    dd_add_dd(h, l, lds14[9], lds14[12]);
+    dd_add_dd(h, l, lds14[10], lds14[13]);
+    res[4] = h + l;
   }
 }
 
