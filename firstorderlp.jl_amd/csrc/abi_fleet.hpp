@@ -15,9 +15,9 @@ static void fleet_release(pdhg_handle *h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (pdhg_handle *m : F->mem) destroy_shard(m);
-  for (void *p : {(void *)F->args_dev, (void *)F->qargs_dev, (void *)F->pow_dev})
+  for (void *p : {(void *)F->args_dev, (void *)F->qargs_dev, (void *)F->pow_dev, F->rsv_dev})
     if (p) (void)hipFree(p);
-  for (void *p : {(void *)F->args_host, (void *)F->qargs_host, (void *)F->pow_host, (void *)F->chk_res})
+  for (void *p : {(void *)F->args_host, (void *)F->qargs_host, (void *)F->pow_host, (void *)F->chk_res, F->rsv_host})
     if (p) (void)hipHostFree(p);
   for (FleetState::Table &T : F->chk_table) {
     if (T.dev) (void)hipFree(T.dev);

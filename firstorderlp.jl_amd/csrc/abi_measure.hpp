@@ -376,6 +376,10 @@ static std::string describe_matrix(const pdhg_handle *h, const CsrDev &D0, int m
 // static rules).  Returns the length of the text (without the terminator); writes at most cap - 1 characters + NUL.
 int pdhg_layout_describe(pdhg_handle *h, char *buf, int cap) {
   if (!h) return fail(-1, "null handle");
+  if (h->bnd_dirty && !h->fleet && !h->bat) {      // (a fleet's shared update left the views to their next reader)
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rcb = bounds_fresh(h)) return rcb;
+  }
   std::string out = "{\"A\": " + describe_matrix(h, h->A, MODE_DUAL, 0) + ", \"At\": " + describe_matrix(h, h->At, h->grp ? MODE_PLAIN : MODE_ATY, 1);
   if (h->has_q) out += ", \"Q\": " + describe_matrix(h, h->Q, MODE_PLAIN, 2) + ", \"Qt\": " + describe_matrix(h, h->Qt, MODE_PLAIN, 2);
   if (h->grp && !h->Achunk.empty()) {

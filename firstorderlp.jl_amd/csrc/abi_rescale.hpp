@@ -32,6 +32,25 @@ static void launch_row_op(pdhg_handle *h, const CsrDev &D, int cols, double pexp
 }
 }  // extern "C++"
 
+// Room for `extra` more steps in a retained record (pdhg_resolve_retain, abi_resolve.hpp): pdhg_rescale knows how many
+// steps it will apply.  Grows by a new allocation and a device copy of the steps recorded so far.
+static int resolve_reserve(pdhg_handle *h, int64_t extra) {
+  ResolveState &R = *h->rs;
+  if (R.steps + extra <= R.cap) return 0;
+  const int64_t len = h->n + h->m, cap = R.steps + extra;
+  double *rec = nullptr;
+  HIP_TRY(hipMalloc((void **)&rec, sizeof(double) * (size_t)std::max<int64_t>(cap * len, 1)));
+  if (R.rec && R.steps * len > 0) {
+    hipError_t e = hipMemcpyAsync(rec, R.rec, sizeof(double) * (size_t)(R.steps * len), hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { (void)hipFree(rec); return fail_hip(e, "copying the retained rescaling record"); }
+  }
+  if (R.rec) (void)hipFree(R.rec);
+  R.rec = rec;
+  R.cap = cap;
+  return 0;
+}
+
 // one scale_problem step on every resident layout + the vectors of one shard
 static int apply_scaling(pdhg_handle *h, RescaleTmp &t) {
   const int n = (int)h->n, m = (int)h->m;
@@ -89,6 +108,13 @@ static int apply_scaling(pdhg_handle *h, RescaleTmp &t) {
   }
   hipLaunchKernelGGL(resc_apply_vectors_kernel, dim3(h->ew_grid_nm), dim3(TPB), 0, h->stream, n, m, t.dv, t.ev,
                      h->c, h->lb, h->ub, h->b, t.cum_d, t.cum_e);
+  if (h->rs) {             // retained: this step's factors go into the record, the handle's own running products move with them
+    ResolveState &R = *h->rs;
+    if (R.steps >= R.cap) return fail(-1, "the retained rescaling record is full");
+    hipLaunchKernelGGL(resolve_record_kernel, dim3(h->ew_grid_nm), dim3(TPB), 0, h->stream, n, m, (const double *)t.dv,
+                       (const double *)t.ev, R.rec + R.steps * ((int64_t)n + m), R.cum_d, R.cum_e);
+    R.steps += 1;
+  }
   HIP_TRY(hipGetLastError());
   if (int rcb = bounds_rebuild(h)) return rcb;             // lb / ub were rescaled in place: 0 and +-inf stay, the rest moves
   if (h->bat) return batch_scale_members(h, t.dv, t.ev);   // the same step on every batch member's vectors
@@ -104,6 +130,8 @@ int pdhg_rescale(pdhg_handle *h0, int l_inf_ruiz_iterations, int l2_norm_rescali
   if (use_pock_chambolle && !(pock_chambolle_alpha >= 0.0 && pock_chambolle_alpha <= 2.0))
     return fail(-1, "pock_chambolle_alpha must be in [0, 2]");
   const Shards L = shards_of(h0);
+  if (h0->rs && (rc = resolve_reserve(h0, (int64_t)std::max(l_inf_ruiz_iterations, 0) + (l2_norm_rescaling ? 1 : 0) +
+                                              (use_pock_chambolle ? 1 : 0)))) return rc;
   if ((rc = flush_pending(L))) return rc;
   bump_version(L);
   for (int i = 0; i < L.count; ++i) L.p[i]->matrix_version += 1;

@@ -679,6 +679,7 @@ void destroy_shard(pdhg_handle *h) {
                     h->ev_qx, h->ev_xg};
   for (double *p : bufs) if (p) (void)hipFree(p);
   bounds_free(h);
+  resolve_release(h);
   graph_destroy(h->tgraph[0]); graph_destroy(h->tgraph[1]);
   if (h->comm_stream) { (void)hipStreamSynchronize(h->comm_stream); (void)hipStreamDestroy(h->comm_stream); }
   for (hipEvent_t ev : h->ev_part) if (ev) (void)hipEventDestroy(ev);

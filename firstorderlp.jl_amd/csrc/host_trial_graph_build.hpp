@@ -247,6 +247,7 @@ int graph_build(pdhg_handle *h, pdhg_handle::TrialGraph &G, double tau, double t
 
 int graph_trial(pdhg_handle *h, const TrialArgs &ta, double out[5]) {
   const double tau = ta.step_size / ta.primal_weight, sigma = ta.primal_weight * ta.step_size, theta = ta.theta;
+  if (int rcb = bounds_fresh(h)) return rcb;       // (the primal node carries the views)
   pdhg_handle::TrialGraph *G = nullptr;
   for (int k = 0; k < 2; ++k)
     if (h->tgraph[k].exec && h->tgraph[k].x == h->x && h->tgraph[k].y == h->y && h->tgraph[k].aty == h->aty)

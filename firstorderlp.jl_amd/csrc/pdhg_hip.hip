@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "pdhg_hip.h"
+#include "pdhg_hip_resolve.h"
 
 // The kernels and layout builders live in the headers below; they form ONE
 // translation unit with this file (the tiled kernel is sensitive to code
@@ -52,8 +53,9 @@
 #include "fleet_check_kernels.hpp"
 #include "tr_coop_kernel.hpp"
 #include "batch_kernels.hpp"
+#include "resolve_kernels.hpp"
 
-namespace { struct DistGroup; struct FleetState; }
+namespace { struct DistGroup; struct FleetState; struct ResolveState; }
 struct BatchState;
 
 struct pdhg_handle {
@@ -85,6 +87,11 @@ struct pdhg_handle {
     double *exc = nullptr;
   } bnd[2];
   uint64_t bounds_version = 0;       // bumped by bounds_rebuild: the trial graphs' primal nodes carry the views
+  // a fleet's shared vector update wrote lb / ub and left the views as they were (abi_resolve.hpp): whoever reads
+  // h->bnd next rebuilds them first (bounds_fresh)
+  bool bnd_dirty = false;
+  // re-solves (abi_resolve.hpp): the retained rescaling steps and the staging buffers; nullptr until pdhg_resolve_retain
+  ResolveState *rs = nullptr;
   double *x = nullptr, *x_next = nullptr, *xbar = nullptr;
   double *y = nullptr, *y_next = nullptr;
   double *aty = nullptr, *aty_next = nullptr;  // n+1 each (slot n: exchange scalar)
@@ -514,6 +521,7 @@ void bounds_free(pdhg_handle *h) {
 int bounds_rebuild(pdhg_handle *h) {
   HIP_TRY(hipStreamSynchronize(h->stream));      // a queued primal_kernel may still read the old arrays
   bounds_free(h);
+  h->bnd_dirty = false;
   h->bounds_version += 1;
   const int n = (int)h->n;
   const char *ev = dev_env("PDHG_BOUNDS");
@@ -564,6 +572,15 @@ int bounds_rebuild(pdhg_handle *h) {
   return rc;
 }
 
+// The views of a handle whose lb / ub a fleet's shared update wrote (bnd_dirty), rebuilt where they are next read: before
+// h->bnd goes into a primal_kernel launch or a graph's primal node, and before it is described.
+void resolve_count_view_rebuild(pdhg_handle *h);
+int bounds_fresh(pdhg_handle *h) {
+  if (!h->bnd_dirty) return 0;
+  resolve_count_view_rebuild(h);
+  return bounds_rebuild(h);
+}
+
 BoundView bound_view(const pdhg_handle *h, int k) {
   const pdhg_handle::BoundsDev &B = h->bnd[k];
   BoundView v = bound_dense(k == 0 ? h->lb : h->ub);
@@ -595,6 +612,7 @@ int ensure_pair_buffers(pdhg_handle *h) {
 // pending term and x' * stage_w, and pend_x stays as it is.
 int launch_primal(pdhg_handle *h, double tau, double theta, bool write_xbar, bool stage = false, double stage_w = 0.0) {
   if (!stage) drop_staging(h);
+  if (int rcb = bounds_fresh(h)) return rcb;
   ProfScope ps(h, PDHG_K_PRIMAL);
   if (h->has_q) {
     EpiArgs e{};
@@ -931,4 +949,5 @@ static int batch_scale_members(pdhg_handle *h, const double *dv, const double *e
 #include "abi_batch.hpp"
 #include "abi_fleet.hpp"
 #include "abi_fleet_checks.hpp"
+#include "abi_resolve.hpp"
 }  // extern "C"

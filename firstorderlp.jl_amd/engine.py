@@ -341,6 +341,47 @@ class HipPdhgEngine:
         _lib.check(self._L.pdhg_matrix_max_abs(self._h, _pd(out)))
         return float(out[0])
 
+    # ---- re-solves on the live handle (include/pdhg_hip_resolve.h) ----------------
+    def _live(self):
+        if not getattr(self, "_h", None):
+            raise _lib.PdhgHipError("the engine is closed")
+        return self._h
+
+    def _vector(self, name, value, length):
+        """``value`` as a contiguous float64 vector of ``length`` entries (None stays None), checked on the host."""
+        if value is None:
+            return None
+        value = _d(value)
+        if value.shape != (length,):
+            raise ValueError(f"{name} has {value.shape} entries, the problem needs ({length},)")
+        return value
+
+    def retain_rescaling(self):
+        """``pdhg_resolve_retain``: to be called before ``rescale``.  From then on the handle keeps every rescaling
+        step's factors (8 * steps * (n + m) bytes of device memory), which ``update_problem_vectors`` and
+        ``warm_start`` need."""
+        _lib.check(self._L.pdhg_resolve_retain(self._live()))
+
+    def update_problem_vectors(self, objective_vector=None, right_hand_side=None, variable_lower_bound=None,
+                               variable_upper_bound=None):
+        """``pdhg_update_problem_vectors``: new vectors of the ORIGINAL problem (the space the engine was created in);
+        ``None`` keeps a vector.  The working vectors become, bit for bit, those of a fresh engine created from the
+        updated problem and rescaled with the same parameters."""
+        h = self._live()
+        c = self._vector("objective_vector", objective_vector, self.n)
+        b = self._vector("right_hand_side", right_hand_side, self.m)
+        lb = self._vector("variable_lower_bound", variable_lower_bound, self.n)
+        ub = self._vector("variable_upper_bound", variable_upper_bound, self.n)
+        _lib.check(self._L.pdhg_update_problem_vectors(h, _pd(c), _pd(b), _pd(lb), _pd(ub)))
+
+    def warm_start(self, x=None, y=None):
+        """``pdhg_warm_start``: start from the point (x, y) of the ORIGINAL problem's space (``None``: zeros) with
+        everything else as on a fresh engine -- empty averages, zero restart point, no pending accept."""
+        h = self._live()
+        x = self._vector("x", x, self.n)
+        y = self._vector("y", y, self.m)
+        _lib.check(self._L.pdhg_warm_start(h, _pd(x), _pd(y)))
+
     # ---- evaluation branch on the device -------------------------------------------
     supports_device_evaluation = True
 

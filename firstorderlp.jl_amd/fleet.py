@@ -26,12 +26,12 @@ import time as _time
 import numpy as np
 
 from . import _lib
-from .engine import _int_p, _MemberEngine, _MemberOwner, _d, _i, _pd, _pi
+from .engine import _dp, _int_p, _MemberEngine, _MemberOwner, _d, _i, _pd, _pi
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams,
                                           MalitskyPockStepsizeParameters, _check_inputs, _constant_step_estimate,
-                                          _device_scaled_problem, _drive_solves, _host_scaled_problem, _pack_ratios,
-                                          _pack_step_states, _rescales_on_device, _Solve, _unpack_step_states,
-                                          take_steps)
+                                          _device_scaled_problem, _drive_solves, _host_scaled_problem, _initial_point,
+                                          _pack_ratios, _pack_step_states, _rescales_on_device, _set_initial_point,
+                                          _Solve, _unpack_step_states, take_steps)
 
 
 class HipPdhgFleet(_MemberOwner):
@@ -152,6 +152,57 @@ class HipPdhgFleet(_MemberOwner):
         _lib.check(self._L.pdhg_fleet_info(self._h, _pi(info)))
         return dict(zip(["check_launches", "carried", "single", "misses"], info[4:8].tolist()))
 
+    # ---- re-solves in shared launches (include/pdhg_hip_resolve.h) ----
+    def _pointer_table(self, name, values, lengths):
+        """An array of K pointers (NULL: the member's entry is None) over ``values`` = None or a list of K vectors /
+        None; also returns the arrays, which must outlive the call."""
+        if not getattr(self, "_h", None):
+            raise _lib.PdhgHipError("the fleet is closed")
+        if values is None:
+            return None, []
+        values = list(values)
+        if len(values) != self.K:
+            raise ValueError(f"{name} has {len(values)} entries, the fleet has {self.K} members")
+        keep = []
+        table = (_dp * self.K)()
+        for k, (v, length) in enumerate(zip(values, lengths)):
+            if v is None:
+                continue
+            v = _d(v)
+            if v.shape != (length,):
+                raise ValueError(f"{name}[{k}] has {v.shape} entries, member {k} needs ({length},)")
+            keep.append(v)
+            table[k] = v.ctypes.data_as(_dp)
+        return table, keep
+
+    def update_problem_vectors(self, objective_vectors=None, right_hand_sides=None, variable_lower_bounds=None,
+                               variable_upper_bounds=None):
+        """``members[k].update_problem_vectors(...)`` for every k, all in ONE launch: each argument is None or a list
+        of K vectors / None (None: keep).  A member whose bounds were given rebuilds its compact bound views where they
+        are next read."""
+        ns, ms = [e.n for e in self.members], [e.m for e in self.members]
+        tables = [self._pointer_table(name, v, lens) for name, v, lens in (
+            ("objective_vectors", objective_vectors, ns), ("right_hand_sides", right_hand_sides, ms),
+            ("variable_lower_bounds", variable_lower_bounds, ns), ("variable_upper_bounds", variable_upper_bounds, ns))]
+        _lib.check(self._L.pdhg_fleet_update_problem_vectors(self._h, *[t for t, _ in tables]))
+
+    def warm_start(self, xs=None, ys=None):
+        """``members[k].warm_start(xs[k], ys[k])`` for every k in ONE launch.  A member whose two entries are None is
+        left as it is; ``xs`` and ``ys`` both None: every member starts from zeros."""
+        ns, ms = [e.n for e in self.members], [e.m for e in self.members]
+        tx, ty = self._pointer_table("xs", xs, ns), self._pointer_table("ys", ys, ms)
+        _lib.check(self._L.pdhg_fleet_warm_start(self._h, tx[0], ty[0]))
+
+    def resolve_info(self):
+        """dict(shared_launches, carried, single, view_rebuilds): shared re-solve launches so far; members the last
+        ``update_problem_vectors`` / ``warm_start`` carried; members the last ``warm_start`` gave a product of their
+        own; lazy rebuilds of bound views so far."""
+        if not getattr(self, "_h", None):
+            raise _lib.PdhgHipError("the fleet is closed")
+        info = np.zeros(4, dtype=np.int64)
+        _lib.check(self._L.pdhg_fleet_resolve_info(self._h, _pi(info)))
+        return dict(zip(["shared_launches", "carried", "single", "view_rebuilds"], info.tolist()))
+
 
 def _default_fleet_factory(problems):
     return HipPdhgFleet.from_problems(problems)
@@ -224,7 +275,7 @@ def _fleet_checks(fleet, solves, pending):
         fleet.trust_region_bounds(items)
 
 
-def optimize_many(params, problems, fleet_factory=None):
+def optimize_many(params, problems, fleet_factory=None, initial_solutions=None):
     """``optimize(params, problems[k])`` for every k, side by side: a list of ``SaddlePointOutput`` in input order.
 
     Anything ``optimize`` accepts: any mix of shapes, LPs and QPs, every step-size policy, any number of problems (an
@@ -235,11 +286,21 @@ def optimize_many(params, problems, fleet_factory=None):
     optionally, ``take_steps_adaptive`` / ``take_steps_constant`` / ``take_steps_malitsky_pock`` and the pair
     ``eval_points`` / ``trust_region_bounds`` (the checks in shared launches); a factory whose
     ``takes_original_problem`` is true receives the original problems and every member rescales on the device, any other
-    one receives the host-rescaled problems."""
+    one receives the host-rescaled problems.
+
+    ``initial_solutions``: ``None`` (every problem starts from zeros, the path as it always was) or one entry per
+    problem -- ``None`` or ``(x0, y0)``, a starting point in the original problem's space with ``optimize``'s
+    semantics (``initial_primal_solution`` / ``initial_dual_solution``)."""
     problems = list(problems)
     if not problems:
         raise ValueError("optimize_many needs at least one problem")
     _check_inputs(params, problems)
+    points = [None] * len(problems)
+    if initial_solutions is not None:
+        initial_solutions = list(initial_solutions)
+        if len(initial_solutions) != len(problems):
+            raise ValueError(f"initial_solutions has {len(initial_solutions)} entries for {len(problems)} problems")
+        points = [None if pt is None else _initial_point(p, *pt) for p, pt in zip(problems, initial_solutions)]
     policy = params.step_size_policy_params
     factory = fleet_factory or _default_fleet_factory
     fleet = None
@@ -255,6 +316,9 @@ def optimize_many(params, problems, fleet_factory=None):
             scaled, max_abs = zip(*[_host_scaled_problem(params, p) for p in problems])
             fleet = factory([s.scaled_qp for s in scaled])
         solves = [_Solve(params, p, s, eng, a) for p, s, eng, a in zip(problems, scaled, fleet.members, max_abs)]
+        for mb, point in zip(solves, points):
+            if point is not None:
+                _set_initial_point(mb.engine, mb.scaled_problem, point)
         for mb in solves:
             mb.start(_constant_step_estimate(mb) if isinstance(policy, ConstantStepsizeParams) else None)
         checks = None

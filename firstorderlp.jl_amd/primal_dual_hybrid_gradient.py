@@ -635,15 +635,70 @@ def _drive_solves(solves, step, checks=None):
     return [mb.output for mb in solves]
 
 
-def optimize(params, original_problem, engine_factory=None):
+def _initial_point(problem, initial_primal_solution, initial_dual_solution):
+    """The starting point of a warm solve, checked on the host before any device work: ``(x0, y0)`` as float64
+    vectors (``None`` stays ``None``: zeros), or ``None`` when neither was given.  Wrong lengths and entries that are
+    not finite raise ``ValueError``."""
+    if initial_primal_solution is None and initial_dual_solution is None:
+        return None
+    m, n = problem.constraint_matrix.shape
+    point = []
+    for name, value, length in (("initial_primal_solution", initial_primal_solution, n),
+                                ("initial_dual_solution", initial_dual_solution, m)):
+        if value is not None:
+            value = np.ascontiguousarray(value, dtype=np.float64)
+            if value.shape != (length,):
+                raise ValueError(f"{name} has shape {value.shape}, the problem needs ({length},)")
+            if not np.all(np.isfinite(value)):
+                raise ValueError(f"{name} holds entries that are not finite")
+        point.append(value)
+    return tuple(point)
+
+
+def _set_initial_point(engine, scaled_problem, point):
+    """A fresh engine's iterate at ``point`` (original space): scaled on the host -- the output divides by the same
+    factors -- and handed to ``engine.set_current``, which also computes A'y."""
+    x0, y0 = point
+    engine.set_current(None if x0 is None else x0 * scaled_problem.variable_rescaling,
+                       None if y0 is None else y0 * scaled_problem.constraint_rescaling)
+
+
+def _step_solves(policy, requests):
+    """``_drive_solves``' step for solves that are stepped one by one through ``take_steps``."""
+    out = []
+    for mb, steps in requests:
+        time_spent_doing_basic_algorithm_checkpoint = _time.time()
+        steps_taken = take_steps(policy, mb.state, steps, mb.is_lp)
+        out.append((mb, steps_taken, _time.time() - time_spent_doing_basic_algorithm_checkpoint))
+    return out
+
+
+def _drive_solve(solve):
+    """One started solve to its end: the loop of the reference's ``optimize`` (pdhg.jl:862-1049) -- evaluate, take the
+    steps up to the next evaluation, until the evaluation terminates.  ``optimize`` and ``session.PdhgSession.solve``
+    run this."""
+    policy = solve.params.step_size_policy_params
+    return _drive_solves([solve], lambda requests: _step_solves(policy, requests))[0]
+
+
+def optimize(params, original_problem, engine_factory=None, initial_primal_solution=None, initial_dual_solution=None):
     """``optimize(params::PdhgParameters, original_problem)`` -- pdhg.jl:782-1049.
 
     ``engine_factory(problem) -> engine`` builds the device state; the default is the HIP engine on the current GPU
     and there is no CPU fallback.  A factory whose ``takes_original_problem`` is true (the default is one) receives
     the original problem and rescales it on the device, any other one the host-rescaled problem.
+
+    ``initial_primal_solution`` / ``initial_dual_solution``: a starting point in the ORIGINAL problem's space (either
+    may be ``None``: zeros; both ``None``, the default: the reference's cold start, untouched).  The reference has no
+    warm start to follow: the point replaces the zeros of ``PdhgSolverState`` (pdhg.jl:805-819) and nothing else
+    changes -- the step size, the primal weight and ``cumulative_kkt_passes`` start exactly as in a cold solve, the
+    averages are empty (so the first evaluation looks at the point itself), and the point is not projected: the
+    first step's projections do that.  Lengths and finiteness are checked before any device work.
+
     Returns a ``SaddlePointOutput``.  The engine (device memory) is released on every exit path, exceptions
     included."""
     _check_inputs(params, [original_problem])
+    point = _initial_point(original_problem, initial_primal_solution, initial_dual_solution)
     factory = engine_factory or _default_engine_factory
     engine = None
     try:
@@ -658,15 +713,11 @@ def optimize(params, original_problem, engine_factory=None):
             scaled_problem, matrix_max_abs = _host_scaled_problem(params, original_problem)
             engine = factory(scaled_problem.scaled_qp)
         solve = _Solve(params, original_problem, scaled_problem, engine, matrix_max_abs)
+        if point is not None:
+            _set_initial_point(engine, scaled_problem, point)
         policy = params.step_size_policy_params
         solve.start(_constant_step_estimate(solve) if isinstance(policy, ConstantStepsizeParams) else None)
-        while True:
-            steps = solve.evaluate()
-            if steps == 0:
-                return solve.output
-            time_spent_doing_basic_algorithm_checkpoint = _time.time()
-            steps_taken = take_steps(policy, solve.state, steps, solve.is_lp)
-            solve.stepped(steps_taken, _time.time() - time_spent_doing_basic_algorithm_checkpoint)
+        return _drive_solve(solve)
     finally:
         if engine is not None and hasattr(engine, "close"):
             engine.close()

@@ -1,0 +1,323 @@
+"""Re-solves on a live handle: the same matrix again and again with other vectors, starting near the last answer.
+
+``optimize`` creates the device state, rescales, solves and frees everything.  A model-predictive controller with a new
+right-hand side every tick, branch-and-bound nodes that differ in a few bounds, a scenario set or a regularization path
+would repeat the create and the rescaling -- layout builders, create-time kernel timing, a dozen rescaling passes over
+every copy of the matrix -- for work that depends on the matrix only.  A session does that work once:
+
+    with PdhgSession(params, problem) as session:
+        first = session.solve()
+        session.update(right_hand_side=b_next)
+        second = session.solve(warm_start=True)        # from the first solve's solution
+
+``PdhgSession.solve()`` returns what ``optimize(params, <the problem as updated>)`` returns, bit for bit -- and
+``solve(warm_start=(x0, y0))`` what ``optimize(..., initial_primal_solution=x0, initial_dual_solution=y0)`` returns: the
+library replays the recorded rescaling steps on the new vectors (include/pdhg_hip_resolve.h) and empties everything a
+fresh handle has empty.  ``PdhgFleetSession`` is the same over a fleet (``fleet.optimize_many``): updates and warm starts
+of all members in one launch each.
+
+The reference has no warm start: a warm solve differs from a cold one in the starting point alone (see ``optimize``).
+"""
+import dataclasses
+
+import numpy as np
+
+from .fleet import _default_fleet_factory, _fleet_checks, _step_fleet
+from .preprocess import validate
+from .primal_dual_hybrid_gradient import (ConstantStepsizeParams, _check_inputs, _constant_step_estimate,
+                                          _default_engine_factory, _device_scaled_problem, _drive_solve, _drive_solves,
+                                          _host_scaled_problem, _initial_point, _rescales_on_device, _Solve)
+
+_UPDATE_FIELDS = ("objective_vector", "right_hand_side", "variable_lower_bound", "variable_upper_bound")
+
+
+def _updated_problem(problem, objective_vector=None, right_hand_side=None, variable_lower_bound=None,
+                     variable_upper_bound=None):
+    """``problem`` with the given vectors replaced, validated on the host (``validate``, and no lower bound above its
+    upper bound); ``problem`` itself is not touched.  Returns (updated problem, {field: new vector})."""
+    given = {k: v for k, v in zip(_UPDATE_FIELDS, (objective_vector, right_hand_side, variable_lower_bound,
+                                                   variable_upper_bound)) if v is not None}
+    changes = {}
+    for name, value in given.items():
+        value = np.array(value, dtype=np.float64).reshape(-1)
+        if value.shape != getattr(problem, name).shape:
+            raise ValueError(f"{name} has shape {value.shape}, the problem needs {getattr(problem, name).shape}")
+        changes[name] = value
+    updated = dataclasses.replace(problem, **changes)
+    validate(updated)
+    if np.any(updated.variable_lower_bound > updated.variable_upper_bound):
+        raise ValueError("the update leaves a variable_lower_bound above its variable_upper_bound")
+    return updated, changes
+
+
+def _warm_point(problem, warm_start, last):
+    """``solve``'s ``warm_start`` argument as ``_initial_point``'s result: None (zeros), True (``last``, the previous
+    solve's solution) or (x0, y0)."""
+    if warm_start is None or warm_start is False:
+        return None
+    if warm_start is True:
+        if last is None:
+            raise ValueError("warm_start=True needs a solve before it")
+        warm_start = last
+    x0, y0 = warm_start
+    return _initial_point(problem, x0, y0)
+
+
+class _Member:
+    """One problem of a session on its engine: created, retained, rescaled; its current problem and scaled problem."""
+
+    def __init__(self, params, problem, engine, on_device, host_scaled=None):
+        self.params, self.problem, self.engine, self.on_device = params, problem, engine, on_device
+        self.last = None
+        self.estimate = None
+        if hasattr(engine, "retain_rescaling"):
+            engine.retain_rescaling()
+        if on_device:
+            self.E, self.D = engine.rescale(params.l_inf_ruiz_iterations, params.l2_norm_rescaling,
+                                            params.pock_chambolle_alpha)
+            self.scaled_problem = _device_scaled_problem(problem, engine, self.E, self.D)
+            self.matrix_max_abs = engine.matrix_max_abs()
+        else:
+            self.scaled_problem, self.matrix_max_abs = host_scaled
+
+    def staged_update(self, **vectors):
+        """The update checked and prepared on the host, nothing changed yet: (updated problem, changes, scaled problem
+        of the host route or None)."""
+        updated, changes = _updated_problem(self.problem, **vectors)
+        host_scaled = None if self.on_device else _host_scaled_problem(self.params, updated)[0]
+        return updated, changes, host_scaled
+
+    def engine_vectors(self, changes, host_scaled):
+        """What the engine's ``update_problem_vectors`` takes for ``changes``: the new vectors themselves on the device
+        route (the library replays its rescaling on them), their host-rescaled form otherwise."""
+        if self.on_device:
+            return {k: changes.get(k) for k in _UPDATE_FIELDS}
+        return {k: (getattr(host_scaled.scaled_qp, k) if k in changes else None) for k in _UPDATE_FIELDS}
+
+    def committed(self, updated, host_scaled):
+        self.problem = updated
+        if self.on_device:
+            self.scaled_problem = _device_scaled_problem(updated, self.engine, self.E, self.D)
+        else:
+            self.scaled_problem = host_scaled
+
+    def engine_point(self, point):
+        """``point`` (original space) as the engine's ``warm_start`` takes it: the library scales on the device route."""
+        x0, y0 = point if point is not None else (None, None)
+        if self.on_device:
+            return x0, y0
+        sp = self.scaled_problem
+        return (None if x0 is None else x0 * sp.variable_rescaling, None if y0 is None else y0 * sp.constraint_rescaling)
+
+    def new_solve(self):
+        """A fresh host-side solve on the live engine (host state, ``qp_cache``, evaluator, primal weight from the
+        current scaled vectors), started; the engine has been warm-started."""
+        solve = _Solve(self.params, self.problem, self.scaled_problem, self.engine, self.matrix_max_abs)
+        if isinstance(self.params.step_size_policy_params, ConstantStepsizeParams):
+            # the power method sees the matrix only: estimated once; its passes count in every solve, as in a fresh one
+            if self.estimate is None:
+                self.estimate = _constant_step_estimate(solve)
+            solve.start(self.estimate)
+        else:
+            solve.start(None)
+        return solve
+
+    def solved(self, output):
+        self.last = (output.primal_solution, output.dual_solution)
+        return output
+
+
+class PdhgSession:
+    """One problem kept on the device across solves.
+
+    ``PdhgSession(params, problem, engine_factory=None)`` creates the engine, retains the rescaling steps, rescales and
+    measures the matrix once.  ``engine_factory`` as in ``optimize``; an engine of another kind must offer
+    ``update_problem_vectors(objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound)`` and
+    ``warm_start(x, y)`` in ITS problem's space (a factory that does not rescale on the device gets host-rescaled
+    vectors and points)."""
+
+    def __init__(self, params, problem, engine_factory=None):
+        _check_inputs(params, [problem])
+        factory = engine_factory or _default_engine_factory
+        self.params = params
+        self._member = None
+        on_device = _rescales_on_device(factory)
+        engine = None
+        try:
+            if on_device:
+                engine = factory(problem)
+                self._member = _Member(params, problem, engine, True)
+            else:
+                host_scaled = _host_scaled_problem(params, problem)
+                engine = factory(host_scaled[0].scaled_qp)
+                self._member = _Member(params, problem, engine, False, host_scaled)
+        except Exception:
+            if engine is not None and hasattr(engine, "close"):
+                engine.close()
+            raise
+
+    @property
+    def problem(self):
+        """The problem as updated so far."""
+        return self._live().problem
+
+    @property
+    def engine(self):
+        return self._live().engine
+
+    def _live(self):
+        if self._member is None:
+            raise RuntimeError("the session is closed")
+        return self._member
+
+    def update(self, objective_vector=None, right_hand_side=None, variable_lower_bound=None, variable_upper_bound=None):
+        """New vectors of the problem (``None``: keep).  The updated problem is validated before any device work; if
+        that raises, the session is as it was."""
+        mb = self._live()
+        updated, changes, host_scaled = mb.staged_update(
+            objective_vector=objective_vector, right_hand_side=right_hand_side,
+            variable_lower_bound=variable_lower_bound, variable_upper_bound=variable_upper_bound)
+        if changes:
+            mb.engine.update_problem_vectors(**mb.engine_vectors(changes, host_scaled))
+        mb.committed(updated, host_scaled)
+
+    def solve(self, warm_start=None):
+        """Solve the problem as updated so far: ``None`` from zeros, ``True`` from the previous solve's solution,
+        ``(x0, y0)`` from that point (either may be ``None``: zeros).  Returns a ``SaddlePointOutput``."""
+        mb = self._live()
+        point = _warm_point(mb.problem, warm_start, mb.last)
+        mb.engine.warm_start(*mb.engine_point(point))
+        return mb.solved(_drive_solve(mb.new_solve()))
+
+    def close(self):
+        mb, self._member = self._member, None
+        if mb is not None and hasattr(mb.engine, "close"):
+            mb.engine.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PdhgFleetSession:
+    """Many independent problems kept on the device across solves: ``PdhgSession`` over a fleet
+    (``fleet.optimize_many``).  A fleet with ``update_problem_vectors`` / ``warm_start`` of its own (``HipPdhgFleet``)
+    takes the updates and the warm starts of all members in one launch each; any other fleet member by member."""
+
+    def __init__(self, params, problems, fleet_factory=None):
+        problems = list(problems)
+        if not problems:
+            raise ValueError("a fleet session needs at least one problem")
+        _check_inputs(params, problems)
+        factory = fleet_factory or _default_fleet_factory
+        self.params = params
+        self._fleet = None
+        self._members = None
+        on_device = _rescales_on_device(factory)
+        fleet = None
+        try:
+            if on_device:
+                fleet = factory(problems)
+                self._members = [_Member(params, p, eng, True) for p, eng in zip(problems, fleet.members)]
+            else:
+                host_scaled = [_host_scaled_problem(params, p) for p in problems]
+                fleet = factory([s.scaled_qp for s, _ in host_scaled])
+                self._members = [_Member(params, p, eng, False, hs)
+                                 for p, eng, hs in zip(problems, fleet.members, host_scaled)]
+            self._fleet = fleet
+        except Exception:
+            self._members = None
+            if fleet is not None and hasattr(fleet, "close"):
+                fleet.close()
+            raise
+
+    @property
+    def fleet(self):
+        self._live()
+        return self._fleet
+
+    @property
+    def problems(self):
+        return [mb.problem for mb in self._live()]
+
+    def _live(self):
+        if self._members is None:
+            raise RuntimeError("the session is closed")
+        return self._members
+
+    def update(self, updates):
+        """``updates``: one entry per problem -- ``None`` (keep the problem) or a dict with any of ``objective_vector``,
+        ``right_hand_side``, ``variable_lower_bound``, ``variable_upper_bound``.  Every updated problem is validated
+        before any device work; if one raises, the session is as it was."""
+        members = self._live()
+        updates = list(updates)
+        if len(updates) != len(members):
+            raise ValueError(f"updates has {len(updates)} entries for {len(members)} problems")
+        staged = [None if u is None else mb.staged_update(**u) for mb, u in zip(members, updates)]
+        vectors = [None if st is None or not st[1] else mb.engine_vectors(st[1], st[2]) for mb, st in zip(members, staged)]
+        if any(v is not None for v in vectors):
+            if hasattr(self._fleet, "update_problem_vectors"):
+                self._fleet.update_problem_vectors(*[[None if v is None else v[k] for v in vectors] for k in _UPDATE_FIELDS])
+            else:
+                for mb, v in zip(members, vectors):
+                    if v is not None:
+                        mb.engine.update_problem_vectors(**v)
+        for mb, st in zip(members, staged):
+            if st is not None:
+                mb.committed(st[0], st[2])
+
+    def solve(self, warm_start=None):
+        """Solve every problem as updated so far; returns what ``optimize_many`` returns.  ``warm_start``: ``None``
+        (everyone from zeros), ``True`` (everyone from its previous solution) or a list with one entry per problem --
+        ``None`` (zeros) or ``(x0, y0)``."""
+        members = self._live()
+        if warm_start is None or warm_start is True:
+            warm_start = [warm_start] * len(members)
+        warm_start = list(warm_start)
+        if len(warm_start) != len(members):
+            raise ValueError(f"warm_start has {len(warm_start)} entries for {len(members)} problems")
+        points = [mb.engine_point(_warm_point(mb.problem, w, mb.last)) for mb, w in zip(members, warm_start)]
+        if hasattr(self._fleet, "warm_start"):
+            if all(x is None and y is None for x, y in points):
+                self._fleet.warm_start(None, None)
+            else:
+                # a member whose two entries are None would be left as it is: zeros are given as zeros
+                xs = [np.zeros(mb.engine.n) if x is None and y is None else x for mb, (x, y) in zip(members, points)]
+                self._fleet.warm_start(xs, [y for _, y in points])
+        else:
+            for mb, (x, y) in zip(members, points):
+                mb.engine.warm_start(x, y)
+        fleet, policy = self._fleet, self.params.step_size_policy_params
+        solves = [mb.new_solve() for mb in members]
+        checks = None
+        if hasattr(fleet, "eval_points") and hasattr(fleet, "trust_region_bounds"):
+            checks = lambda pending: _fleet_checks(fleet, solves, pending)      # noqa: E731
+        outputs = _drive_solves(solves, lambda requests: _step_fleet(fleet, solves, policy, requests), checks)
+        return [mb.solved(out) for mb, out in zip(members, outputs)]
+
+    def close(self):
+        fleet, self._fleet, self._members = self._fleet, None, None
+        if fleet is not None and hasattr(fleet, "close"):
+            fleet.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

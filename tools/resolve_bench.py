@@ -1,0 +1,203 @@
+"""What a re-solve on a live handle saves: a series of ticks, each with a new right-hand side, solved three ways.
+
+    python tools/resolve_bench.py [--shapes netlib27x32,netlib56x97,random1000x800] [--ks 64,256] [--single l1svm,pagerank1m]
+                                  [--ticks 20] [--reps 5] [--iteration-limit 5000] [--profile-k 256] [--no-profile]
+                                  [--out profiles/resolve_throughput.txt]
+
+At every tick the right-hand side of every problem is perturbed by 1 % (a fixed seed per tick and member).  Per tick:
+
+  (a) the existing route: `optimize_many(params, updated)` for a fleet, `optimize(params, updated)` for a single problem --
+      create and rescale again.  The baseline; it runs code this tool does not touch.
+  (b) session update + cold solve (`PdhgFleetSession` / `PdhgSession`): what create and rescale cost.
+  (c) session update + warm solve, from the previous tick's solution.
+
+Fleet members: tools/fleet_bench.py's (`random_lp` of the shape, a distinct seed per member); single problems: the
+L1-SVM substitute and the 1M-node PageRank LP of the README.  Parameters: solve_qp's defaults (Ruiz-10 +
+Pock-Chambolle, adaptive steps, adaptive-normalized restarts, an evaluation every 40 iterations, tolerance 1e-6).
+Reported: wall ms per tick and iterations per solve (mean over ticks and members), best of `reps` series with the
+spread (worst / best) of the repetitions; routes (a) and (b) must give the same iteration counts (same bits).  The
+session is created once per repetition, outside the timed ticks (its first solve is the warm-up).
+
+Also the kernel durations of the shared update and warm-start launches (fleet_resolve_replay_kernel,
+fleet_resolve_point_kernel) at --profile-k members, from a `rocprofv3 --kernel-trace --stats` run of a child process of
+its own, with no counters.
+"""
+import argparse
+import dataclasses
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+KERNELS = ("fleet_resolve_replay_kernel", "fleet_resolve_point_kernel", "resolve_replay_kernel", "resolve_point_kernel")
+
+
+def single_problem(name):
+    from firstorderlp_jl_amd.generators import l1_svm_rcv1_like_lp, pagerank_lp
+    if name == "l1svm":
+        return l1_svm_rcv1_like_lp()
+    if name == "pagerank1m":
+        return pagerank_lp(1_000_000, seed=1)
+    raise ValueError(f"unknown problem {name}")
+
+
+def tick_rhs(problem, tick, member):
+    rng = np.random.default_rng([tick, member, 1234])
+    return problem.right_hand_side * (1.0 + 0.01 * rng.uniform(-1.0, 1.0, problem.num_constraints))
+
+
+def _iterations(outs):
+    return float(np.mean([o.iteration_count for o in outs]))
+
+
+def series(problems, params, ticks, route, single):
+    """One series of `ticks` ticks by `route` ('a', 'b', 'c'): (seconds per tick, iterations per solve)."""
+    from firstorderlp_jl_amd import PdhgFleetSession, PdhgSession, optimize_many
+    from firstorderlp_jl_amd.primal_dual_hybrid_gradient import optimize
+    seconds, iterations = [], []
+    session = None
+    try:
+        if route != "a":
+            session = PdhgSession(params, problems[0]) if single else PdhgFleetSession(params, problems)
+            session.solve()
+        for tick in range(ticks):
+            rhs = [tick_rhs(p, tick, k) for k, p in enumerate(problems)]
+            updated = [dataclasses.replace(p, right_hand_side=b) for p, b in zip(problems, rhs)] if route == "a" else None
+            t0 = time.perf_counter()
+            if route == "a":
+                outs = [optimize(params, updated[0])] if single else optimize_many(params, updated)
+            elif single:
+                session.update(right_hand_side=rhs[0])
+                outs = [session.solve(warm_start=True if route == "c" else None)]
+            else:
+                session.update([{"right_hand_side": b} for b in rhs])
+                outs = session.solve(warm_start=True if route == "c" else None)
+            seconds.append(time.perf_counter() - t0)
+            iterations.append(_iterations(outs))
+    finally:
+        if session is not None:
+            session.close()
+    return float(np.mean(seconds)), float(np.mean(iterations))
+
+
+def measure(problems, params, ticks, reps, single):
+    """{route: (best ms per tick, worst / best over the repetitions, iterations per solve)}, the routes alternating."""
+    runs = {r: [] for r in "abc"}
+    for _ in range(reps):
+        for route in "abc":
+            runs[route].append(series(problems, params, ticks, route, single))
+    out = {}
+    for route, rs in runs.items():
+        secs = [s for s, _ in rs]
+        out[route] = (1e3 * min(secs), max(secs) / min(secs), rs[0][1])
+    return out
+
+
+def child(shape, K, ticks):
+    """What the profiled child runs: a fleet session, `ticks` updates and warm solves with a short iteration limit."""
+    from fleet_bench import members, solve_params
+    from firstorderlp_jl_amd import PdhgFleetSession
+    problems = members(shape, K)
+    with PdhgFleetSession(solve_params(80), problems) as session:
+        session.solve()
+        for tick in range(ticks):
+            session.update([{"right_hand_side": tick_rhs(p, tick, k)} for k, p in enumerate(problems)])
+            session.solve(warm_start=True)
+
+
+def kernel_us(shape, K, ticks=4, timeout=400):
+    """{kernel: (calls, average us)} of the re-solve kernels in a `rocprofv3 --kernel-trace --stats` run of a child of its
+    own, or a string saying why there is none."""
+    from rocprof_summary import summarize
+    rp = shutil.which("rocprofv3")
+    if not rp:
+        return "rocprofv3 not on PATH"
+    work = tempfile.mkdtemp(prefix="pdhg_resolve_prof_", dir="/tmp")
+    try:
+        cmd = [rp, "--kernel-trace", "--stats", "-d", work, "--", sys.executable, os.path.abspath(__file__), "--child", shape, str(K), str(ticks)]
+        r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), timeout=timeout, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
+        if r.returncode != 0:
+            return f"profiled child failed ({r.returncode}): {r.stderr.decode(errors='replace')[-200:]}"
+        out = {}
+        for k in summarize(work):
+            hit = re.search(r"\b(" + "|".join(KERNELS) + r")\(", k["name"])
+            if hit:
+                out[hit.group(1)] = (k.get("calls"), k["avg_us"])
+        return out or "no re-solve kernel in the trace"
+    except subprocess.TimeoutExpired:
+        return f"profiled child timed out after {timeout} s"
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="netlib27x32,netlib56x97,random1000x800")
+    ap.add_argument("--ks", default="64,256")
+    ap.add_argument("--single", default="l1svm,pagerank1m")
+    ap.add_argument("--ticks", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--iteration-limit", type=int, default=5000)
+    ap.add_argument("--profile-k", type=int, default=256)
+    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", nargs=3, default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args(argv)
+    import folp_loader
+    folp_loader.load()
+    from fleet_bench import members, solve_params
+    if args.child:
+        child(args.child[0], int(args.child[1]), int(args.child[2]))
+        return
+    params = solve_params(args.iteration_limit)
+    lines = []
+
+    def emit(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    emit(f"# tools/resolve_bench.py --shapes {args.shapes} --ks {args.ks} --single {args.single} --ticks {args.ticks} --reps {args.reps} "
+         f"--iteration-limit {args.iteration_limit}")
+    emit("# per tick: b perturbed by 1 %; (a) optimize / optimize_many on the updated problems (create + rescale again), (b) session "
+         "update + cold solve, (c) session update + warm solve from the last solution")
+    emit("# ms per tick: best series of `reps` (mean over its ticks); spread: worst / best series; it: iterations per solve")
+    emit(f"{'problem':<15} {'K':>5} {'(a) ms':>9} {'spread':>6} {'it':>7} {'(b) ms':>9} {'spread':>6} {'it':>7} {'(c) ms':>9} {'spread':>6} {'it':>7} "
+         f"{'a/b':>6} {'a/c':>6}")
+
+    def row(name, K, problems, single):
+        got = measure(problems, params, args.ticks, args.reps, single)
+        a, b, c = got["a"], got["b"], got["c"]
+        emit(f"{name:<15} {K:>5} {a[0]:>9.2f} {a[1]:>6.2f} {a[2]:>7.1f} {b[0]:>9.2f} {b[1]:>6.2f} {b[2]:>7.1f} {c[0]:>9.2f} {c[1]:>6.2f} "
+             f"{c[2]:>7.1f} {a[0] / b[0]:>6.2f} {a[0] / c[0]:>6.2f}" + ("" if a[2] == b[2] else "   # (a) and (b) DIFFER in iterations"))
+
+    ks = [int(k) for k in args.ks.split(",") if k]
+    for shape in [s for s in args.shapes.split(",") if s]:
+        problems = members(shape, max(ks))
+        for K in ks:
+            row(shape, K, problems[:K], False)
+        if not args.no_profile:
+            K = min(args.profile_k, max(ks))
+            got = kernel_us(shape, K)
+            if isinstance(got, str):
+                emit(f"# {shape}: re-solve kernels at K = {K}: not measured ({got})")
+            else:
+                emit(f"# {shape}: re-solve kernels at K = {K} (rocprofv3 --kernel-trace --stats, a run of its own), calls x average us: "
+                     + "; ".join(f"{n} {c} x {us:.1f}" for n, (c, us) in sorted(got.items())))
+    for name in [s for s in args.single.split(",") if s]:
+        row(name, 1, [single_problem(name)], True)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
