@@ -12,4 +12,4 @@ from .engine import HipPdhgEngine  # noqa: F401
 from . import _lib  # noqa: F401
 from .batch import HipPdhgBatch, optimize_batch  # noqa: F401
 from .fleet import HipPdhgFleet, optimize_many  # noqa: F401
-from .session import PdhgFleetSession, PdhgSession  # noqa: F401
+from .session import PdhgBatchSession, PdhgFleetSession, PdhgSession  # noqa: F401

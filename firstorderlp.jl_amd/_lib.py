@@ -51,6 +51,11 @@ RESOLVE_EXPORTS = [
     "pdhg_fleet_update_problem_vectors", "pdhg_fleet_warm_start", "pdhg_fleet_resolve_info",
 ]
 
+# every symbol include/pdhg_hip_batch_resolve.h declares: the same for a batch, on the batch handle
+BATCH_RESOLVE_EXPORTS = [
+    "pdhg_batch_resolve_retain", "pdhg_batch_update_problem_vectors", "pdhg_batch_warm_start", "pdhg_batch_resolve_info",
+]
+
 ABI_VERSION = 11
 UNIQUE_ID_BYTES = 128
 (K_PRIMAL, K_SPMV_DUAL, K_SPMV_ATY, K_FINAL, K_ACCEPT, K_ALLGATHER, K_REDUCE_SCATTER,
@@ -62,7 +67,7 @@ def build(force=False, verbose=False):
     """Cross-compile the HIP library for gfx950 with hipcc (no GPU needed)."""
     hipcc = os.environ.get("HIPCC", "hipcc")
     sources = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))] + \
-              [os.path.join(INCLUDE, "pdhg_hip.h"), os.path.join(INCLUDE, "pdhg_hip_resolve.h")]
+              [os.path.join(INCLUDE, f) for f in ("pdhg_hip.h", "pdhg_hip_resolve.h", "pdhg_hip_batch_resolve.h")]
     if not force and os.path.exists(LIB_PATH) and \
             os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in sources):
         return LIB_PATH
@@ -96,7 +101,7 @@ def build_sanitized(kind="asan", force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "hipcc")
     path, flags = SANITIZED[kind]
     sources = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))] + \
-              [os.path.join(INCLUDE, "pdhg_hip.h"), os.path.join(INCLUDE, "pdhg_hip_resolve.h")]
+              [os.path.join(INCLUDE, f) for f in ("pdhg_hip.h", "pdhg_hip_resolve.h", "pdhg_hip_batch_resolve.h")]
     if not force and os.path.exists(path) and os.path.getmtime(path) >= max(os.path.getmtime(f) for f in sources):
         return path
     cmd = [hipcc, "-O1", "-g"] + HIPCC_FLAGS[1:] + flags + ["-fno-gpu-sanitize", "-I", INCLUDE, "-o", path, SRC_PATH] + LINK_FLAGS
@@ -130,7 +135,7 @@ def lib():
     d, i64, i32 = ctypes.c_double, ctypes.c_int64, ctypes.c_int
     # a stale library (older ABI: different out[] lengths, missing entry points)
     # must fail here, not as a buffer overrun deep inside a solve
-    missing = [name for name in EXPORTS + RESOLVE_EXPORTS if not hasattr(L, name)]
+    missing = [name for name in EXPORTS + RESOLVE_EXPORTS + BATCH_RESOLVE_EXPORTS if not hasattr(L, name)]
     L.pdhg_abi_version.restype = i32
     L.pdhg_abi_version.argtypes = []
     version = L.pdhg_abi_version() if not missing or "pdhg_abi_version" not in missing else None
@@ -295,6 +300,15 @@ def lib():
     L.pdhg_fleet_warm_start.argtypes = [_vp, _dpp, _dpp]
     L.pdhg_fleet_resolve_info.restype = i32
     L.pdhg_fleet_resolve_info.argtypes = [_vp, _ip]
+    # include/pdhg_hip_batch_resolve.h (arrays of K pointers, K = the batch's members)
+    L.pdhg_batch_resolve_retain.restype = i32
+    L.pdhg_batch_resolve_retain.argtypes = [_vp]
+    L.pdhg_batch_update_problem_vectors.restype = i32
+    L.pdhg_batch_update_problem_vectors.argtypes = [_vp, _dpp, _dpp, _dpp, _dpp]
+    L.pdhg_batch_warm_start.restype = i32
+    L.pdhg_batch_warm_start.argtypes = [_vp, _dpp, _dpp]
+    L.pdhg_batch_resolve_info.restype = i32
+    L.pdhg_batch_resolve_info.argtypes = [_vp, _ip]
     _lib = L
     return L
 

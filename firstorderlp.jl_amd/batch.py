@@ -9,7 +9,9 @@ per-problem solve object (``primal_dual_hybrid_gradient._Solve``): only the step
 
 ``HipPdhgBatch`` is the device side: one ``pdhg_handle`` that owns the matrix plus K member handles that borrow it
 (``.members``: ``HipPdhgEngine`` views -- every single-LP method works on them).  With ``objective_matrix`` the members
-are QPs that borrow one objective matrix too (``pdhg_batch_set_objective_matrix``).
+are QPs that borrow one objective matrix too (``pdhg_batch_set_objective_matrix``).  A batch that is solved again and
+again keeps its handle (``retain_rescaling`` / ``update_problem_vectors`` / ``warm_start``,
+include/pdhg_hip_batch_resolve.h; ``session.PdhgBatchSession`` drives them).
 """
 import ctypes
 import os
@@ -19,11 +21,12 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _lib
-from .engine import _MemberEngine, _MemberOwner, _d, _i, _int_p, _pd, _pi
+from .engine import _dp, _MemberEngine, _MemberOwner, _d, _i, _int_p, _pd, _pi
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams,
                                           MalitskyPockStepsizeParameters, _check_inputs, _constant_step_estimate,
-                                          _device_scaled_problem, _drive_solves, _host_scaled_problem, _pack_step_states,
-                                          _rescales_on_device, _Solve, _unpack_step_states, adaptive_step_rule)
+                                          _device_scaled_problem, _drive_solves, _host_scaled_problem, _initial_point,
+                                          _pack_step_states, _rescales_on_device, _set_initial_point, _Solve,
+                                          _unpack_step_states, adaptive_step_rule)
 
 MAX_BATCH = 32
 
@@ -132,6 +135,66 @@ class HipPdhgBatch(_MemberOwner):
         return self._take_steps_adaptive(self._L.pdhg_batch_take_steps_adaptive, int(n_steps), reduction_exponent,
                                          growth_exponent, step_sizes, primal_weights, total_number_iterations,
                                          cumulative_kkt_passes, a.ctypes.data_as(_int_p))
+
+    # ---- re-solves on the batch handle (include/pdhg_hip_batch_resolve.h) ----
+    def _live(self):
+        if not getattr(self, "_h", None):
+            raise _lib.PdhgHipError("the batch is closed")
+        return self._h
+
+    def _pointer_table(self, name, values, length):
+        """An array of K pointers (NULL: the member's entry is None) over ``values`` = None or a list of K vectors /
+        None, shapes checked; also returns the arrays, which must outlive the call."""
+        if values is None:
+            return None, []
+        values = list(values)
+        if len(values) != self.K:
+            raise ValueError(f"{name} has {len(values)} entries, the batch has {self.K} members")
+        keep = []
+        table = (_dp * self.K)()
+        for k, v in enumerate(values):
+            if v is None:
+                continue
+            v = _d(v)
+            if v.shape != (length,):
+                raise ValueError(f"{name}[{k}] has {v.shape} entries, a member needs ({length},)")
+            keep.append(v)
+            table[k] = v.ctypes.data_as(_dp)
+        return table, keep
+
+    def retain_rescaling(self):
+        """``pdhg_batch_resolve_retain``: to be called before ``rescale`` (and after the objective matrix is set).
+        The batch keeps every rescaling step's factors once for all members (8 * steps * (n + m) bytes of device
+        memory), which ``update_problem_vectors`` and ``warm_start`` need."""
+        _lib.check(self._L.pdhg_batch_resolve_retain(self._live()))
+
+    def update_problem_vectors(self, objective_vectors=None, right_hand_sides=None, variable_lower_bounds=None,
+                               variable_upper_bounds=None):
+        """New vectors of the members' ORIGINAL problems, all members in ONE launch: each argument is None or a list of
+        K vectors / None (None: keep).  A member's working vectors become, bit for bit, those of a fresh batch's
+        member created from the updated problems and rescaled with the same parameters."""
+        h = self._live()
+        tables = [self._pointer_table(name, v, length) for name, v, length in (
+            ("objective_vectors", objective_vectors, self.n), ("right_hand_sides", right_hand_sides, self.m),
+            ("variable_lower_bounds", variable_lower_bounds, self.n),
+            ("variable_upper_bounds", variable_upper_bounds, self.n))]
+        _lib.check(self._L.pdhg_batch_update_problem_vectors(h, *[t for t, _ in tables]))
+
+    def warm_start(self, xs=None, ys=None):
+        """``pdhg_batch_warm_start``: member k starts from (xs[k], ys[k]) in the original problem's space with
+        everything else as on a fresh member.  A member whose two entries are None is left as it is; with one entry
+        given the other means zeros; ``xs`` and ``ys`` both None: every member starts from zeros."""
+        h = self._live()
+        tx, ty = self._pointer_table("xs", xs, self.n), self._pointer_table("ys", ys, self.m)
+        _lib.check(self._L.pdhg_batch_warm_start(h, tx[0], ty[0]))
+
+    def resolve_info(self):
+        """dict(shared_launches, carried, single, batched_product): shared re-solve launches so far; members the last
+        ``update_problem_vectors`` / ``warm_start`` carried; members the last ``warm_start`` gave a product of their
+        own; whether it ran the batched product."""
+        info = np.zeros(4, dtype=np.int64)
+        _lib.check(self._L.pdhg_batch_resolve_info(self._live(), _pi(info)))
+        return dict(zip(["shared_launches", "carried", "single", "batched_product"], info.tolist()))
 
 
 def _shared_q(problem):
@@ -254,7 +317,32 @@ def _take_steps(batch, members, n_steps, policy):
     return _take_steps_python(batch, members, n_steps, policy)
 
 
-def optimize_batch(params, problems, batch_factory=None):
+def _step_batch(batch, policy, requests):
+    """``_drive_solves``' step for the solves of a batch: lockstep -- the members that named the same step count step
+    together, the smaller counts first.  Returns (solve, steps taken, seconds) per request."""
+    groups = {}
+    for mb, steps in requests:
+        groups.setdefault(steps, []).append(mb)
+    out = []
+    for steps, group in sorted(groups.items()):
+        t0 = _time.time()
+        done = _take_steps(batch, group, steps, policy)
+        dt = _time.time() - t0
+        out.extend((mb, d, dt) for mb, d in zip(group, done))
+    return out
+
+
+def _initial_points(problems, initial_solutions):
+    """``initial_solutions`` of ``optimize_batch`` checked on the host: one ``_initial_point`` result per problem."""
+    if initial_solutions is None:
+        return [None] * len(problems)
+    initial_solutions = list(initial_solutions)
+    if len(initial_solutions) != len(problems):
+        raise ValueError(f"initial_solutions has {len(initial_solutions)} entries for {len(problems)} problems")
+    return [None if pt is None else _initial_point(p, *pt) for p, pt in zip(problems, initial_solutions)]
+
+
+def optimize_batch(params, problems, batch_factory=None, initial_solutions=None):
     """``optimize(params, problems[k])`` for every k, as one batch: a list of ``SaddlePointOutput`` in input order.
 
     The problems must share the constraint matrix (shape, pattern, values) and ``num_equalities``, and be LPs
@@ -266,6 +354,11 @@ def optimize_batch(params, problems, batch_factory=None):
     of LPs and QPs, QPs with different objective matrices, an empty list or more than 32 problems raise ``ValueError``
     before any device work.
 
+    ``initial_solutions``: ``None`` (every problem starts from zeros, the path as it always was) or one entry per
+    problem -- ``None`` or ``(x0, y0)``, a starting point in the original problem's space with ``optimize``'s
+    semantics (``initial_primal_solution`` / ``initial_dual_solution``), checked before any device work.
+    ``session.PdhgBatchSession`` keeps the batch across solves.
+
     Measured on one MI355X (README, "Batched solves"; ``profiles/batch_qp_throughput.txt``): at K = 8 a QP batch of
     ``generators.random_qp_family`` runs 1.19x the solo QP handle's member-iterations/s at 10M x 10M and 1.48x at
     1M x 1M; at 10M x 10M, K = 16 is no gain (0.98x)."""
@@ -274,6 +367,7 @@ def optimize_batch(params, problems, batch_factory=None):
     policy = params.step_size_policy_params
     if not isinstance(policy, (AdaptiveStepsizeParams, ConstantStepsizeParams)):
         raise ValueError(f"optimize_batch does not support the step-size policy {type(policy).__name__}")
+    points = _initial_points(problems, initial_solutions)
     factory = batch_factory or _default_batch_factory
     batch = None
     try:
@@ -287,26 +381,16 @@ def optimize_batch(params, problems, batch_factory=None):
             matrix_max_abs = max_abs[0]
             batch = factory([s.scaled_qp for s in scaled])
         members = [_Solve(params, p, s, eng, matrix_max_abs) for p, s, eng in zip(problems, scaled, batch.members)]
+        for mb, point in zip(members, points):
+            if point is not None:
+                _set_initial_point(mb.engine, mb.scaled_problem, point)
 
         # the constant policy's power method depends on the matrix only: run once, on member 0's operators
         estimate = _constant_step_estimate(members[0]) if isinstance(policy, ConstantStepsizeParams) else None
         for mb in members:
             mb.start(estimate)
 
-        def step(requests):
-            # lockstep: the members that named the same step count step together, the smaller counts first
-            groups = {}
-            for mb, steps in requests:
-                groups.setdefault(steps, []).append(mb)
-            out = []
-            for steps, group in sorted(groups.items()):
-                t0 = _time.time()
-                done = _take_steps(batch, group, steps, policy)
-                dt = _time.time() - t0
-                out.extend((mb, d, dt) for mb, d in zip(group, done))
-            return out
-
-        return _drive_solves(members, step)
+        return _drive_solves(members, lambda requests: _step_batch(batch, policy, requests))
     finally:
         if batch is not None and hasattr(batch, "close"):
             batch.close()

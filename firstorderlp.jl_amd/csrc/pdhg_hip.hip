@@ -35,6 +35,7 @@
 
 #include "pdhg_hip.h"
 #include "pdhg_hip_resolve.h"
+#include "pdhg_hip_batch_resolve.h"
 
 // The kernels and layout builders live in the headers below; they form ONE
 // translation unit with this file (the tiled kernel is sensitive to code
@@ -54,6 +55,7 @@
 #include "tr_coop_kernel.hpp"
 #include "batch_kernels.hpp"
 #include "resolve_kernels.hpp"
+#include "batch_resolve_kernels.hpp"
 
 namespace { struct DistGroup; struct FleetState; struct ResolveState; }
 struct BatchState;
@@ -950,4 +952,5 @@ static int batch_scale_members(pdhg_handle *h, const double *dv, const double *e
 #include "abi_fleet.hpp"
 #include "abi_fleet_checks.hpp"
 #include "abi_resolve.hpp"
+#include "abi_batch_resolve.hpp"
 }  // extern "C"

@@ -14,7 +14,8 @@ every copy of the matrix -- for work that depends on the matrix only.  A session
 ``solve(warm_start=(x0, y0))`` what ``optimize(..., initial_primal_solution=x0, initial_dual_solution=y0)`` returns: the
 library replays the recorded rescaling steps on the new vectors (include/pdhg_hip_resolve.h) and empties everything a
 fresh handle has empty.  ``PdhgFleetSession`` is the same over a fleet (``fleet.optimize_many``): updates and warm starts
-of all members in one launch each.
+of all members in one launch each, and ``PdhgBatchSession`` over a batch (``batch.optimize_batch``): problems that share
+the matrix share the record of its rescaling too (include/pdhg_hip_batch_resolve.h).
 
 The reference has no warm start: a warm solve differs from a cold one in the starting point alone (see ``optimize``).
 """
@@ -22,9 +23,10 @@ import dataclasses
 
 import numpy as np
 
+from .batch import _default_batch_factory, _step_batch, check_batch
 from .fleet import _default_fleet_factory, _fleet_checks, _step_fleet
 from .preprocess import validate
-from .primal_dual_hybrid_gradient import (ConstantStepsizeParams, _check_inputs, _constant_step_estimate,
+from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams, _check_inputs, _constant_step_estimate,
                                           _default_engine_factory, _device_scaled_problem, _drive_solve, _drive_solves,
                                           _host_scaled_problem, _initial_point, _rescales_on_device, _Solve)
 
@@ -66,10 +68,15 @@ def _warm_point(problem, warm_start, last):
 class _Member:
     """One problem of a session on its engine: created, retained, rescaled; its current problem and scaled problem."""
 
-    def __init__(self, params, problem, engine, on_device, host_scaled=None):
+    def __init__(self, params, problem, engine, on_device, host_scaled=None, rescaled=None):
         self.params, self.problem, self.engine, self.on_device = params, problem, engine, on_device
         self.last = None
         self.estimate = None
+        if rescaled is not None:
+            # a batch member: its batch retained and rescaled for all members -- (E, D, matrix_max_abs)
+            self.E, self.D, self.matrix_max_abs = rescaled
+            self.scaled_problem = _device_scaled_problem(problem, engine, self.E, self.D)
+            return
         if hasattr(engine, "retain_rescaling"):
             engine.retain_rescaling()
         if on_device:
@@ -308,6 +315,138 @@ class PdhgFleetSession:
         fleet, self._fleet, self._members = self._fleet, None, None
         if fleet is not None and hasattr(fleet, "close"):
             fleet.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PdhgBatchSession:
+    """Problems that share the constraint matrix (and the objective matrix) kept on the device across solves:
+    ``PdhgSession`` over a batch (``batch.optimize_batch``, whose preconditions hold here: 1..32 problems, one matrix,
+    the adaptive or the constant policy).  A batch with ``retain_rescaling`` / ``update_problem_vectors`` / ``warm_start``
+    of its own (``HipPdhgBatch``) keeps one record of the rescaling for all members and takes the updates and the warm
+    starts of all members in one launch each; a factory that does not rescale on the device, or any other batch, is
+    served member by member through its engines' ``update_problem_vectors`` / ``warm_start``."""
+
+    def __init__(self, params, problems, batch_factory=None):
+        problems = check_batch(problems, params)
+        _check_inputs(params, problems)
+        policy = params.step_size_policy_params
+        if not isinstance(policy, (AdaptiveStepsizeParams, ConstantStepsizeParams)):
+            raise ValueError(f"a batch session does not support the step-size policy {type(policy).__name__}")
+        factory = batch_factory or _default_batch_factory
+        self.params = params
+        self._batch = None
+        self._members = None
+        self._estimate = None
+        batch = None
+        try:
+            if _rescales_on_device(factory):
+                batch = factory(problems)
+                if hasattr(batch, "retain_rescaling"):
+                    batch.retain_rescaling()
+                E, D = batch.rescale(params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
+                max_abs = batch.members[0].matrix_max_abs()
+                self._members = [_Member(params, p, eng, True, rescaled=(E.copy(), D.copy(), max_abs))
+                                 for p, eng in zip(problems, batch.members)]
+            else:
+                host_scaled = [_host_scaled_problem(params, p) for p in problems]
+                batch = factory([s.scaled_qp for s, _ in host_scaled])
+                self._members = [_Member(params, p, eng, False, (s, host_scaled[0][1]))
+                                 for p, eng, (s, _) in zip(problems, batch.members, host_scaled)]
+            self._batch = batch
+        except Exception:
+            self._members = None
+            if batch is not None and hasattr(batch, "close"):
+                batch.close()
+            raise
+
+    @property
+    def batch(self):
+        self._live()
+        return self._batch
+
+    @property
+    def problems(self):
+        return [mb.problem for mb in self._live()]
+
+    def _live(self):
+        if self._members is None:
+            raise RuntimeError("the session is closed")
+        return self._members
+
+    def _shared(self, members):
+        """Does the batch itself take the updates and the warm starts (original-space vectors, one launch each)?"""
+        return all(mb.on_device for mb in members) and hasattr(self._batch, "update_problem_vectors") and \
+            hasattr(self._batch, "warm_start")
+
+    def update(self, updates):
+        """``updates``: one entry per problem -- ``None`` (keep the problem) or a dict with any of ``objective_vector``,
+        ``right_hand_side``, ``variable_lower_bound``, ``variable_upper_bound``.  Every updated problem is validated
+        before any device work; if one raises, the session is as it was."""
+        members = self._live()
+        updates = list(updates)
+        if len(updates) != len(members):
+            raise ValueError(f"updates has {len(updates)} entries for {len(members)} problems")
+        staged = [None if u is None else mb.staged_update(**u) for mb, u in zip(members, updates)]
+        vectors = [None if st is None or not st[1] else mb.engine_vectors(st[1], st[2]) for mb, st in zip(members, staged)]
+        if any(v is not None for v in vectors):
+            if self._shared(members):
+                self._batch.update_problem_vectors(*[[None if v is None else v[k] for v in vectors] for k in _UPDATE_FIELDS])
+            else:
+                for mb, v in zip(members, vectors):
+                    if v is not None:
+                        mb.engine.update_problem_vectors(**v)
+        for mb, st in zip(members, staged):
+            if st is not None:
+                mb.committed(st[0], st[2])
+
+    def solve(self, warm_start=None):
+        """Solve every problem as updated so far; returns what ``optimize_batch`` returns.  ``warm_start``: ``None``
+        (everyone from zeros), ``True`` (everyone from its previous solution) or a list with one entry per problem --
+        ``None`` (zeros) or ``(x0, y0)``."""
+        members = self._live()
+        if warm_start is None or warm_start is True:
+            warm_start = [warm_start] * len(members)
+        warm_start = list(warm_start)
+        if len(warm_start) != len(members):
+            raise ValueError(f"warm_start has {len(warm_start)} entries for {len(members)} problems")
+        points = [mb.engine_point(_warm_point(mb.problem, w, mb.last)) for mb, w in zip(members, warm_start)]
+        if self._shared(members):
+            if all(x is None and y is None for x, y in points):
+                self._batch.warm_start(None, None)
+            else:
+                # a member whose two entries are None would be left as it is: zeros are given as zeros
+                xs = [np.zeros(mb.engine.n) if x is None and y is None else x for mb, (x, y) in zip(members, points)]
+                self._batch.warm_start(xs, [y for _, y in points])
+        else:
+            for mb, (x, y) in zip(members, points):
+                mb.engine.warm_start(x, y)
+        batch, policy = self._batch, self.params.step_size_policy_params
+        solves = [_Solve(self.params, mb.problem, mb.scaled_problem, mb.engine, mb.matrix_max_abs) for mb in members]
+        if isinstance(policy, ConstantStepsizeParams) and self._estimate is None:
+            # the power method sees the matrix only: once per session, on member 0's operators (as optimize_batch runs
+            # it); its passes count in every solve, as in a fresh one
+            self._estimate = _constant_step_estimate(solves[0])
+        for solve in solves:
+            solve.start(self._estimate)
+        outputs = _drive_solves(solves, lambda requests: _step_batch(batch, policy, requests))
+        return [mb.solved(out) for mb, out in zip(members, outputs)]
+
+    def close(self):
+        batch, self._batch, self._members = self._batch, None, None
+        if batch is not None and hasattr(batch, "close"):
+            batch.close()
 
     def __enter__(self):
         return self

@@ -3,6 +3,7 @@
     python tools/resolve_bench.py [--shapes netlib27x32,netlib56x97,random1000x800] [--ks 64,256] [--single l1svm,pagerank1m]
                                   [--ticks 20] [--reps 5] [--iteration-limit 5000] [--profile-k 256] [--no-profile]
                                   [--out profiles/resolve_throughput.txt]
+                                  [--batch pagerank,l1svm,randomqp] [--batch-k 8] [--batch-qp-shape 1000000x1000000]
 
 At every tick the right-hand side of every problem is perturbed by 1 % (a fixed seed per tick and member).  Per tick:
 
@@ -21,6 +22,13 @@ session is created once per repetition, outside the timed ticks (its first solve
 Also the kernel durations of the shared update and warm-start launches (fleet_resolve_replay_kernel,
 fleet_resolve_point_kernel) at --profile-k members, from a `rocprofv3 --kernel-trace --stats` run of a child process of
 its own, with no counters.
+
+--batch adds the batch legs (nothing else changes): families that share the matrix -- tools/batch_bench.py's
+personalized PageRank at 1M nodes and its L1-SVM regularization path, and ``generators.random_qp_family`` at
+--batch-qp-shape -- at --batch-k members, where (a) is `optimize_batch` on the updated problems and (b), (c) are a
+`PdhgBatchSession`.  Their kernels (batch_resolve_replay_kernel, batch_resolve_point_kernel) are timed the same way in a
+child whose updates give all four vectors of every member, so that the replay streams the whole record: its bytes per
+second are tiles * 8 * S * (n + m) over the kernel's average duration (tiles = ceil(K / 4), S = 11 recorded steps).
 """
 import argparse
 import dataclasses
@@ -38,7 +46,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-KERNELS = ("fleet_resolve_replay_kernel", "fleet_resolve_point_kernel", "resolve_replay_kernel", "resolve_point_kernel")
+KERNELS = ("fleet_resolve_replay_kernel", "fleet_resolve_point_kernel", "resolve_replay_kernel", "resolve_point_kernel",
+           "batch_resolve_replay_kernel", "batch_resolve_point_kernel")
+BATCH_RESOLVE_TILE = 4          # csrc/batch_resolve_kernels.hpp
 
 
 def single_problem(name):
@@ -59,15 +69,22 @@ def _iterations(outs):
     return float(np.mean([o.iteration_count for o in outs]))
 
 
-def series(problems, params, ticks, route, single):
+def batch_problems(config, K, qp_shape):
+    from batch_bench import members, qp_members
+    return qp_members(qp_shape, K) if config == "randomqp" else members(config, K)
+
+
+def series(problems, params, ticks, route, single, batch=False):
     """One series of `ticks` ticks by `route` ('a', 'b', 'c'): (seconds per tick, iterations per solve)."""
-    from firstorderlp_jl_amd import PdhgFleetSession, PdhgSession, optimize_many
+    from firstorderlp_jl_amd import PdhgBatchSession, PdhgFleetSession, PdhgSession, optimize_batch, optimize_many
     from firstorderlp_jl_amd.primal_dual_hybrid_gradient import optimize
+    if batch:
+        optimize_many = optimize_batch
     seconds, iterations = [], []
     session = None
     try:
         if route != "a":
-            session = PdhgSession(params, problems[0]) if single else PdhgFleetSession(params, problems)
+            session = PdhgSession(params, problems[0]) if single else (PdhgBatchSession if batch else PdhgFleetSession)(params, problems)
             session.solve()
         for tick in range(ticks):
             rhs = [tick_rhs(p, tick, k) for k, p in enumerate(problems)]
@@ -89,12 +106,12 @@ def series(problems, params, ticks, route, single):
     return float(np.mean(seconds)), float(np.mean(iterations))
 
 
-def measure(problems, params, ticks, reps, single):
+def measure(problems, params, ticks, reps, single, batch=False):
     """{route: (best ms per tick, worst / best over the repetitions, iterations per solve)}, the routes alternating."""
     runs = {r: [] for r in "abc"}
     for _ in range(reps):
         for route in "abc":
-            runs[route].append(series(problems, params, ticks, route, single))
+            runs[route].append(series(problems, params, ticks, route, single, batch))
     out = {}
     for route, rs in runs.items():
         secs = [s for s, _ in rs]
@@ -114,16 +131,31 @@ def child(shape, K, ticks):
             session.solve(warm_start=True)
 
 
-def kernel_us(shape, K, ticks=4, timeout=400):
+def batch_child(config, K, ticks, qp_shape):
+    """What the profiled child of a batch leg runs: a batch session, `ticks` updates of all four vectors of every member
+    (b perturbed, the others as they are) and warm solves with a short iteration limit."""
+    from fleet_bench import solve_params
+    from firstorderlp_jl_amd import PdhgBatchSession
+    problems = batch_problems(config, K, qp_shape)
+    with PdhgBatchSession(solve_params(80), problems) as session:
+        session.solve()
+        for tick in range(ticks):
+            session.update([{"objective_vector": p.objective_vector, "right_hand_side": tick_rhs(p, tick, k),
+                             "variable_lower_bound": p.variable_lower_bound, "variable_upper_bound": p.variable_upper_bound}
+                            for k, p in enumerate(problems)])
+            session.solve(warm_start=True)
+
+
+def kernel_us(shape, K, ticks=4, timeout=400, extra=()):
     """{kernel: (calls, average us)} of the re-solve kernels in a `rocprofv3 --kernel-trace --stats` run of a child of its
-    own, or a string saying why there is none."""
+    own, or a string saying why there is none.  `extra`: more arguments for the child (a batch leg's)."""
     from rocprof_summary import summarize
     rp = shutil.which("rocprofv3")
     if not rp:
         return "rocprofv3 not on PATH"
     work = tempfile.mkdtemp(prefix="pdhg_resolve_prof_", dir="/tmp")
     try:
-        cmd = [rp, "--kernel-trace", "--stats", "-d", work, "--", sys.executable, os.path.abspath(__file__), "--child", shape, str(K), str(ticks)]
+        cmd = [rp, "--kernel-trace", "--stats", "-d", work, "--", sys.executable, os.path.abspath(__file__), "--child", shape, str(K), str(ticks), *extra]
         r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), timeout=timeout, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
         if r.returncode != 0:
             return f"profiled child failed ({r.returncode}): {r.stderr.decode(errors='replace')[-200:]}"
@@ -150,11 +182,17 @@ def main(argv=None):
     ap.add_argument("--profile-k", type=int, default=256)
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--child", nargs=3, default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--batch", default="", help="batch legs: any of pagerank,l1svm,randomqp")
+    ap.add_argument("--batch-k", type=int, default=8)
+    ap.add_argument("--batch-qp-shape", default="1000000x1000000")
+    ap.add_argument("--child", nargs="+", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     import folp_loader
     folp_loader.load()
     from fleet_bench import members, solve_params
+    if args.child and len(args.child) > 3:
+        batch_child(args.child[0], int(args.child[1]), int(args.child[2]), args.child[3])
+        return
     if args.child:
         child(args.child[0], int(args.child[1]), int(args.child[2]))
         return
@@ -173,8 +211,8 @@ def main(argv=None):
     emit(f"{'problem':<15} {'K':>5} {'(a) ms':>9} {'spread':>6} {'it':>7} {'(b) ms':>9} {'spread':>6} {'it':>7} {'(c) ms':>9} {'spread':>6} {'it':>7} "
          f"{'a/b':>6} {'a/c':>6}")
 
-    def row(name, K, problems, single):
-        got = measure(problems, params, args.ticks, args.reps, single)
+    def row(name, K, problems, single, batch=False):
+        got = measure(problems, params, args.ticks, args.reps, single, batch)
         a, b, c = got["a"], got["b"], got["c"]
         emit(f"{name:<15} {K:>5} {a[0]:>9.2f} {a[1]:>6.2f} {a[2]:>7.1f} {b[0]:>9.2f} {b[1]:>6.2f} {b[2]:>7.1f} {c[0]:>9.2f} {c[1]:>6.2f} "
              f"{c[2]:>7.1f} {a[0] / b[0]:>6.2f} {a[0] / c[0]:>6.2f}" + ("" if a[2] == b[2] else "   # (a) and (b) DIFFER in iterations"))
@@ -194,6 +232,25 @@ def main(argv=None):
                      + "; ".join(f"{n} {c} x {us:.1f}" for n, (c, us) in sorted(got.items())))
     for name in [s for s in args.single.split(",") if s]:
         row(name, 1, [single_problem(name)], True)
+    for config in [s for s in args.batch.split(",") if s]:
+        K = args.batch_k
+        problems = batch_problems(config, K, args.batch_qp_shape)
+        m, n = problems[0].constraint_matrix.shape
+        row("batch:" + config, K, problems, False, True)
+        del problems
+        if args.no_profile:
+            continue
+        got = kernel_us(config, K, ticks=2, extra=(args.batch_qp_shape,))
+        if isinstance(got, str):
+            emit(f"# batch:{config}: re-solve kernels at K = {K}: not measured ({got})")
+            continue
+        emit(f"# batch:{config}: re-solve kernels at K = {K} (rocprofv3 --kernel-trace --stats, a run of its own), calls x average us: "
+             + "; ".join(f"{name} {c} x {us:.1f}" for name, (c, us) in sorted(got.items())))
+        if "batch_resolve_replay_kernel" in got:
+            steps = 11                                        # solve_params: ten Ruiz passes and Pock-Chambolle
+            record = -(-K // BATCH_RESOLVE_TILE) * 8 * steps * (n + m)
+            emit(f"# batch:{config}: the replay reads {record / 1e6:.1f} MB of record per launch ({m} x {n}, {steps} steps, "
+                 f"{-(-K // BATCH_RESOLVE_TILE)} tiles): {record / got['batch_resolve_replay_kernel'][1] / 1e3:.1f} GB/s of record")
     if args.out:
         with open(args.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
