@@ -640,16 +640,25 @@ static int take_step_malitsky_pock_one(pdhg_handle *h, PolicyIO &io) {
 }
 
 // The per-handle loop of the two calls from a given place (io.steps_done of the n_steps are taken already): batches of
-// two and more go to the one-workgroup kernel where the handle suits it (small_policy_steps), everything else -- and a
-// Malitsky-Pock take_step into an empty primal average -- is taken launch by launch.
+// two and more go to the one-workgroup kernel where the handle suits it (small_policy_steps), then -- under
+// PDHG_DEVICE_LOOP=1 -- to the persistent multi-step kernel (coop_policy_steps); each answers 1 for "not taken".
+// Everything else -- and a Malitsky-Pock take_step into an empty primal average -- is taken launch by launch.
 static int take_steps_policy_resume(pdhg_handle *h, int64_t n_steps, PolicyIO &io) {
+  int (*const launchers[])(pdhg_handle *, int64_t, PolicyIO &) = {small_policy_steps, coop_policy_steps};
   while (io.steps_done < n_steps && !io.numerical_error) {
-    const bool quirk = io.policy == SMALL_MALITSKY_POCK && h->sum_x_count == 0;
-    if (!quirk && n_steps - io.steps_done >= 2 && !h->grp && check_handle(h) == 0) {
-      const int rc = small_policy_steps(h, n_steps - io.steps_done, io);
-      if (rc == 0) continue;
-      if (rc != 1) return rc;
+    bool go_on = false;       // a launch took whole take_steps: offer the rest again
+    for (auto launch : launchers) {
+      const bool quirk = io.policy == SMALL_MALITSKY_POCK && h->sum_x_count == 0;
+      if (quirk || n_steps - io.steps_done < 2 || h->grp || check_handle(h) != 0) break;
+      const int64_t before = io.steps_done;
+      const int rc = launch(h, n_steps - before, io);
+      if (rc != 0 && rc != 1) return rc;
+      // (nothing taken: a barrier timed out in the launch's first step -- the next step singly, from the state left)
+      go_on = rc == 0 && io.steps_done > before;
+      if (rc == 0) break;
     }
+    if (go_on) continue;
+    if (io.steps_done >= n_steps || io.numerical_error) break;
     if (int rc = io.policy == SMALL_MALITSKY_POCK ? take_step_malitsky_pock_one(h, io) : take_step_constant_one(h, io)) return rc;
     io.steps_done += 1;
   }

@@ -244,10 +244,13 @@ inline StepRule step_after_trial(StepIO &io, const double raw[5]) {
   return rule;
 }
 
+// the step-size policies as the multi-step kernels are instantiated for them (small_lp_kernel.hpp, trial_kernel.hpp)
+enum SmallPolicy { SMALL_ADAPTIVE = 0, SMALL_CONSTANT = 1, SMALL_MALITSKY_POCK = 2 };
+
 // The same for the two other policies (pdhg_take_steps_constant / _malitsky_pock).  The constant policy reads step_size
 // and primal_weight alone and moves kkt_passes and steps_done; its callers bind the others to storage nobody reads.
 struct PolicyIO {
-  int policy;                   // SMALL_CONSTANT or SMALL_MALITSKY_POCK (small_lp_kernel.hpp)
+  int policy;                   // SMALL_CONSTANT or SMALL_MALITSKY_POCK
   double &step_size;
   double &ratio;                // ratio_step_sizes
   int64_t &iterations;
@@ -255,6 +258,8 @@ struct PolicyIO {
   int &numerical_error;
   int64_t &steps_done;
   double primal_weight, downscaling_factor, breaking_factor, interpolation_coefficient;
+  // does policy_steps_kernel take this call's batches?  -1: not asked yet (PDHG_DEVICE_LOOP is read once per call)
+  int device_loop = -1;
 };
 
 // A load that cannot be served by a stale line of this CU's L1: agent scope (sc1), served by the L2.  The

@@ -155,20 +155,7 @@ int small_policy_collect(pdhg_handle *h, unsigned long long seq, PolicyIO &io) {
   double r[STEPS_RES_K];
   if (int rc = wait_words(h->stream, h->steps_res, STEPS_RES_CAP, STEPS_RES_K, seq, r, 400000000L,
                           "small-LP kernel finished without publishing its results")) return rc;
-  const int64_t steps = (int64_t)r[1], trials = (int64_t)r[2], failed = r[8] != 0.0 ? 1 : 0;
-  h->n_graph_trials += trials;
-  h->sum_x_count += steps; h->sum_y_count += steps;
-  h->sum_x_weights = r[6]; h->sum_y_weights = r[7];
-  if (io.policy == SMALL_MALITSKY_POCK) {
-    io.step_size = r[0];
-    io.ratio = r[3];
-    io.iterations += trials;
-    for (int64_t q = 0; q < steps + failed + trials; ++q) io.kkt_passes += 0.5;
-  } else {
-    for (int64_t q = 0; q < steps; ++q) io.kkt_passes += 1;
-  }
-  io.steps_done += steps + failed;      // the failing take_step counts as taken (it is not repeated), as under the adaptive policy
-  if (failed) io.numerical_error = 1;
+  policy_account(h, io, r, r[3]);
   h->small_lp_launches += 1;
   h->state_version += 1;
   return 0;

@@ -403,3 +403,147 @@ int coop_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
   return 0;
 }
 
+// ---- the constant and the Malitsky-Pock policy in the persistent kernel (policy_steps_kernel, trial_kernel.hpp) -------
+// A multi-step launch's result words into the handle's bookkeeping and the step state of the two other policies, by the
+// statements of the host loops (abi_trial.hpp): half a KKT pass for x' and for every dual trial, a whole one per constant
+// step (halves add exactly: the host loops' bits).  r: the words ([1] take_steps, [2] trials, [6] / [7] weight sums,
+// [8] numerical_error, [0] the next take_step's step size); ratio: where the launcher's kernel leaves ratio_step_sizes.
+static void policy_account(pdhg_handle *h, PolicyIO &io, const double r[STEPS_RES_K], double ratio) {
+  const int64_t steps = (int64_t)r[1], trials = (int64_t)r[2], failed = r[8] != 0.0 ? 1 : 0;
+  h->n_graph_trials += trials;
+  h->sum_x_count += steps; h->sum_y_count += steps;
+  h->sum_x_weights = r[6]; h->sum_y_weights = r[7];
+  if (io.policy == SMALL_MALITSKY_POCK) {
+    io.step_size = r[0];
+    io.ratio = ratio;
+    io.iterations += trials;
+    for (int64_t q = 0; q < steps + failed + trials; ++q) io.kkt_passes += 0.5;
+  } else {
+    for (int64_t q = 0; q < steps; ++q) io.kkt_passes += 1;
+  }
+  io.steps_done += steps + failed;      // the failing take_step counts as taken (it is not repeated), as under the adaptive policy
+  if (failed) io.numerical_error = 1;
+}
+
+int small_policy_launch_steps(int policy, int64_t n_steps);      // host_small_lp.hpp
+
+// Up to n_steps take_steps of io.policy in ONE launch of policy_steps_kernel, from the step state `io` on; coop_steps'
+// eligibility, launch shape and handling of a barrier time-out.  PDHG_DEVICE_LOOP=1 alone switches it on, for LPs and
+// QPs (read once per call); unset or 0, the two policies go launch by launch as before.  Returns 1 when nothing was
+// launched.  Malitsky-Pock: the caller has seen to it that the primal average is not empty and that the handle is an LP.
+int coop_policy_steps(pdhg_handle *h, int64_t n_steps, PolicyIO &io) {
+  if (io.device_loop < 0) {
+    const char *dl_env = getenv("PDHG_DEVICE_LOOP");
+    io.device_loop = dl_env && dl_env[0] == '1' ? 1 : 0;
+  }
+  if (!io.device_loop || h->profile || !coop_eligible(h) || !h->lazy_accept || h->pend_x != h->pend_y) return 1;
+  const bool mp = io.policy == SMALL_MALITSKY_POCK, qp = h->has_q;
+  if (mp && qp) return 1;
+  drop_staging(h);      // (the launch consumes the pending term)
+  int rc = coop_prepare(h);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  if ((rc = steps_result_words(h))) return rc;
+  if (!h->steps_ctl) {
+    HIP_TRY(hipMalloc((void **)&h->steps_ctl, sizeof(StepsCtl)));
+    HIP_TRY(hipMemsetAsync(h->steps_ctl, 0, sizeof(StepsCtl), h->stream));
+  }
+  std::lock_guard<std::mutex> one_at_a_time(coop_device_mutex(h->device));
+  PolicyStepsArgs a{};
+  a.n = (int)h->n; a.num_eq = (int)h->num_eq;
+  a.xa = h->x; a.xb = h->x_next; a.ya = h->y; a.yb = h->y_next; a.atya = h->aty; a.atyb = h->aty_next;
+  a.c = h->c; a.lb = h->lb; a.ub = h->ub; a.b = h->b;
+  a.xbar = h->xbar; a.sum_x = h->sum_x; a.sum_y = h->sum_y;
+  EpiArgs none{};
+  a.A = trial_product(h, h->A, nullptr, none);
+  a.T = trial_product(h, h->At, nullptr, none);
+  h->A.coop_uses -= 1; h->At.coop_uses -= 1;       // (trial_product counted one use: the launch's own count comes back with the results)
+  a.uses_a = a.A.uses; a.uses_t = a.T.uses;
+  a.pA = h->pA; a.pAt = h->pAt; a.pA_slots = h->A.slots(); a.pAt_stride = h->pAt_stride;
+  if (qp) {
+    // Q x is kept for the iterate and for the trial point (qx / qx2 flip with x); the first step's Q x is this product,
+    // ahead of the launch in stream order -- the bits of trial_kernel's phase -1
+    if (!h->qx2 && (rc = alloc_zero(&h->qx2, h->n))) return rc;
+    EpiArgs qe{};
+    qe.out = h->qx;
+    if ((rc = launch_spmv<MODE_PLAIN, 2>(h, h->Q, h->x, qe))) return rc;
+    a.Q = trial_product(h, h->Q, nullptr, none);
+    h->Q.coop_uses -= 1;
+    a.uses_q = a.Q.uses;
+    a.qxa = h->qx; a.qxb = h->qx2;
+  }
+  if (mp) {
+    // the leaders' second stage reads where the block partials are from the control block, as steps_kernel's does
+    const FinalSpec sp = trial_final_spec(h, h->At.slots(), h->A.slots(), 0, h->A.slots(), nullptr);
+    if (!h->policy_sp_host) HIP_TRY(hipHostMalloc((void **)&h->policy_sp_host, sizeof(FinalSpec), hipHostMallocDefault));
+    memcpy(h->policy_sp_host, &sp, sizeof sp);
+    HIP_TRY(hipMemcpyAsync(&h->steps_ctl->sp, h->policy_sp_host, sizeof sp, hipMemcpyHostToDevice, h->stream));
+    a.ratio = io.ratio;
+    a.downscaling_factor = io.downscaling_factor; a.breaking_factor = io.breaking_factor;
+    a.interpolation_coefficient = io.interpolation_coefficient;
+  }
+  a.primal_weight = io.primal_weight; a.step_size = io.step_size;
+  // (the worst case of a launch -- MALITSKY_POCK_MAX_TRIALS trials in every take_step -- stays within the largest adaptive launch's trials)
+  a.n_steps = small_policy_launch_steps(io.policy, n_steps);
+  a.pend = h->pend_x ? 1 : 0; a.pend_w = h->pend_w;
+  a.wsum_x = h->sum_x_weights; a.wsum_y = h->sum_y_weights;
+  const bool local = steps_local_prepare(h) == 0;
+  a.epoch = local ? h->local_epoch : h->coop_epoch;
+  a.sync = local ? h->lsync : h->gsync; a.ctl = h->steps_ctl; a.res_host = h->steps_res;
+  a.local_g = local ? h->coop_grid : 0; a.local_home = 0;
+  if (local && dev_env("PDHG_COOP_LOCAL_TEST_BAD")) a.local_g += 8;      // (coop_steps' test knob)
+  if (local) {                                                             // the stayers' ticket word: zeroed before every launch (coop_steps)
+    HIP_TRY(hipMemsetAsync(&h->lsync->ticket[0][0], 0, sizeof(unsigned long long), h->stream));
+    a.local_ticket_base = 0;
+  }
+  a.seq = ++h->steps_seq;
+  a.nxcd = h->coop_nxcd; a.relaxed = h->relaxed ? 1 : 0;
+  for (int x = 0; x < 8; ++x) a.xcd_cnt[x] = h->coop_xcd_cnt[x];
+  const dim3 grid(local ? 8 * h->coop_grid : h->coop_grid);
+  const auto c1 = std::chrono::steady_clock::now();
+#define POLICY_STEPS_LAUNCH(POLICY, QP)                                                                                          \
+  do {                                                                                                                           \
+    if (local) hipLaunchKernelGGL((policy_steps_kernel<true, POLICY, QP>), grid, dim3(TPB), 0, h->stream, a);                    \
+    else hipLaunchKernelGGL((policy_steps_kernel<false, POLICY, QP>), grid, dim3(TPB), 0, h->stream, a);                         \
+  } while (0)
+  if (mp) POLICY_STEPS_LAUNCH(SMALL_MALITSKY_POCK, false);
+  else if (qp) POLICY_STEPS_LAUNCH(SMALL_CONSTANT, true);
+  else POLICY_STEPS_LAUNCH(SMALL_CONSTANT, false);
+#undef POLICY_STEPS_LAUNCH
+  HIP_TRY(hipGetLastError());
+  const auto c2 = std::chrono::steady_clock::now();
+  h->t_launch += std::chrono::duration<double>(c2 - c1).count();
+  h->pend_x = h->pend_y = false;                   // the launch carries the deferred average update
+  double r[STEPS_RES_K];
+  if ((rc = wait_words(h->stream, h->steps_res, STEPS_RES_CAP, STEPS_RES_K, a.seq, r, 400000000L,
+                       "multi-step kernel finished without publishing its results"))) return rc;
+  h->t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - c2).count();
+  policy_account(h, io, r, r[12]);
+  const int64_t trials = (int64_t)r[2];
+  const bool flip = r[3] != 0.0, aborted = r[9] != 0.0 || r[11] != 0.0;
+  // products actually run: the counted trials, and after a time-out the trial it rose in and ([9] - 1) trials of the
+  // take_step that the host now takes again from its start
+  const unsigned long long run = (unsigned long long)trials + (r[9] != 0.0 ? (unsigned long long)r[9] : aborted ? 1ull : 0ull);
+  h->steps_launches += 1; h->steps_trials += trials;
+  if (local) { h->local_epoch = (unsigned long long)r[10]; h->local_launches += 1; }
+  else h->coop_epoch = (unsigned long long)r[10];
+  h->A.coop_uses += run;
+  h->At.coop_uses += run;
+  if (qp) h->Q.coop_uses += run;
+  if (flip) { std::swap(h->x, h->x_next); std::swap(h->y, h->y_next); std::swap(h->aty, h->aty_next); }
+  if (flip && qp) std::swap(h->qx, h->qx2);
+  h->pend_x = h->pend_y = r[4] != 0.0;
+  h->pend_w = r[5];
+  if (run > 0) h->state_version += 1;
+  if (aborted && local) {
+    h->local_mode = 0;
+    fprintf(stderr, "[pdhg_hip] multi-step policy kernel, XCD-local mode: a barrier timed out (code %g) -- all-XCD mode from here on\n", r[11]);
+  } else if (aborted) {
+    h->coop_mode = 0;
+    h->coop_fallbacks += 1;
+    fprintf(stderr, "[pdhg_hip] multi-step policy kernel: a grid barrier timed out (code %g; is the device shared with another "
+                    "persistent kernel?) -- this handle uses the %s path from here on\n", r[11],
+            graph_eligible(h) ? "graph" : "separate-launch");
+  }
+  return 0;
+}

@@ -44,7 +44,6 @@ namespace {
 constexpr int SMALL_TPB = 1024;          // threads of the workgroup for n or m beyond SMALL_FEW_ROWS; 256 below (fewer waves per barrier)
 constexpr int SMALL_FEW_ROWS = 256;      // (30 x 30: 173k it/s with 256 threads against 126k with 1024; 300 x 300: 116k against 120k)
 constexpr int SMALL_MAX_ROW = 256;       // rows of more entries are summed wave-parallel in relaxed order elsewhere
-enum SmallPolicy { SMALL_ADAPTIVE = 0, SMALL_CONSTANT = 1, SMALL_MALITSKY_POCK = 2 };
 
 struct SmallLpArgs {
   int n, m, num_eq;

@@ -544,4 +544,260 @@ __global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void steps_kernel(Ste
   }
 }
 
+
+// ---- several constant-step or Malitsky-Pock take_steps per launch (pdhg_take_steps_constant / _malitsky_pock) ----
+// The two other step-size policies in a persistent kernel of their own name (steps_kernel keeps its text: its LP forms
+// sit at their register limit).  PDHG_DEVICE_LOOP=1 alone reaches it; the launch shape -- coop_grid workgroups, or
+// 8 x coop_grid in the XCD-local mode with the ticket numbering and the early leave --, the barriers' words, epochs and
+// census, the control line and the coherence rules are steps_kernel's (the comment block in front of StepsCtl): every
+// load of a vector that another compute unit may have rewritten is ldc<true>, what a thread re-reads after its own
+// store stays plain.  Statement by statement the two policies of small_lp_kernel.hpp, with grid barriers where that
+// kernel has __syncthreads().
+//
+// Constant (pdhg.jl:737-767): no reduction, no decision, no table of powers -- every step is accepted with weight
+// step_size.  Three barriers per step:
+//   phase 0  x', xbar with theta = 1 (primal_body; a QP with the kept Q x) + the previous accept's deferred sum_x update
+//   phase 1  y' from A xbar + the deferred sum_y update; a QP also Q x' into the other Q x buffer (it flips with x)
+//   phase 2  A'y' (MODE_PLAIN: nobody reads the interaction sums under this policy, and the row sums are the same bits)
+// then one look at the barriers' error word, which decides whether the step counts.
+//
+// Malitsky-Pock (pdhg.jl:555-647), LPs, a primal average that is not empty (the first-accept quirk stays on the host):
+//   phase 0  x' with tau = entry / primal_weight (no xbar from primal_body) + the deferred sum_x update; thread 0: the
+//            first trial step; xbar = x' + (step / entry)(x' - x) by xbar_pairs_body, primal_body's mapping: a thread
+//            reads the x' it wrote itself, so no barrier stands between the two
+//   then up to MALITSKY_POCK_MAX_TRIALS dual trials: barrier; phase 1 (y', sum dy^2, the deferred sum_y update);
+//   barrier; phase 2 (A'y' and its sums); the third barrier, whose XCD leaders reduce (final_reduce_lp), apply
+//   malitsky_pock_rule to raw[2] and raw[3] and publish the decision through the control line as steps_kernel does.
+//   Rejected: every workgroup forms xbar again with the new ratio.  Accepted: flip, the average update pending with
+//   weight `entry`, the accepted step is the next take_step's step size.  Sixty rejections: numerical_error, the
+//   launch ends, iterate, step size and ratio stay as they came.
+// The long rows' tickets advance by one per product run: uses_a / uses_t per dual trial, uses_q per constant step.
+//
+// result words: steps_kernel's table, except [0] the step size of the NEXT take_step, [9] nonzero: aborted on a barrier
+// time-out, 1 + the dual trials of the unfinished take_step (they ran, so their tickets are drawn, but [2] does not
+// count them: the host takes that take_step again from its start), [12] the ratio (a launch never ends inside a
+// take_step otherwise).
+struct PolicyStepsArgs : StepsKernelArgs {
+  double ratio, downscaling_factor, breaking_factor, interpolation_coefficient;     // Malitsky-Pock alone
+};
+
+// steps_kernel's third barrier, as a function for the kernel below: arrive; the XCD's last arriver meets the other
+// leaders, adds the block partials, lets thread 0 apply `rule` (res -> accept, next step size) and publishes
+// {epoch, accept}, the next step size and a check word in the XCD's control line, which IS the release.  On return
+// s_dec holds [0] accept, [2] the next step size, [3] nonzero: a barrier timed out.
+template <bool LOCAL, typename Rule>
+__device__ __forceinline__ void lp_decision_barrier(const StepsKernelArgs &a, unsigned long long epoch, unsigned long long err_pref,
+                                                    int *s_leader, double *s_dec, double *s_res8, Rule rule) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    *s_leader = 0;
+    s_dec[3] = (double)err_pref;
+    if (err_pref == 0) {
+      const unsigned xcd = xcc_id();
+      unsigned long long *slot = reinterpret_cast<unsigned long long *>(a.ctl->slot[xcd]);
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      const unsigned long long cnt = LOCAL ? (unsigned long long)a.local_g : (unsigned long long)a.xcd_cnt[xcd];
+      const unsigned long long prev = __hip_atomic_fetch_add(&a.sync->xcd_arrive[xcd][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (prev + 1 == cnt * epoch) {
+        if (LOCAL) asm volatile("buffer_inv sc1" ::: "memory");
+        else if (!xcd_leader_meet(a.sync, epoch, a.nxcd, 4ull)) s_dec[3] = 4.0;
+        *s_leader = (s_dec[3] == 0.0) ? 1 : 0;       // (a leader whose wait ran out publishes nothing: its waiters leave through the error word)
+      } else {
+        for (long spins = 0;;) {
+          const unsigned long long w0 = __hip_atomic_load(slot + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const unsigned long long w1 = __hip_atomic_load(slot + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const unsigned long long w2 = __hip_atomic_load(slot + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if ((w0 >> 2) == epoch && (w0 ^ w1 ^ WORDS_CHECK_SALT) == w2) {
+            s_dec[0] = (double)(w0 & 1ull);
+            s_dec[2] = __longlong_as_double((long long)w1);
+            break;
+          }
+          __builtin_amdgcn_s_sleep(1);
+          if (++spins > GRID_SPIN_LIMIT) { __hip_atomic_store(&a.sync->error[0], 5ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); s_dec[3] = 5.0; break; }
+          if ((spins & 0xFFF) == 0) {
+            const unsigned long long ew = __hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (ew != 0) { s_dec[3] = (double)ew; break; }
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (*s_leader) {                                           // workgroup-uniform
+    double res[5];
+    final_reduce_lp<PDHG_STEPS_LP_BATCH>(a.ctl->sp, res, s_res8);
+    if (threadIdx.x == 0) {
+      int accept = 0;
+      double next = 0.0;
+      rule(res, accept, next);
+      unsigned long long *slot = reinterpret_cast<unsigned long long *>(a.ctl->slot[xcc_id()]);
+      const unsigned long long w0 = (epoch << 2) | (accept ? 1ull : 0ull);
+      const unsigned long long w1 = (unsigned long long)__double_as_longlong(next);
+      __hip_atomic_store(slot + 0, w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(slot + 1, w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(slot + 2, w0 ^ w1 ^ WORDS_CHECK_SALT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      s_dec[0] = (double)accept; s_dec[2] = next;
+    }
+  }
+  if (threadIdx.x == 0) asm volatile("s_dcache_inv" ::: "memory");
+  __syncthreads();
+}
+
+template <bool LOCAL, int POLICY, bool QP>
+__global__ __launch_bounds__(TPB, PDHG_TRIAL_WAVES_PER_EU) void policy_steps_kernel(PolicyStepsArgs a) {
+  static_assert(POLICY == SMALL_CONSTANT || POLICY == SMALL_MALITSKY_POCK, "the adaptive policy has steps_kernel");
+  static_assert(!(QP && POLICY == SMALL_MALITSKY_POCK), "Malitsky and Pock linesearch is only supported for LPs");
+  __shared__ double prod[BLOCK_NNZ];
+  __shared__ double red[6][TPB / WAVE];
+  __shared__ int s_leader;
+  __shared__ double s_dec[4];
+  // thread 0's doubles of the loop's state, in LDS as in steps_kernel: [0] step size of the trial, [1] step size on entry
+  // of the take_step, [2] weight of the pending average update, [3] / [4] the averages' weight sums, [5] the ratio
+  __shared__ double s_st[6];
+  __shared__ double s_res8[8];
+  int w = blockIdx.x, nwg = gridDim.x;
+  constexpr bool local = LOCAL;
+  if (local) {                                               // XCD-local mode: steps_kernel's numbering and early leave
+    if (xcc_id() != a.local_home) return;
+    __shared__ int s_w;
+    if (threadIdx.x == 0)
+      s_w = (int)(__hip_atomic_fetch_add(&a.sync->ticket[0][0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - a.local_ticket_base);
+    __syncthreads();
+    w = s_w; nwg = a.local_g;
+    if (w >= nwg) return;
+  }
+  int flip = 0, pend = a.pend, steps = 0, trials = 0, open = 0, num_err = 0, hw_err = 0;
+  if (threadIdx.x == 0) { s_st[0] = a.step_size; s_st[1] = a.step_size; s_st[2] = a.pend_w; s_st[3] = a.wsum_x; s_st[4] = a.wsum_y; s_st[5] = a.ratio; }
+  unsigned long long epoch = a.epoch;
+  Prefetched f;
+  __syncthreads();
+  auto barrier = [&](unsigned long long err_pref) {
+    if (local) grid_barrier_local(a.sync, ++epoch, a.local_home, (unsigned long long)a.local_g, err_pref);
+    else grid_barrier(a.sync, ++epoch, a.nxcd, a.xcd_cnt, err_pref);
+  };
+  auto error_word = [&]() { return threadIdx.x == 0 ? __hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull; };
+  // phase 1 of both policies: y' and sum dy^2 (+ the deferred sum_y update); `run`: products of A this launch has run
+  auto dual_phase = [&](const double *y, double *yn, double sigma, double pend_w, int run) {
+    EpiArgs e{};
+    e.y = y; e.b = a.b; e.y_next = yn; e.sigma = sigma; e.num_eq = a.num_eq;
+    e.partials = a.pA; e.stride = a.pA_slots; e.lo_offset = a.pA_slots;
+    if (pend) { e.sum_y = a.sum_y; e.avg_w = pend_w; }
+    product_phase<MODE_DUAL, true>(a.A, a.xbar, e, a.uses_a + (unsigned long long)run, a.relaxed, f, prod, red, w, nwg);
+  };
+  if constexpr (POLICY == SMALL_CONSTANT) {
+    const double step = a.step_size;
+    const double tau = step / a.primal_weight, sigma = a.primal_weight * step;
+    unsigned long long err_pref = error_word();
+    while (steps < a.n_steps) {
+      const double pend_w = s_st[2];
+      double *x = flip ? a.xb : a.xa, *xn = flip ? a.xa : a.xb;
+      double *y = flip ? a.yb : a.ya, *yn = flip ? a.ya : a.yb;
+      double *aty = flip ? a.atyb : a.atya, *atyn = flip ? a.atya : a.atyb;
+      // ---- phase 0: x' and xbar (+ the deferred sum_x update of the previous accept)
+      primal_body<QP, true, true>(a.n, x, a.c, aty, QP ? (flip ? a.qxb : a.qxa) : nullptr, bound_dense(a.lb), bound_dense(a.ub), tau, 1.0, xn,
+                                  a.xbar, pend_w, pend ? a.sum_x : nullptr, w, nwg);
+      product_prefetch(a.A, f, w, nwg);
+      barrier(err_pref);
+      // ---- phase 1: y' (+ the deferred sum_y update); a QP: Q x' for the next step's gradient
+      err_pref = error_word();
+      dual_phase(y, yn, sigma, pend_w, steps);
+      if constexpr (QP) {
+        Prefetched none;
+        none.kind = 0;
+        EpiArgs e{};
+        e.out = flip ? a.qxa : a.qxb;
+        int wq = w - a.A.grid % nwg;                         // Q's row blocks start at the workgroup after A's last one
+        wq += wq < 0 ? nwg : 0;
+        product_phase<MODE_PLAIN, true>(a.Q, xn, e, a.uses_q + (unsigned long long)steps, a.relaxed, none, prod, red, wq, nwg);
+      }
+      pend = 0;
+      product_prefetch(a.T, f, w, nwg);
+      barrier(err_pref);
+      // ---- phase 2: A'y'
+      err_pref = error_word();
+      {
+        EpiArgs e{};
+        e.out = atyn;
+        product_phase<MODE_PLAIN, true>(a.T, yn, e, a.uses_t + (unsigned long long)steps, a.relaxed, f, prod, red, w, nwg);
+      }
+      barrier(err_pref);
+      // ---- has a barrier timed out?  Then this step does not count (the host takes it again from the state left).  Read
+      // after the step's last barrier; the same word serves the next step's first one.
+      err_pref = error_word();
+      if (threadIdx.x == 0) s_dec[3] = (double)err_pref;
+      __syncthreads();
+      const int bad = __builtin_amdgcn_readfirstlane((int)(s_dec[3] != 0.0));
+      if (bad) { hw_err = 1; break; }
+      flip ^= 1; pend = 1; steps += 1; trials += 1;          // update_solution_in_solver_state with weight step_size
+      if (threadIdx.x == 0) { s_st[2] = step; s_st[3] = s_st[3] + step; s_st[4] = s_st[4] + step; }
+      __syncthreads();                                       // (s_dec is rewritten, s_st read, in the next step)
+    }
+  }
+  if constexpr (POLICY == SMALL_MALITSKY_POCK) {
+    while (steps < a.n_steps) {
+      const double entry = s_st[1], pend_w = s_st[2], ratio_in = s_st[5];
+      double *x = flip ? a.xb : a.xa, *xn = flip ? a.xa : a.xb;
+      double *y = flip ? a.yb : a.ya, *yn = flip ? a.ya : a.yb;
+      double *aty = flip ? a.atyb : a.atya, *atyn = flip ? a.atya : a.atyb;
+      unsigned long long err_pref = error_word();
+      // ---- phase 0: x' with the step size on entry (+ the deferred sum_x update); the first trial step
+      primal_body<false, false, true>(a.n, x, a.c, aty, nullptr, bound_dense(a.lb), bound_dense(a.ub), entry / a.primal_weight, 0.0, xn, a.xbar,
+                                      pend_w, pend ? a.sum_x : nullptr, w, nwg);
+      if (threadIdx.x == 0) s_st[0] = malitsky_pock_first_step(entry, ratio_in, a.interpolation_coefficient);
+      __syncthreads();
+      int acc = 0;
+      open = 0;
+      for (int it = 0; it < MALITSKY_POCK_MAX_TRIALS && !acc; ++it) {
+        const double step = s_st[0];
+        const double ratio = step / entry, sigma = a.primal_weight * step;
+        if (it > 0) err_pref = error_word();
+        // ---- xbar = x' + ratio (x' - x): the thread's own x'
+        xbar_pairs_body(a.n, x, xn, ratio, a.xbar, w, nwg);
+        product_prefetch(a.A, f, w, nwg);
+        barrier(err_pref);
+        // ---- phase 1: y' and sum dy^2 (+ the deferred sum_y update, in the take_step's first trial)
+        err_pref = error_word();
+        dual_phase(y, yn, sigma, pend_w, trials + open);
+        pend = 0;
+        product_prefetch(a.T, f, w, nwg);
+        barrier(err_pref);
+        // ---- phase 2: A'y' and its sums
+        err_pref = error_word();
+        {
+          EpiArgs e{};
+          e.x = x; e.x_next = xn; e.aty = aty; e.aty_next = atyn;
+          e.partials = a.pAt; e.stride = a.pAt_stride; e.lo_offset = 3 * a.pAt_stride;
+          product_phase<MODE_ATY, true>(a.T, yn, e, a.uses_t + (unsigned long long)(trials + open), a.relaxed, f, prod, red, w, nwg);
+        }
+        // ---- third barrier: the leaders reduce and decide
+        ++epoch;
+        lp_decision_barrier<LOCAL>(a, epoch, err_pref, &s_leader, s_dec, s_res8, [&](const double (&res)[5], int &accept, double &next) {
+          const MalitskyPockRule rule = malitsky_pock_rule(res, step, a.breaking_factor, a.downscaling_factor);
+          accept = rule.accept; next = rule.next_step;
+        });
+        const int bad = __builtin_amdgcn_readfirstlane((int)(s_dec[3] != 0.0));
+        if (bad) { hw_err = 1; break; }                      // this trial does not count
+        acc = __builtin_amdgcn_readfirstlane((int)(s_dec[0] != 0.0));
+        open += 1;
+        if (threadIdx.x == 0) {
+          if (acc) { s_st[1] = step; s_st[5] = ratio; s_st[2] = entry; s_st[3] = s_st[3] + entry; s_st[4] = s_st[4] + entry; }
+          else s_st[0] = s_dec[2];
+        }
+        __syncthreads();                                     // the state is read, s_dec / s_leader rewritten, in the next trial
+      }
+      if (hw_err) break;
+      trials += open; open = 0;
+      // sixty rejections: the iterate, the step size and the ratio stay as they came (the take_step has used up the pending update)
+      if (!acc) { num_err = 1; break; }
+      flip ^= 1; pend = 1; steps += 1;                       // update_solution_in_solver_state with the step size on entry as weight
+    }
+  }
+  if (w == 0 && threadIdx.x == 0) {
+    const double r[STEPS_RES_K] = {s_st[1], (double)steps, (double)trials, (double)flip, (double)pend, s_st[2], s_st[3], s_st[4],
+                                   (double)num_err, hw_err ? (double)(1 + open) : 0.0, (double)epoch,
+                                   (double)__hip_atomic_load(&a.sync->error[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), s_st[5]};
+    publish_words(a.res_host, STEPS_RES_CAP, STEPS_RES_K, a.seq, [&](int q) { return r[q]; });
+  }
+}
+
 }  // namespace

@@ -269,6 +269,20 @@ __device__ __forceinline__ void diff_pairs_body(int n, const double *a, const do
   }
   if ((n & 1) && bid == 0 && threadIdx.x == 0) out[n - 1] = a[n - 1] - b[n - 1];
 }
+// xbar_body's expression with the same mapping: the multi-step Malitsky-Pock kernel forms xbar -- again after every
+// rejected dual trial -- from the x' the thread wrote itself in the primal step
+__device__ __forceinline__ void xbar_pairs_body(int n, const double *x, const double *x_next, double theta, double *xbar, int bid, int nb) {
+  const int npair = n >> 1;
+  const int stride = nb * TPB;
+  auto one = [&](int j) {
+    const double v = x_next[j];
+    const double d = v - x[j];
+    const double t = theta * d;
+    xbar[j] = v + t;
+  };
+  for (int p = bid * TPB + threadIdx.x; p < npair; p += stride) { one(2 * p); one(2 * p + 1); }
+  if ((n & 1) && bid == 0 && threadIdx.x == 0) one(n - 1);
+}
 __global__ __launch_bounds__(TPB) void diff_kernel(int n, const double *__restrict__ a,
                                                    const double *__restrict__ b,
                                                    double *__restrict__ out) {

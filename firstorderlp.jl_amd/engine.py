@@ -230,8 +230,9 @@ class HipPdhgEngine:
         return ss.value, it.value, kkt.value, bool(err.value), done.value
 
     def take_steps_constant(self, n_steps, step_size, primal_weight, cumulative_kkt_passes):
-        """pdhg_take_steps_constant: `n_steps` constant-step take_steps in one call.  Returns
-        (cumulative_kkt_passes, steps_done)."""
+        """pdhg_take_steps_constant: `n_steps` constant-step take_steps in one call.  A small LP takes the batch in the
+        one-workgroup kernel; with PDHG_DEVICE_LOOP=1 a medium LP or QP takes it in the persistent multi-step kernel (the
+        same bits); otherwise launch by launch.  Returns (cumulative_kkt_passes, steps_done)."""
         kkt = ctypes.c_double(cumulative_kkt_passes)
         done = ctypes.c_int64(0)
         _lib.check(self._L.pdhg_take_steps_constant(self._h, int(n_steps), step_size, primal_weight, ctypes.byref(kkt),
@@ -241,7 +242,8 @@ class HipPdhgEngine:
     def take_steps_malitsky_pock(self, n_steps, downscaling_factor, breaking_factor, interpolation_coefficient,
                                  step_size, ratio_step_sizes, primal_weight, total_number_iterations,
                                  cumulative_kkt_passes):
-        """pdhg_take_steps_malitsky_pock: `n_steps` take_steps in one call (an LP only).  Returns (step_size,
+        """pdhg_take_steps_malitsky_pock: `n_steps` take_steps in one call (an LP only; the paths of
+        take_steps_constant, a take_step into an empty primal average always launch by launch).  Returns (step_size,
         ratio_step_sizes, total_number_iterations, cumulative_kkt_passes, numerical_error, steps_done)."""
         ss = ctypes.c_double(step_size)
         ratio = ctypes.c_double(ratio_step_sizes)

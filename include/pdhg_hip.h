@@ -45,7 +45,10 @@
  *   PDHG_COOP            1 | 0                         one persistent kernel per trial (csrc/trial_kernel.hpp)
  *   PDHG_DEVICE_LOOP     1 | 0                         several take_steps per launch of the persistent kernel.  Unset: LPs, while QPs
  *                                                      go launch by launch; 1: whenever eligible, QPs too large for the small class
- *                                                      included (Q and Q' in the stream layout); 0: never.  Same bits either way
+ *                                                      included (Q and Q' in the stream layout); 0: never.  The constant and the
+ *                                                      Malitsky-Pock policy (pdhg_take_steps_constant, pdhg_take_steps_malitsky_pock,
+ *                                                      a fleet's singly stepped members) enter the kernel with 1 alone, LPs and QPs:
+ *                                                      unset or 0 they go launch by launch.  Read once per call.  Same bits either way
  *   PDHG_SMALL_LP        1 | 0                         whole batches of steps in one workgroup (csrc/small_lp_kernel.hpp)
  *   PDHG_SMALL_QP        0 | 1                         small QPs in that class too (Q and Q' of rows <= 256 entries, 11 n + 4 m doubles
  *                                                      <= 144 KiB): solo, and in a fleet's shared launches beside the LPs.  Read when the
