@@ -698,7 +698,7 @@ void destroy_shard(pdhg_handle *h) {
   if (h->steps_ctl) (void)hipFree(h->steps_ctl);
   if (h->steps_pow_dev) (void)hipFree(h->steps_pow_dev);
   if (h->steps_pow_host) (void)hipHostFree(h->steps_pow_host);
-  if (h->policy_sp_host) (void)hipHostFree(h->policy_sp_host);
+  if (h->steps_sp_host) (void)hipHostFree(h->steps_sp_host);
   if (h->steps_res) (void)hipHostFree(h->steps_res);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);

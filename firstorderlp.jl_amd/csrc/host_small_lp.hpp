@@ -99,18 +99,25 @@ int small_lp_collect(pdhg_handle *h, unsigned long long seq, StepIO &io) {
   return 0;
 }
 
-// Up to n_steps take_steps from the step state `io` on, as coop_steps; returns 1 when not eligible (nothing launched)
-int small_lp_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
+// What the two solo launchers open with: the class (1: not eligible), the device, the pending term -- the launch consumes
+// it; one that only x or only y still owes is applied first -- and the launch's dynamic LDS, opted in for `policy`'s kernel.
+static int small_lp_begin(pdhg_handle *h, int policy, size_t *lds) {
   if (!small_lp_eligible(h)) return 1;
   HIP_TRY(hipSetDevice(h->device));
-  int rc;
-  drop_staging(h);      // (the launch consumes the pending term)
-  if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
+  drop_staging(h);
+  if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if (int rc = flush_pending(L)) return rc; }
+  *lds = small_lp_lds_bytes(h);
+  return small_lp_lds_limit(h->device, policy, 0, *lds, h->has_q);
+}
+
+// Up to n_steps take_steps from the step state `io` on, as coop_steps; returns 1 when not eligible (nothing launched)
+int small_lp_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
+  size_t lds = 0;
+  int rc = small_lp_begin(h, SMALL_ADAPTIVE, &lds);
+  if (rc) return rc;
   const int n = (int)std::min<int64_t>(n_steps, 1 << 20);
   int max_trials = 0, table_len = 0;
   if ((rc = steps_prepare(h, n, io, &max_trials, &table_len))) return rc;
-  const size_t lds = small_lp_lds_bytes(h);
-  if ((rc = small_lp_lds_limit(h->device, SMALL_ADAPTIVE, 0, lds, h->has_q))) return rc;
   const SmallLpArgs a = small_lp_stage(h, n, max_trials, table_len, io.step_size, io.primal_weight, h->steps_pow_dev,
                                        h->steps_pow_dev + table_len);
   const auto c1 = std::chrono::steady_clock::now();
@@ -164,14 +171,10 @@ int small_policy_collect(pdhg_handle *h, unsigned long long seq, PolicyIO &io) {
 // Up to n_steps take_steps of io.policy in one launch; returns 1 when not eligible (nothing launched).  Malitsky-Pock:
 // the caller has seen to it that the primal average is not empty.
 int small_policy_steps(pdhg_handle *h, int64_t n_steps, PolicyIO &io) {
-  if (!small_lp_eligible(h)) return 1;
-  HIP_TRY(hipSetDevice(h->device));
-  int rc;
-  drop_staging(h);      // (the launch consumes the pending term)
-  if (h->pend_x != h->pend_y) { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
+  size_t lds = 0;
+  int rc = small_lp_begin(h, io.policy, &lds);
+  if (rc) return rc;
   if ((rc = steps_result_words(h))) return rc;
-  const size_t lds = small_lp_lds_bytes(h);
-  if ((rc = small_lp_lds_limit(h->device, io.policy, 0, lds, h->has_q))) return rc;
   const SmallLpArgs a = small_policy_stage(h, small_policy_launch_steps(io.policy, n_steps), io);
   const bool few = small_lp_few_rows(h);
   const auto c1 = std::chrono::steady_clock::now();

@@ -39,6 +39,23 @@ int xcd_census(hipStream_t stream, int grid, GridSync *sync, unsigned long long 
   HIP_TRY(hipGetLastError());
   return census_read(stream, sync, total, nxcd, cnt);
 }
+// The handle's all-XCD census (coop_prepare) and what goes with it into the argument block of a persistent launch
+// (TrialKernelArgs, StepsKernelArgs).
+template <typename Args>
+static void census_args(const pdhg_handle *h, Args &a) {
+  a.nxcd = h->coop_nxcd; a.relaxed = h->relaxed ? 1 : 0;
+  a.trace = h->coop_trace;
+  for (int x = 0; x < 8; ++x) a.xcd_cnt[x] = h->coop_xcd_cnt[x];
+}
+// A barrier of an all-XCD persistent launch (`kernel` names it) ran into its spin limit: the handle's barrier counters are
+// out of step now, so it leaves the one-launch paths for good.
+static void coop_timed_out(pdhg_handle *h, const char *kernel, double code) {
+  h->coop_mode = 0;
+  h->coop_fallbacks += 1;
+  fprintf(stderr, "[pdhg_hip] %s: a grid barrier timed out (code %g; is the device shared with another "
+                  "persistent kernel?) -- this handle uses the %s path from here on\n", kernel, code,
+          graph_eligible(h) ? "graph" : "separate-launch");
+}
 
 // grid of the persistent launch + the census of workgroups per XCD (once per handle)
 // cap_limit: at most this many workgroups (several shards share a device); several_items: accept more items than
@@ -141,9 +158,8 @@ int coop_trial(pdhg_handle *h, const TrialArgs &ta, double out[5]) {
   }
   a.seq_dev = h->seq_dev; a.res_host = h->res_host; a.sync = h->gsync;
   h->seq_expected += 1;
-  a.launch = h->coop_launches; a.seq = h->seq_expected; a.nxcd = h->coop_nxcd; a.relaxed = h->relaxed ? 1 : 0;
-  a.trace = h->coop_trace;
-  for (int x = 0; x < 8; ++x) a.xcd_cnt[x] = h->coop_xcd_cnt[x];
+  a.launch = h->coop_launches; a.seq = h->seq_expected;
+  census_args(h, a);
   // test knob: raise the barriers' error word in front of launch number k, as a time-out in it would (the launch
   // then runs without synchronisation and reports the error; the recovery below is what is being tested)
   static const long break_at = dev_env("PDHG_COOP_TEST_BREAK_AT") ? atol(dev_env("PDHG_COOP_TEST_BREAK_AT")) : -1;
@@ -172,12 +188,8 @@ int coop_trial(pdhg_handle *h, const TrialArgs &ta, double out[5]) {
     // workgroup waits any more, every workgroup still runs every phase, so the launch has ended and the elementwise
     // work that does not depend on the barriers -- the deferred average update it carried -- is applied exactly once.
     // x', y', A'y' and the sums are not trustworthy: the caller repeats the trial on the graph / plain path (its
-    // inputs x, y, A'y are untouched), and this handle stays there (the barrier counters are out of step now).
-    h->coop_mode = 0;
-    h->coop_fallbacks += 1;
-    fprintf(stderr, "[pdhg_hip] one-launch trial: a grid barrier timed out (code %g; is the device shared with another "
-                    "persistent kernel?) -- this handle uses the %s path from here on\n", h->res_error,
-            graph_eligible(h) ? "graph" : "separate-launch");
+    // inputs x, y, A'y are untouched), and this handle stays there (coop_timed_out).
+    coop_timed_out(h, "one-launch trial", h->res_error);
     return 1;
   }
   return 0;
@@ -214,8 +226,7 @@ static int steps_prepare(pdhg_handle *h, int n, const StepIO &io, int *max_trial
     h->steps_pow_dev = h->steps_pow_host = nullptr;
     h->steps_pow_cap = std::max(table_len, 512);
     HIP_TRY(hipMalloc((void **)&h->steps_pow_dev, sizeof(double) * 2 * (size_t)h->steps_pow_cap));
-    // (room behind the tables: coop_steps stages its FinalSpec there)
-    HIP_TRY(hipHostMalloc((void **)&h->steps_pow_host, sizeof(double) * 2 * (size_t)h->steps_pow_cap + sizeof(FinalSpec) + 64, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void **)&h->steps_pow_host, sizeof(double) * 2 * (size_t)h->steps_pow_cap, hipHostMallocDefault));
   }
   // the t-th trial of the launch runs with total_number_iterations = total + t + 1 and uses k1 = that + 1 (pdhg.jl:713-714)
   for (int t = 0; t < table_len; ++t) {
@@ -291,59 +302,67 @@ static bool device_loop_for(pdhg_handle *h) {
   return device_loop;
 }
 
-// Up to n_steps adaptive take_steps in ONE launch (steps_kernel, trial_kernel.hpp), from the step state `io` on.  On
-// return io counts the take_steps taken (fewer than n_steps when the launch ran out of its trial budget, met
-// numerical_error, or a barrier timed out: the caller goes on from the state left).  Returns 1 when nothing was
-// launched (the multi-step kernel is not wanted for this call, or the handle does not suit it).
-int coop_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
-  if (io.device_loop < 0) io.device_loop = device_loop_for(h) ? 1 : 0;
-  if (!io.device_loop || h->profile || !coop_eligible(h) || !h->lazy_accept || h->pend_x != h->pend_y) return 1;
-  drop_staging(h);      // (the launch consumes the pending term)
-  int rc = coop_prepare(h);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  const int n = (int)std::min<int64_t>(n_steps, 1 << 20);
-  int max_trials = 0, table_len = 0;
+// ---- what the two launchers of the persistent multi-step kernels (coop_steps, coop_policy_steps) share -----------------
+// Eligibility, staging, the launch and what follows the wait: this text decides whether a handle's barrier counters and
+// long-row tickets stay in step after a time-out, so it stands once.  `device_loop`: the launcher's own decision (how
+// PDHG_DEVICE_LOOP is read differs between the two).
+static bool steps_launch_eligible(pdhg_handle *h, int device_loop) {
+  return device_loop && !h->profile && coop_eligible(h) && h->lazy_accept && h->pend_x == h->pend_y;
+}
+
+// The StepsKernelArgs part of a launch's argument block (policy_steps_kernel's derives from it) for up to n_steps
+// take_steps from (step_size, primal_weight) on; what only one kernel reads -- tables and trial budget, the Malitsky-Pock
+// factors -- the launcher adds.  A QP's Q product always goes along; with_qt: Q' too, with dx, Q'dx and the block
+// partials of their dot product (the adaptive rule's interaction term).  final_spec: the XCD leaders reduce block
+// partials, and read where those are from the control block.  *local_out: the launch takes the XCD-local form.
+static int steps_stage(pdhg_handle *h, StepsKernelArgs &a, int n_steps, double step_size, double primal_weight, bool with_qt,
+                       bool final_spec, bool *local_out) {
+  int rc;
   if (!h->steps_ctl) {
     HIP_TRY(hipMalloc((void **)&h->steps_ctl, sizeof(StepsCtl)));
     HIP_TRY(hipMemsetAsync(h->steps_ctl, 0, sizeof(StepsCtl), h->stream));
   }
-  std::lock_guard<std::mutex> one_at_a_time(coop_device_mutex(h->device));
-  if ((rc = steps_prepare(h, n, io, &max_trials, &table_len))) return rc;
-  StepsKernelArgs a{};
   a.n = (int)h->n; a.num_eq = (int)h->num_eq;
   a.xa = h->x; a.xb = h->x_next; a.ya = h->y; a.yb = h->y_next; a.atya = h->aty; a.atyb = h->aty_next;
   a.c = h->c; a.lb = h->lb; a.ub = h->ub; a.b = h->b;
   a.xbar = h->xbar; a.sum_x = h->sum_x; a.sum_y = h->sum_y;
+  // trial_product counts one use of the product, as a single trial makes: taken back here, because how many times the
+  // launch runs each product -- what its long rows' tickets advance by -- is known only from its results (steps_finish)
   EpiArgs none{};
   a.A = trial_product(h, h->A, nullptr, none);
   a.T = trial_product(h, h->At, nullptr, none);
-  h->A.coop_uses -= 1; h->At.coop_uses -= 1;       // (trial_product counted one use: the launch's own count comes back with the results)
+  h->A.coop_uses -= 1; h->At.coop_uses -= 1;
   a.uses_a = a.A.uses; a.uses_t = a.T.uses;
   a.pA = h->pA; a.pAt = h->pAt; a.pA_slots = h->A.slots(); a.pAt_stride = h->pAt_stride;
-  const bool qp = h->has_q;
-  if (qp) {
-    // the QP form keeps Q x for the iterate and for the trial point (qx / qx2 flip with x); the first trial's Q x is
-    // this product, ahead of the launch in stream order -- the bits of trial_kernel's phase -1
+  if (h->has_q) {
+    // Q x is kept for the iterate and for the trial point (qx / qx2 flip with x).  The kernels compute Q x' beside the
+    // other products and never Q x of the iterate they start from: the first trial's Q x is this product, ahead of the
+    // launch in stream order -- the bits of trial_kernel's phase -1
     if (!h->qx2 && (rc = alloc_zero(&h->qx2, h->n))) return rc;
     EpiArgs qe{};
     qe.out = h->qx;
     if ((rc = launch_spmv<MODE_PLAIN, 2>(h, h->Q, h->x, qe))) return rc;
     a.Q = trial_product(h, h->Q, nullptr, none);
-    a.Qt = trial_product(h, h->Qt, nullptr, none);
-    h->Q.coop_uses -= 1; h->Qt.coop_uses -= 1;
-    a.uses_q = a.Q.uses; a.uses_qt = a.Qt.uses;
+    h->Q.coop_uses -= 1;
+    a.uses_q = a.Q.uses;
     a.qxa = h->qx; a.qxb = h->qx2;
-    a.dx = h->tmp_n; a.qtdx = h->tmp_n2; a.pq = h->pQ; a.q_blocks = h->ew_grid_n;
+    if (with_qt) {
+      a.Qt = trial_product(h, h->Qt, nullptr, none);
+      h->Qt.coop_uses -= 1;
+      a.uses_qt = a.Qt.uses;
+      a.dx = h->tmp_n; a.qtdx = h->tmp_n2; a.pq = h->pQ; a.q_blocks = h->ew_grid_n;
+    }
   }
-  const FinalSpec sp = trial_final_spec(h, h->At.slots(), h->A.slots(), qp ? h->ew_grid_n : 0, h->A.slots(), nullptr);
-  memcpy(h->steps_pow_host + 2 * (size_t)table_len, &sp, sizeof sp);        // staged behind the pow tables (pinned)
-  HIP_TRY(hipMemcpyAsync(&h->steps_ctl->sp, h->steps_pow_host + 2 * (size_t)table_len, sizeof sp, hipMemcpyHostToDevice, h->stream));
-  a.primal_weight = io.primal_weight; a.step_size = io.step_size;
-  a.n_steps = n; a.max_trials = max_trials; a.table_len = table_len;
+  if (final_spec) {
+    const FinalSpec sp = trial_final_spec(h, h->At.slots(), h->A.slots(), a.q_blocks, h->A.slots(), nullptr);
+    if (!h->steps_sp_host) HIP_TRY(hipHostMalloc((void **)&h->steps_sp_host, sizeof(FinalSpec), hipHostMallocDefault));
+    memcpy(h->steps_sp_host, &sp, sizeof sp);      // (pinned; free again once the launch's results are back)
+    HIP_TRY(hipMemcpyAsync(&h->steps_ctl->sp, h->steps_sp_host, sizeof sp, hipMemcpyHostToDevice, h->stream));
+  }
+  a.primal_weight = primal_weight; a.step_size = step_size;
+  a.n_steps = n_steps;
   a.pend = h->pend_x ? 1 : 0; a.pend_w = h->pend_w;
   a.wsum_x = h->sum_x_weights; a.wsum_y = h->sum_y_weights;
-  a.pow_red = h->steps_pow_dev; a.pow_growth = h->steps_pow_dev + table_len;
   const bool local = steps_local_prepare(h) == 0;
   a.epoch = local ? h->local_epoch : h->coop_epoch;
   a.sync = local ? h->lsync : h->gsync; a.ctl = h->steps_ctl; a.res_host = h->steps_res;
@@ -359,47 +378,83 @@ int coop_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
     a.local_ticket_base = 0;
   }
   a.seq = ++h->steps_seq;
-  a.nxcd = h->coop_nxcd; a.relaxed = h->relaxed ? 1 : 0;
-  a.trace = h->coop_trace;
-  for (int x = 0; x < 8; ++x) a.xcd_cnt[x] = h->coop_xcd_cnt[x];
+  census_args(h, a);
+  *local_out = local;
+  return 0;
+}
+
+// The launch itself, in its XCD-local or its all-XCD form; *launched: when the call returned.
+template <typename Args>
+static int steps_launch(pdhg_handle *h, bool local, void (*local_form)(Args), void (*all_xcd_form)(Args), const Args &a,
+                        std::chrono::steady_clock::time_point *launched) {
   const auto c1 = std::chrono::steady_clock::now();
-  if (local && qp) hipLaunchKernelGGL((steps_kernel<true, true>), dim3(8 * h->coop_grid), dim3(TPB), 0, h->stream, a);
-  else if (qp) hipLaunchKernelGGL((steps_kernel<false, true>), dim3(h->coop_grid), dim3(TPB), 0, h->stream, a);
-  else if (local) hipLaunchKernelGGL(steps_kernel<true>, dim3(8 * h->coop_grid), dim3(TPB), 0, h->stream, a);
-  else hipLaunchKernelGGL(steps_kernel<false>, dim3(h->coop_grid), dim3(TPB), 0, h->stream, a);
+  if (local) hipLaunchKernelGGL(local_form, dim3(8 * h->coop_grid), dim3(TPB), 0, h->stream, a);
+  else hipLaunchKernelGGL(all_xcd_form, dim3(h->coop_grid), dim3(TPB), 0, h->stream, a);
   HIP_TRY(hipGetLastError());
-  const auto c2 = std::chrono::steady_clock::now();
-  h->t_launch += std::chrono::duration<double>(c2 - c1).count();
-  double r[STEPS_RES_K];
-  if ((rc = steps_collect(h, a.seq, io, r))) return rc;
-  h->t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - c2).count();
+  *launched = std::chrono::steady_clock::now();
+  h->t_launch += std::chrono::duration<double>(*launched - c1).count();
+  return 0;
+}
+
+// A launch's result words r (the table is at StepsKernelArgs, trial_kernel.hpp) into what the handle keeps about its
+// barriers, tickets and vectors; the step state is the launcher's affair.  local, with_qt: as staged; `kernel` names the
+// launch in a time-out's message.
+static void steps_finish(pdhg_handle *h, const double r[STEPS_RES_K], bool local, bool with_qt, const char *kernel) {
   const int64_t trials = (int64_t)r[2];
-  const bool flip = r[3] != 0.0, aborted = r[9] != 0.0 || r[11] != 0.0;
+  const bool flip = r[3] != 0.0, aborted = r[9] != 0.0 || r[11] != 0.0, qp = h->has_q;
+  // products actually run: the counted trials, and after a time-out the trial it rose in and, under Malitsky-Pock,
+  // ([9] - 1) more trials of the take_step that the host now takes again from its start (steps_kernel publishes 0 or 1)
+  const unsigned long long run = (unsigned long long)trials + (r[9] != 0.0 ? (unsigned long long)r[9] : aborted ? 1ull : 0ull);
   h->steps_launches += 1; h->steps_trials += trials;
   if (local) { h->local_epoch = (unsigned long long)r[10]; h->local_launches += 1; }
   else h->coop_epoch = (unsigned long long)r[10];
-  h->A.coop_uses += (unsigned long long)trials + (aborted ? 1ull : 0ull);
-  h->At.coop_uses += (unsigned long long)trials + (aborted ? 1ull : 0ull);
-  if (qp) {
-    h->Q.coop_uses += (unsigned long long)trials + (aborted ? 1ull : 0ull);
-    h->Qt.coop_uses += (unsigned long long)trials + (aborted ? 1ull : 0ull);
-  }
+  h->A.coop_uses += run;
+  h->At.coop_uses += run;
+  if (qp) h->Q.coop_uses += run;
+  if (qp && with_qt) h->Qt.coop_uses += run;
   if (flip) { std::swap(h->x, h->x_next); std::swap(h->y, h->y_next); std::swap(h->aty, h->aty_next); }
   if (flip && qp) std::swap(h->qx, h->qx2);
   h->pend_x = h->pend_y = r[4] != 0.0;
   h->pend_w = r[5];
-  if (trials > 0 || aborted) h->state_version += 1;     // (bump_version of a single handle)
+  if (run > 0) h->state_version += 1;     // (bump_version of a single handle)
   if (aborted && local) {
     // the XCD-local form failed (a workgroup of the launch was not where the census saw it): the all-XCD form from here on
     h->local_mode = 0;
-    fprintf(stderr, "[pdhg_hip] multi-step trial kernel, XCD-local mode: a barrier timed out (code %g) -- all-XCD mode from here on\n", r[11]);
+    fprintf(stderr, "[pdhg_hip] %s, XCD-local mode: a barrier timed out (code %g) -- all-XCD mode from here on\n", kernel, r[11]);
   } else if (aborted) {
-    h->coop_mode = 0;
-    h->coop_fallbacks += 1;
-    fprintf(stderr, "[pdhg_hip] multi-step trial kernel: a grid barrier timed out (code %g; is the device shared with another "
-                    "persistent kernel?) -- this handle uses the %s path from here on\n", r[11],
-            graph_eligible(h) ? "graph" : "separate-launch");
+    coop_timed_out(h, kernel, r[11]);
   }
+}
+
+// Up to n_steps adaptive take_steps in ONE launch (steps_kernel, trial_kernel.hpp), from the step state `io` on.  On
+// return io counts the take_steps taken (fewer than n_steps when the launch ran out of its trial budget, met
+// numerical_error, or a barrier timed out: the caller goes on from the state left).  Returns 1 when nothing was
+// launched (the multi-step kernel is not wanted for this call, or the handle does not suit it).
+int coop_steps(pdhg_handle *h, int64_t n_steps, StepIO &io) {
+  if (io.device_loop < 0) io.device_loop = device_loop_for(h) ? 1 : 0;
+  if (!steps_launch_eligible(h, io.device_loop)) return 1;
+  drop_staging(h);      // (the launch consumes the pending term)
+  int rc = coop_prepare(h);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const int n = (int)std::min<int64_t>(n_steps, 1 << 20);
+  int max_trials = 0, table_len = 0;
+  std::lock_guard<std::mutex> one_at_a_time(coop_device_mutex(h->device));
+  if ((rc = steps_prepare(h, n, io, &max_trials, &table_len))) return rc;
+  const bool qp = h->has_q;
+  bool local = false;
+  StepsKernelArgs a{};
+  if ((rc = steps_stage(h, a, n, io.step_size, io.primal_weight, qp, true, &local))) return rc;
+  a.max_trials = max_trials; a.table_len = table_len;
+  a.pow_red = h->steps_pow_dev; a.pow_growth = h->steps_pow_dev + table_len;
+  std::chrono::steady_clock::time_point c2;
+  if (qp) rc = steps_launch(h, local, steps_kernel<true, true>, steps_kernel<false, true>, a, &c2);
+  else rc = steps_launch(h, local, steps_kernel<true, false>, steps_kernel<false, false>, a, &c2);
+  if (rc) return rc;
+  double r[STEPS_RES_K];
+  if ((rc = steps_collect(h, a.seq, io, r))) return rc;
+  h->t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - c2).count();
+  steps_finish(h, r, local, qp, "multi-step trial kernel");
   return 0;
 }
 
@@ -427,16 +482,17 @@ static void policy_account(pdhg_handle *h, PolicyIO &io, const double r[STEPS_RE
 
 int small_policy_launch_steps(int policy, int64_t n_steps);      // host_small_lp.hpp
 
-// Up to n_steps take_steps of io.policy in ONE launch of policy_steps_kernel, from the step state `io` on; coop_steps'
-// eligibility, launch shape and handling of a barrier time-out.  PDHG_DEVICE_LOOP=1 alone switches it on, for LPs and
-// QPs (read once per call); unset or 0, the two policies go launch by launch as before.  Returns 1 when nothing was
-// launched.  Malitsky-Pock: the caller has seen to it that the primal average is not empty and that the handle is an LP.
+// Up to n_steps take_steps of io.policy in ONE launch of policy_steps_kernel, from the step state `io` on; eligibility,
+// staging, launch shape and handling of a barrier time-out are the adaptive launcher's (steps_launch_eligible,
+// steps_stage, steps_launch, steps_finish).  PDHG_DEVICE_LOOP=1 alone switches it on, for LPs and QPs (read once per
+// call); unset or 0, the two policies go launch by launch as before.  Returns 1 when nothing was launched.
+// Malitsky-Pock: the caller has seen to it that the primal average is not empty and that the handle is an LP.
 int coop_policy_steps(pdhg_handle *h, int64_t n_steps, PolicyIO &io) {
   if (io.device_loop < 0) {
     const char *dl_env = getenv("PDHG_DEVICE_LOOP");
     io.device_loop = dl_env && dl_env[0] == '1' ? 1 : 0;
   }
-  if (!io.device_loop || h->profile || !coop_eligible(h) || !h->lazy_accept || h->pend_x != h->pend_y) return 1;
+  if (!steps_launch_eligible(h, io.device_loop)) return 1;
   const bool mp = io.policy == SMALL_MALITSKY_POCK, qp = h->has_q;
   if (mp && qp) return 1;
   drop_staging(h);      // (the launch consumes the pending term)
@@ -444,106 +500,29 @@ int coop_policy_steps(pdhg_handle *h, int64_t n_steps, PolicyIO &io) {
   if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
   if ((rc = steps_result_words(h))) return rc;
-  if (!h->steps_ctl) {
-    HIP_TRY(hipMalloc((void **)&h->steps_ctl, sizeof(StepsCtl)));
-    HIP_TRY(hipMemsetAsync(h->steps_ctl, 0, sizeof(StepsCtl), h->stream));
-  }
   std::lock_guard<std::mutex> one_at_a_time(coop_device_mutex(h->device));
+  // (the worst case of a launch -- MALITSKY_POCK_MAX_TRIALS trials in every take_step -- stays within the largest adaptive launch's trials)
+  const int n = small_policy_launch_steps(io.policy, n_steps);
+  bool local = false;
   PolicyStepsArgs a{};
-  a.n = (int)h->n; a.num_eq = (int)h->num_eq;
-  a.xa = h->x; a.xb = h->x_next; a.ya = h->y; a.yb = h->y_next; a.atya = h->aty; a.atyb = h->aty_next;
-  a.c = h->c; a.lb = h->lb; a.ub = h->ub; a.b = h->b;
-  a.xbar = h->xbar; a.sum_x = h->sum_x; a.sum_y = h->sum_y;
-  EpiArgs none{};
-  a.A = trial_product(h, h->A, nullptr, none);
-  a.T = trial_product(h, h->At, nullptr, none);
-  h->A.coop_uses -= 1; h->At.coop_uses -= 1;       // (trial_product counted one use: the launch's own count comes back with the results)
-  a.uses_a = a.A.uses; a.uses_t = a.T.uses;
-  a.pA = h->pA; a.pAt = h->pAt; a.pA_slots = h->A.slots(); a.pAt_stride = h->pAt_stride;
-  if (qp) {
-    // Q x is kept for the iterate and for the trial point (qx / qx2 flip with x); the first step's Q x is this product,
-    // ahead of the launch in stream order -- the bits of trial_kernel's phase -1
-    if (!h->qx2 && (rc = alloc_zero(&h->qx2, h->n))) return rc;
-    EpiArgs qe{};
-    qe.out = h->qx;
-    if ((rc = launch_spmv<MODE_PLAIN, 2>(h, h->Q, h->x, qe))) return rc;
-    a.Q = trial_product(h, h->Q, nullptr, none);
-    h->Q.coop_uses -= 1;
-    a.uses_q = a.Q.uses;
-    a.qxa = h->qx; a.qxb = h->qx2;
-  }
+  // (Malitsky-Pock alone decides on sums: the leaders' second stage reads where the block partials are, as steps_kernel's does)
+  if ((rc = steps_stage(h, a, n, io.step_size, io.primal_weight, false, mp, &local))) return rc;
   if (mp) {
-    // the leaders' second stage reads where the block partials are from the control block, as steps_kernel's does
-    const FinalSpec sp = trial_final_spec(h, h->At.slots(), h->A.slots(), 0, h->A.slots(), nullptr);
-    if (!h->policy_sp_host) HIP_TRY(hipHostMalloc((void **)&h->policy_sp_host, sizeof(FinalSpec), hipHostMallocDefault));
-    memcpy(h->policy_sp_host, &sp, sizeof sp);
-    HIP_TRY(hipMemcpyAsync(&h->steps_ctl->sp, h->policy_sp_host, sizeof sp, hipMemcpyHostToDevice, h->stream));
     a.ratio = io.ratio;
     a.downscaling_factor = io.downscaling_factor; a.breaking_factor = io.breaking_factor;
     a.interpolation_coefficient = io.interpolation_coefficient;
   }
-  a.primal_weight = io.primal_weight; a.step_size = io.step_size;
-  // (the worst case of a launch -- MALITSKY_POCK_MAX_TRIALS trials in every take_step -- stays within the largest adaptive launch's trials)
-  a.n_steps = small_policy_launch_steps(io.policy, n_steps);
-  a.pend = h->pend_x ? 1 : 0; a.pend_w = h->pend_w;
-  a.wsum_x = h->sum_x_weights; a.wsum_y = h->sum_y_weights;
-  const bool local = steps_local_prepare(h) == 0;
-  a.epoch = local ? h->local_epoch : h->coop_epoch;
-  a.sync = local ? h->lsync : h->gsync; a.ctl = h->steps_ctl; a.res_host = h->steps_res;
-  a.local_g = local ? h->coop_grid : 0; a.local_home = 0;
-  if (local && dev_env("PDHG_COOP_LOCAL_TEST_BAD")) a.local_g += 8;      // (coop_steps' test knob)
-  if (local) {                                                             // the stayers' ticket word: zeroed before every launch (coop_steps)
-    HIP_TRY(hipMemsetAsync(&h->lsync->ticket[0][0], 0, sizeof(unsigned long long), h->stream));
-    a.local_ticket_base = 0;
-  }
-  a.seq = ++h->steps_seq;
-  a.nxcd = h->coop_nxcd; a.relaxed = h->relaxed ? 1 : 0;
-  for (int x = 0; x < 8; ++x) a.xcd_cnt[x] = h->coop_xcd_cnt[x];
-  const dim3 grid(local ? 8 * h->coop_grid : h->coop_grid);
-  const auto c1 = std::chrono::steady_clock::now();
-#define POLICY_STEPS_LAUNCH(POLICY, QP)                                                                                          \
-  do {                                                                                                                           \
-    if (local) hipLaunchKernelGGL((policy_steps_kernel<true, POLICY, QP>), grid, dim3(TPB), 0, h->stream, a);                    \
-    else hipLaunchKernelGGL((policy_steps_kernel<false, POLICY, QP>), grid, dim3(TPB), 0, h->stream, a);                         \
-  } while (0)
-  if (mp) POLICY_STEPS_LAUNCH(SMALL_MALITSKY_POCK, false);
-  else if (qp) POLICY_STEPS_LAUNCH(SMALL_CONSTANT, true);
-  else POLICY_STEPS_LAUNCH(SMALL_CONSTANT, false);
-#undef POLICY_STEPS_LAUNCH
-  HIP_TRY(hipGetLastError());
-  const auto c2 = std::chrono::steady_clock::now();
-  h->t_launch += std::chrono::duration<double>(c2 - c1).count();
+  std::chrono::steady_clock::time_point c2;
+  if (mp) rc = steps_launch(h, local, policy_steps_kernel<true, SMALL_MALITSKY_POCK, false>, policy_steps_kernel<false, SMALL_MALITSKY_POCK, false>, a, &c2);
+  else if (qp) rc = steps_launch(h, local, policy_steps_kernel<true, SMALL_CONSTANT, true>, policy_steps_kernel<false, SMALL_CONSTANT, true>, a, &c2);
+  else rc = steps_launch(h, local, policy_steps_kernel<true, SMALL_CONSTANT, false>, policy_steps_kernel<false, SMALL_CONSTANT, false>, a, &c2);
+  if (rc) return rc;
   h->pend_x = h->pend_y = false;                   // the launch carries the deferred average update
   double r[STEPS_RES_K];
   if ((rc = wait_words(h->stream, h->steps_res, STEPS_RES_CAP, STEPS_RES_K, a.seq, r, 400000000L,
                        "multi-step kernel finished without publishing its results"))) return rc;
   h->t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - c2).count();
   policy_account(h, io, r, r[12]);
-  const int64_t trials = (int64_t)r[2];
-  const bool flip = r[3] != 0.0, aborted = r[9] != 0.0 || r[11] != 0.0;
-  // products actually run: the counted trials, and after a time-out the trial it rose in and ([9] - 1) trials of the
-  // take_step that the host now takes again from its start
-  const unsigned long long run = (unsigned long long)trials + (r[9] != 0.0 ? (unsigned long long)r[9] : aborted ? 1ull : 0ull);
-  h->steps_launches += 1; h->steps_trials += trials;
-  if (local) { h->local_epoch = (unsigned long long)r[10]; h->local_launches += 1; }
-  else h->coop_epoch = (unsigned long long)r[10];
-  h->A.coop_uses += run;
-  h->At.coop_uses += run;
-  if (qp) h->Q.coop_uses += run;
-  if (flip) { std::swap(h->x, h->x_next); std::swap(h->y, h->y_next); std::swap(h->aty, h->aty_next); }
-  if (flip && qp) std::swap(h->qx, h->qx2);
-  h->pend_x = h->pend_y = r[4] != 0.0;
-  h->pend_w = r[5];
-  if (run > 0) h->state_version += 1;
-  if (aborted && local) {
-    h->local_mode = 0;
-    fprintf(stderr, "[pdhg_hip] multi-step policy kernel, XCD-local mode: a barrier timed out (code %g) -- all-XCD mode from here on\n", r[11]);
-  } else if (aborted) {
-    h->coop_mode = 0;
-    h->coop_fallbacks += 1;
-    fprintf(stderr, "[pdhg_hip] multi-step policy kernel: a grid barrier timed out (code %g; is the device shared with another "
-                    "persistent kernel?) -- this handle uses the %s path from here on\n", r[11],
-            graph_eligible(h) ? "graph" : "separate-launch");
-  }
+  steps_finish(h, r, local, false, "multi-step policy kernel");
   return 0;
 }

@@ -238,7 +238,7 @@ struct pdhg_handle {
   // several take_steps per launch (steps_kernel): control lines, pow tables (device + pinned staging), result words
   StepsCtl *steps_ctl = nullptr;
   double *steps_pow_dev = nullptr, *steps_pow_host = nullptr, *steps_res = nullptr;
-  FinalSpec *policy_sp_host = nullptr;   // pinned staging of the FinalSpec a Malitsky-Pock launch of policy_steps_kernel uploads
+  FinalSpec *steps_sp_host = nullptr;    // pinned staging of the FinalSpec a multi-step launch uploads (steps_stage)
   int steps_pow_cap = 0;
   unsigned long long steps_seq = 0;
   int64_t steps_launches = 0, steps_trials = 0;
