@@ -215,7 +215,7 @@ int graph_build(pdhg_handle *h, pdhg_handle::TrialGraph &G, double tau, double t
   HIP_TRY(graph_add_kernel(G.graph, &G.n_primal, {}, (const void *)primal_kernel<false, true>, a.primal_grid, dim3(TPB),
                            a.n, (const double *)h->x, (const double *)h->c, (const double *)h->aty, nullq,
                            bound_view(h, 0), bound_view(h, 1), tau, theta, h->x_next, h->xbar,
-                           h->pend_w, h->pend_x ? h->sum_x : (double *)nullptr, 0.0, (double *)nullptr));
+                           h->pend_w, h->pend_x ? h->sum_x : (double *)nullptr, 0.0, (double *)nullptr, 0));
   // K3+K4 on CSR(A), K5+K6 on CSR(A'): the stream kernel (or its column-slab passes, a
   // chain) and the long-row pair are independent branches
   std::vector<hipGraphNode_t> dual_done, aty_done;
@@ -265,7 +265,7 @@ int graph_trial(pdhg_handle *h, const TrialArgs &ta, double out[5]) {
       HIP_TRY(graph_set_kernel(G->exec, G->n_primal, (const void *)primal_kernel<false, true>, a.primal_grid, dim3(TPB),
                                a.n, (const double *)h->x, (const double *)h->c, (const double *)h->aty, nullq,
                                bound_view(h, 0), bound_view(h, 1), tau, theta, h->x_next, h->xbar,
-                               h->pend_w, h->pend_x ? h->sum_x : (double *)nullptr, 0.0, (double *)nullptr));
+                               h->pend_w, h->pend_x ? h->sum_x : (double *)nullptr, 0.0, (double *)nullptr, 0));
       G->tau = tau; G->theta = theta; G->bounds_version = h->bounds_version;
       G->add_x = h->pend_x; G->add_wx = h->pend_w;
     }

@@ -609,6 +609,20 @@ int ensure_pair_buffers(pdhg_handle *h) {
   return 0;
 }
 
+// The streaming loads of a plain handle's separate launches (vector_kernels.hpp: primal_body, spmv_kernels.hpp:
+// epi_load).  The graph, the persistent kernels, batches, fleets and shard groups keep the loads they had.
+// D: the sweep the loads make room for -- the one whose epilogue it is, or (primal_kernel) the A xbar sweep behind it.
+// They pay where that sweep has more workgroups than the device holds at once (two per CU: several residency rounds,
+// row epilogues beside the tile loops of the next round; random LPs, 10 entries per row: 10M x 10M -57 us per
+// take_step, 6M x 6M -7 us) and cost where one round holds everything and the vectors stay in the caches from kernel
+// to kernel (4M x 4M +3 us, 2M x 2M +9 us, 1M x 1M +5 us): NOTEBOOK section 14.
+// knob (dev, read per launch: the tests compare both forms in one process): "0" the plain loads, "1" the streaming ones.
+int stream_loads(const pdhg_handle *h, const CsrDev &D, const char *knob) {
+  if (h->grp || h->bat || h->owner || h->fleet || h->fleet_of || !D.tiled) return 0;
+  if (const char *ev = dev_env(knob)) return ev[0] != '0';
+  return D.grid > 256 * 2;        // (the slots choose_tile_cols plans with)
+}
+
 // K1+K2 on this shard's column slice (the whole vector for a plain handle).
 // QP: Q is replicated and acts on the full x (kept full on every shard).
 // stage (trial_dispatch alone asks for it; pend_x is set): the paired form -- sum_x is read, sum_x_alt written with the
@@ -629,11 +643,12 @@ int launch_primal(pdhg_handle *h, double tau, double theta, bool write_xbar, boo
   // a plain handle reads the compact bounds; a column slice does not start on a block of the masks: DENSE
   const bool whole = o == 0 && h->cn == h->n;
   const BoundView lbv = whole ? bound_view(h, 0) : bound_dense(h->lb + o), ubv = whole ? bound_view(h, 1) : bound_dense(h->ub + o);
+  const int stream = whole ? stream_loads(h, h->A, "PDHG_PRIMAL_STREAM") : 0;
 #define PK(HQ, WX)                                                                           \
   hipLaunchKernelGGL((primal_kernel<HQ, WX>), dim3(grid), dim3(TPB), 0, h->stream, n,        \
                      h->x + o, h->c + o, h->aty + o, h->has_q ? h->qx + o : nullptr, lbv, ubv, tau, theta, \
                      h->x_next + o, h->xbar + o, h->pend_w, h->pend_x ? h->sum_x + o : nullptr, stage_w,   \
-                     stage ? h->sum_x_alt : (double *)nullptr)
+                     stage ? h->sum_x_alt : (double *)nullptr, stream)
   if (h->has_q) { if (write_xbar) PK(true, true); else PK(true, false); }
   else          { if (write_xbar) PK(false, true); else PK(false, false); }
 #undef PK
@@ -702,6 +717,7 @@ int launch_dual(pdhg_handle *h, double sigma, bool stage = false, double stage_w
   ProfScope ps(h, PDHG_K_SPMV_DUAL);
   EpiArgs e = dual_epilogue(h, sigma);
   if (stage) { e.sum_y_out = h->sum_y_alt; e.avg_w2 = stage_w; }
+  e.stream = stream_loads(h, h->A, "PDHG_EPI_STREAM");
   const int rc = launch_spmv<MODE_DUAL, 0>(h, h->A, h->xbar, e);
   if (!rc && !stage) h->pend_y = false;
   if (!rc && stage) { h->staged = true; h->staged_w = stage_w; }
@@ -736,7 +752,9 @@ int launch_dual_chunked(pdhg_handle *h, double sigma, bool wait_events) {
 
 int launch_aty_fused(pdhg_handle *h) {
   ProfScope ps(h, PDHG_K_SPMV_ATY);
-  return launch_spmv<MODE_ATY, 1>(h, h->At, h->y_next, aty_epilogue(h));
+  EpiArgs e = aty_epilogue(h);
+  e.stream = stream_loads(h, h->At, "PDHG_EPI_STREAM");
+  return launch_spmv<MODE_ATY, 1>(h, h->At, h->y_next, e);
 }
 
 int launch_aty_plain(pdhg_handle *h, const double *yin, double *out) {

@@ -43,11 +43,22 @@ struct EpiArgs {
   // sum_y_out = (sum_y + avg_w * y) + avg_w2 * y' is what the sums are once this trial is accepted with weight avg_w2
   double *sum_y_out;
   double avg_w2;
+  // the streaming policy of the epilogue's loads (spmv_tiled_kernel<MODE_DUAL, .> and <MODE_ATY, .> alone read it;
+  // launch-uniform): the row operands are touched once per launch, and the caches are what holds the vector the sweeps
+  // gather from -- this launch's column tiles, and what this epilogue writes for the next product
+  int stream;
 };
 
 template <bool COH>
 __device__ __forceinline__ void stc(double *p, double v) {
   *p = v;
+}
+// NT: the non-temporal form (known at compile time: a run-time choice between two loads of one address is folded into
+// one load by the compiler, and the policy is lost)
+template <bool COH, bool NT>
+__device__ __forceinline__ double epi_ld(const double *p) {
+  if (NT) return __builtin_nontemporal_load(p);
+  return ldc<COH>(p);
 }
 // The operands a row's epilogue reads, apart from the row sum: loaded by epi_load, consumed by epi_apply, so that a
 // kernel can request them long before the sum exists (sj_kernels.hpp).  row_epilogue is the two back to back: one
@@ -55,17 +66,18 @@ __device__ __forceinline__ void stc(double *p, double v) {
 struct EpiOps {
   double a, b, c;
 };
-template <int MODE, bool COH = false>
+// STREAM: non-temporal loads (false: the text is what it was)
+template <int MODE, bool COH = false, bool STREAM = false>
 __device__ __forceinline__ EpiOps epi_load(const EpiArgs &e, int r) {
   EpiOps o{0.0, 0.0, 0.0};
   if (MODE == MODE_DUAL) {
-    o.a = ldc<COH>(e.y + r);
-    o.b = e.b[r];
-    if (e.sum_y) o.c = ldc<COH>(e.sum_y + r);
+    o.a = epi_ld<COH, STREAM>(e.y + r);
+    o.b = STREAM ? __builtin_nontemporal_load(e.b + r) : e.b[r];
+    if (e.sum_y) o.c = epi_ld<COH, STREAM>(e.sum_y + r);
   } else if (MODE == MODE_ATY) {
-    o.a = ldc<COH>(e.x_next + r);
-    o.b = ldc<COH>(e.x + r);
-    o.c = ldc<COH>(e.aty + r);
+    o.a = epi_ld<COH, STREAM>(e.x_next + r);
+    o.b = epi_ld<COH, STREAM>(e.x + r);
+    o.c = epi_ld<COH, STREAM>(e.aty + r);
   }
   return o;
 }
@@ -107,10 +119,10 @@ __device__ __forceinline__ void epi_apply(const EpiArgs &e, int r, double s, con
     dd_add(acc.hi[2], acc.lo[2], dd * dd);
   }
 }
-template <int MODE, bool COH = false, bool PAIR = false>
+template <int MODE, bool COH = false, bool PAIR = false, bool STREAM = false>
 __device__ __forceinline__ void row_epilogue(const EpiArgs &e, int r, double s,
                                              Acc3 &acc) {
-  epi_apply<MODE, COH, PAIR>(e, r, s, epi_load<MODE, COH>(e, r), acc);
+  epi_apply<MODE, COH, PAIR>(e, r, s, epi_load<MODE, COH, STREAM>(e, r), acc);
 }
 
 template <int MODE>
@@ -828,7 +840,12 @@ __global__ __launch_bounds__(TW_WPB * WAVE) void spmv_tiled_kernel(
   }
   const int nrows = rr.y - rr.x;
   // (the one kernel whose MODE_DUAL epilogue knows the paired average update: launch_dual alone sets e.sum_y_out)
-  for (int r = lane; r < nrows; r += WAVE) row_epilogue<MODE, false, MODE == MODE_DUAL>(e, rr.x + r, acc[r], acc3);
+  // (and the one whose MODE_DUAL / MODE_ATY epilogues know the streaming loads, EpiArgs::stream: one row loop per form)
+  if (MODE != MODE_PLAIN && e.stream) {
+    for (int r = lane; r < nrows; r += WAVE) row_epilogue<MODE, false, MODE == MODE_DUAL, true>(e, rr.x + r, acc[r], acc3);
+  } else {
+    for (int r = lane; r < nrows; r += WAVE) row_epilogue<MODE, false, MODE == MODE_DUAL>(e, rr.x + r, acc[r], acc3);
+  }
   constexpr int NQ = ModeNQ<MODE>::value;
   if (NQ > 0) {
     block_sum_dd<NQ, TW_THREADS>(acc3, red);

@@ -53,23 +53,52 @@ struct BoundView {
 };
 __host__ __device__ inline BoundView bound_dense(const double *p) { return BoundView{p, nullptr, nullptr, nullptr, 0.0, BND_DENSE}; }
 
+// The streaming loads of the plain-launch primal_kernel (its `stream` argument, launch-uniform): every operand is read
+// once per launch, and what the caches hold when the kernel ends should be the xbar it wrote, which the sweep behind it
+// gathers from.  The builtin wants native vector types for the 16-byte loads.
+typedef double nt_dbl2_t __attribute__((ext_vector_type(2)));
+typedef unsigned long long nt_ull2_t __attribute__((ext_vector_type(2)));
+// NT: the non-temporal form (known at compile time: a run-time choice between two loads of one address is folded into
+// one load by the compiler, and the policy is lost)
+template <bool NT>
+__device__ __forceinline__ double2 ld_pair(const double *a, int p) {
+  if (NT) {
+    const nt_dbl2_t v = __builtin_nontemporal_load(reinterpret_cast<const nt_dbl2_t *>(a) + p);
+    return double2{v.x, v.y};
+  }
+  return reinterpret_cast<const double2 *>(a)[p];
+}
+
 // entries 2p and 2p + 1
-template <int BM>
+template <int BM, bool NT = false>
 __device__ __forceinline__ double2 bound_pair(const BoundView &b, int p) {
-  if (BM == BND_DENSE) return reinterpret_cast<const double2 *>(b.dense)[p];
+  if (BM == BND_DENSE) return ld_pair<NT>(b.dense, p);
   double2 r = {b.def, b.def};
   if (BM == BND_SPARSE) {
     const int blk = p >> 6, l = p & 63;                 // one block per wave: both loads are one line per wave
-    const ulonglong2 w = reinterpret_cast<const ulonglong2 *>(b.mask)[blk];
-    const int base = b.blk[blk];
+    ulonglong2 w;
+    int base;
+    if (NT) {
+      const nt_ull2_t t = __builtin_nontemporal_load(reinterpret_cast<const nt_ull2_t *>(b.mask) + blk);
+      w.x = t.x; w.y = t.y;
+      base = __builtin_nontemporal_load(b.blk + blk);
+    } else {
+      w = reinterpret_cast<const ulonglong2 *>(b.mask)[blk];
+      base = b.blk[blk];
+    }
     const unsigned long long mine = l < 32 ? w.x : w.y;
     const int sh = 2 * (l & 31);
     const unsigned bits = (unsigned)(mine >> sh) & 3u;
     if (bits) {
       const int rank = __popcll(mine & ((1ull << sh) - 1ull)) + (l < 32 ? 0 : __popcll(w.x));
       const double *e = b.exc + base + rank;
-      if (bits & 1u) r.x = e[0];
-      if (bits & 2u) r.y = e[bits & 1u];
+      if (NT) {
+        if (bits & 1u) r.x = __builtin_nontemporal_load(e);
+        if (bits & 2u) r.y = __builtin_nontemporal_load(e + (bits & 1u));
+      } else {
+        if (bits & 1u) r.x = e[0];
+        if (bits & 2u) r.y = e[bits & 1u];
+      }
     }
   }
   return r;
@@ -93,7 +122,8 @@ __device__ __forceinline__ double bound_at(const BoundView &b, int j) {
 // kernel): coherent loads
 // LBM / UBM: the modes of lb / ub, known at compile time (primal_kernel dispatches on them once per launch; shard
 // slices and the persistent kernels pass DENSE views: the loads they always had)
-template <bool HAS_Q, bool WRITE_XBAR, bool COH = false, int LBM = BND_DENSE, int UBM = BND_DENSE>
+// STREAM: non-temporal loads (the plain-launch primal_kernel alone asks for them; the pairs, not the odd tail)
+template <bool HAS_Q, bool WRITE_XBAR, bool COH = false, int LBM = BND_DENSE, int UBM = BND_DENSE, bool STREAM = false>
 __device__ __forceinline__ void primal_body(
     int n, const double *x, const double *c, const double *aty, const double *qx,
     const BoundView &lb, const BoundView &ub, double tau, double theta, double *x_next, double *xbar,
@@ -106,25 +136,25 @@ __device__ __forceinline__ void primal_body(
   const int npair = n >> 1;
   const int stride = nb * TPB;
   for (int p = bid * TPB + threadIdx.x; p < npair; p += stride) {
-    const double2 xv = reinterpret_cast<const double2 *>(x)[p];
+    const double2 xv = ld_pair<STREAM>(x, p);
     double2 sv = {0.0, 0.0};
     if (sum_x) {
-      sv = reinterpret_cast<double2 *>(sum_x)[p];
+      sv = ld_pair<STREAM>(sum_x, p);
       const double t0 = xv.x * avg_w, t1 = xv.y * avg_w;
       sv.x = sv.x + t0;
       sv.y = sv.y + t1;
       if (!sum_x_out) reinterpret_cast<double2 *>(sum_x)[p] = sv;
     }
-    const double2 cv = reinterpret_cast<const double2 *>(c)[p];
+    const double2 cv = ld_pair<STREAM>(c, p);
     double2 av;
     if (COH) { av.x = ldc<true>(aty + 2 * p); av.y = ldc<true>(aty + 2 * p + 1); }
-    else av = reinterpret_cast<const double2 *>(aty)[p];
-    const double2 lv = bound_pair<LBM>(lb, p);
-    const double2 uv = bound_pair<UBM>(ub, p);
+    else av = ld_pair<STREAM>(aty, p);
+    const double2 lv = bound_pair<LBM, STREAM>(lb, p);
+    const double2 uv = bound_pair<UBM, STREAM>(ub, p);
     double2 qv = {0.0, 0.0};
     if (HAS_Q) {
       if (COH) { qv.x = ldc<true>(qx + 2 * p); qv.y = ldc<true>(qx + 2 * p + 1); }
-      else qv = reinterpret_cast<const double2 *>(qx)[p];
+      else qv = ld_pair<STREAM>(qx, p);
     }
     double2 xn, xb;
     primal_one<HAS_Q, WRITE_XBAR>(xv.x, cv.x, av.x, qv.x, lv.x, uv.x, tau, theta, xn.x, xb.x);
@@ -165,10 +195,15 @@ __global__ __launch_bounds__(TPB) void primal_kernel(
     const double *__restrict__ aty, const double *__restrict__ qx,
     BoundView lb, BoundView ub, double tau,
     double theta, double *__restrict__ x_next, double *__restrict__ xbar,
-    double avg_w, double *__restrict__ sum_x, double avg_w2, double *__restrict__ sum_x_out) {
+    double avg_w, double *__restrict__ sum_x, double avg_w2, double *__restrict__ sum_x_out, int stream) {
+#define PDHG_PB_S(L, U, S)                                                                                              \
+  primal_body<HAS_Q, WRITE_XBAR, false, L, U, S>(n, x, c, aty, qx, lb, ub, tau, theta, x_next, xbar, avg_w, sum_x, blockIdx.x, gridDim.x, \
+                                                 avg_w2, sum_x_out)
 #define PDHG_PB(L, U)                                                                                                   \
-  primal_body<HAS_Q, WRITE_XBAR, false, L, U>(n, x, c, aty, qx, lb, ub, tau, theta, x_next, xbar, avg_w, sum_x, blockIdx.x, gridDim.x, \
-                                              avg_w2, sum_x_out)
+  do {                                                                                                                  \
+    if (stream) PDHG_PB_S(L, U, true);                                                                                  \
+    else PDHG_PB_S(L, U, false);                                                                                        \
+  } while (0)
   switch (lb.mode * 3 + ub.mode) {        // launch-uniform: one loop per pair of modes, no test inside it
     case BND_DENSE * 3 + BND_CONST: PDHG_PB(BND_DENSE, BND_CONST); break;
     case BND_DENSE * 3 + BND_SPARSE: PDHG_PB(BND_DENSE, BND_SPARSE); break;
@@ -181,6 +216,7 @@ __global__ __launch_bounds__(TPB) void primal_kernel(
     default: PDHG_PB(BND_DENSE, BND_DENSE); break;
   }
 #undef PDHG_PB
+#undef PDHG_PB_S
 }
 
 // ---- building the compact forms (bounds_rebuild, pdhg_hip.hip) ----
