@@ -21,7 +21,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _lib
-from .engine import _dp, _MemberEngine, _MemberOwner, _d, _i, _int_p, _pd, _pi
+from .engine import _MemberEngine, _MemberOwner, _d, _i, _int_p, _pd, _pi
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams,
                                           MalitskyPockStepsizeParameters, _check_inputs, _constant_step_estimate,
                                           _device_scaled_problem, _drive_solves, _host_scaled_problem, _initial_point,
@@ -136,65 +136,17 @@ class HipPdhgBatch(_MemberOwner):
                                          growth_exponent, step_sizes, primal_weights, total_number_iterations,
                                          cumulative_kkt_passes, a.ctypes.data_as(_int_p))
 
-    # ---- re-solves on the batch handle (include/pdhg_hip_batch_resolve.h) ----
-    def _live(self):
-        if not getattr(self, "_h", None):
-            raise _lib.PdhgHipError("the batch is closed")
-        return self._h
+    # ---- re-solves on the batch handle (include/pdhg_hip_batch_resolve.h): ``_MemberOwner``'s, over these ----
+    _noun, _resolve_other = "batch", "batched_product"
 
-    def _pointer_table(self, name, values, length):
-        """An array of K pointers (NULL: the member's entry is None) over ``values`` = None or a list of K vectors /
-        None, shapes checked; also returns the arrays, which must outlive the call."""
-        if values is None:
-            return None, []
-        values = list(values)
-        if len(values) != self.K:
-            raise ValueError(f"{name} has {len(values)} entries, the batch has {self.K} members")
-        keep = []
-        table = (_dp * self.K)()
-        for k, v in enumerate(values):
-            if v is None:
-                continue
-            v = _d(v)
-            if v.shape != (length,):
-                raise ValueError(f"{name}[{k}] has {v.shape} entries, a member needs ({length},)")
-            keep.append(v)
-            table[k] = v.ctypes.data_as(_dp)
-        return table, keep
+    def _resolve_calls(self):
+        return (self._L.pdhg_batch_update_problem_vectors, self._L.pdhg_batch_warm_start, self._L.pdhg_batch_resolve_info)
 
     def retain_rescaling(self):
         """``pdhg_batch_resolve_retain``: to be called before ``rescale`` (and after the objective matrix is set).
         The batch keeps every rescaling step's factors once for all members (8 * steps * (n + m) bytes of device
         memory), which ``update_problem_vectors`` and ``warm_start`` need."""
         _lib.check(self._L.pdhg_batch_resolve_retain(self._live()))
-
-    def update_problem_vectors(self, objective_vectors=None, right_hand_sides=None, variable_lower_bounds=None,
-                               variable_upper_bounds=None):
-        """New vectors of the members' ORIGINAL problems, all members in ONE launch: each argument is None or a list of
-        K vectors / None (None: keep).  A member's working vectors become, bit for bit, those of a fresh batch's
-        member created from the updated problems and rescaled with the same parameters."""
-        h = self._live()
-        tables = [self._pointer_table(name, v, length) for name, v, length in (
-            ("objective_vectors", objective_vectors, self.n), ("right_hand_sides", right_hand_sides, self.m),
-            ("variable_lower_bounds", variable_lower_bounds, self.n),
-            ("variable_upper_bounds", variable_upper_bounds, self.n))]
-        _lib.check(self._L.pdhg_batch_update_problem_vectors(h, *[t for t, _ in tables]))
-
-    def warm_start(self, xs=None, ys=None):
-        """``pdhg_batch_warm_start``: member k starts from (xs[k], ys[k]) in the original problem's space with
-        everything else as on a fresh member.  A member whose two entries are None is left as it is; with one entry
-        given the other means zeros; ``xs`` and ``ys`` both None: every member starts from zeros."""
-        h = self._live()
-        tx, ty = self._pointer_table("xs", xs, self.n), self._pointer_table("ys", ys, self.m)
-        _lib.check(self._L.pdhg_batch_warm_start(h, tx[0], ty[0]))
-
-    def resolve_info(self):
-        """dict(shared_launches, carried, single, batched_product): shared re-solve launches so far; members the last
-        ``update_problem_vectors`` / ``warm_start`` carried; members the last ``warm_start`` gave a product of their
-        own; whether it ran the batched product."""
-        info = np.zeros(4, dtype=np.int64)
-        _lib.check(self._L.pdhg_batch_resolve_info(self._live(), _pi(info)))
-        return dict(zip(["shared_launches", "carried", "single", "batched_product"], info.tolist()))
 
 
 def _shared_q(problem):

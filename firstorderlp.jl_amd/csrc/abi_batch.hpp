@@ -34,9 +34,8 @@ struct BatchState {
   int *act_dev = nullptr, *act_host = nullptr;
   double *res_dev = nullptr, *res_host = nullptr;
   int64_t trials = 0;
-  // re-solves (abi_batch_resolve.hpp): shared launches so far; members the last update / warm start carried; members
-  // of the last warm start given a product of their own; whether it ran the batched product
-  int64_t rsv_launches = 0, rsv_carried = 0, rsv_single = 0, rsv_batched = 0;
+  // re-solves (abi_batch_resolve.hpp): what the calls did (`other`: whether the last warm start ran the batched product)
+  ResolveCounters rsv;
 };
 
 static void batch_free_product(BatchProduct &P) {

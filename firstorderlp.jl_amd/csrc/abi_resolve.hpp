@@ -1,5 +1,6 @@
 // abi_resolve.hpp -- part of the single translation unit pdhg_hip.hip (included there, inside its extern "C" block, last).
-// C ABI: RE-SOLVES on a live handle (include/pdhg_hip_resolve.h; kernels in resolve_kernels.hpp).  The matrix copies, the
+// C ABI: RE-SOLVES on a live handle (include/pdhg_hip_resolve.h; kernels in resolve_kernels.hpp; what this form shares
+// with a batch's, abi_batch_resolve.hpp, in host_resolve.hpp).  The matrix copies, the
 // layouts and the rescaling factors depend on A and Q only: a caller who solves the same matrix again with other vectors
 // keeps the handle, sends the new c / b / lb / ub in the space pdhg_create took them in, and names a starting point.
 //
@@ -26,53 +27,13 @@ static int resolve_refuse(pdhg_handle *h, const std::string &who, bool need_reco
 }
 
 int pdhg_resolve_retain(pdhg_handle *h) {
-  int rc = resolve_refuse(h, "pdhg_resolve_retain", false);
-  if (rc) return rc;
-  if (h->rs) return 0;
-  if ((rc = check_handle(h))) return rc;
-  const int64_t n = h->n, m = h->m;
-  ResolveState *R = new ResolveState();
-  h->rs = R;
-  auto body = [&]() -> int {
-    int r2;
-    if ((r2 = alloc_zero(&R->cum_d, n))) return r2;
-    if ((r2 = alloc_zero(&R->cum_e, m))) return r2;
-    if ((r2 = alloc_zero(&R->stage_dev, 3 * n + m))) return r2;
-    HIP_TRY(hipHostMalloc((void **)&R->stage_host, sizeof(double) * (size_t)std::max<int64_t>(3 * n + m, 1), hipHostMallocDefault));
-    hipLaunchKernelGGL(fill_kernel, dim3(h->ew_grid_n), dim3(TPB), 0, h->stream, (int)n, 1.0, R->cum_d);
-    hipLaunchKernelGGL(fill_kernel, dim3(h->ew_grid_m), dim3(TPB), 0, h->stream, (int)m, 1.0, R->cum_e);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
-  };
-  rc = body();
-  if (rc) resolve_release(h);
-  return rc;
+  const int rc = resolve_refuse(h, "pdhg_resolve_retain", false);
+  return rc ? rc : resolve_retain(h, 3 * h->n + h->m);
 }
 
-// the replay of one handle as kernel arguments: `in` = where the given vectors lie on the device, in the order c, lb, ub, b
-// (only the given ones, side by side)
-static ResolveReplayArgs resolve_replay_args(pdhg_handle *h, const double *in, bool gc, bool gb, bool gl, bool gu) {
-  const ResolveState &R = *h->rs;
-  ResolveReplayArgs a{};
-  a.n = (int)h->n; a.m = (int)h->m; a.steps = (int)R.steps; a.rec = R.rec;
-  if (gc) { a.in_c = in; in += h->n; }
-  if (gl) { a.in_lb = in; in += h->n; }
-  if (gu) { a.in_ub = in; in += h->n; }
-  if (gb) { a.in_b = in; in += h->m; }
-  a.c = h->c; a.lb = h->lb; a.ub = h->ub; a.b = h->b;
-  return a;
-}
-// ... and the same vectors packed into `dst` (host); returns the doubles written
-static int64_t resolve_pack_vectors(const pdhg_handle *h, double *dst, const double *c, const double *b, const double *lb, const double *ub) {
-  int64_t off = 0;
-  auto put = [&](const double *src, int64_t len) {
-    if (!src) return;
-    if (len > 0) memcpy(dst + off, src, sizeof(double) * (size_t)len);
-    off += len;
-  };
-  put(c, h->n); put(lb, h->n); put(ub, h->n); put(b, h->m);
-  return off;
+// the replay of one handle as kernel arguments, its given vectors placed at S
+static ResolveReplayArgs resolve_replay_args(pdhg_handle *h, ResolveStage &S, const double *c, const double *b, const double *lb, const double *ub) {
+  return ResolveReplayArgs{(int)h->n, (int)h->m, (int)h->rs->steps, h->rs->rec, resolve_replay_member(h, S, c, b, lb, ub)};
 }
 
 int pdhg_update_problem_vectors(pdhg_handle *h, const double *c, const double *b, const double *lb, const double *ub) {
@@ -84,9 +45,9 @@ int pdhg_update_problem_vectors(pdhg_handle *h, const double *c, const double *b
   const Shards L = shards_of(h);
   if ((rc = flush_pending(L))) return rc;
   ResolveState &R = *h->rs;
-  const int64_t len = resolve_pack_vectors(h, R.stage_host, c, b, lb, ub);
-  if (len > 0) HIP_TRY(hipMemcpyAsync(R.stage_dev, R.stage_host, sizeof(double) * (size_t)len, hipMemcpyHostToDevice, h->stream));
-  const ResolveReplayArgs a = resolve_replay_args(h, R.stage_dev, c != nullptr, b != nullptr, lb != nullptr, ub != nullptr);
+  ResolveStage S{R.stage_host, R.stage_dev};
+  const ResolveReplayArgs a = resolve_replay_args(h, S, c, b, lb, ub);
+  if (S.off > 0) HIP_TRY(hipMemcpyAsync(R.stage_dev, R.stage_host, sizeof(double) * S.off, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(resolve_replay_kernel, dim3(h->ew_grid_nm), dim3(TPB), 0, h->stream, a);
   HIP_TRY(hipGetLastError());
   // the evaluation caches and a fleet's stored check results are keyed by versions that do not see these four arrays
@@ -97,28 +58,15 @@ int pdhg_update_problem_vectors(pdhg_handle *h, const double *c, const double *b
   return 0;
 }
 
-// What a warm start empties on the host side of one handle (the vectors are zeroed by the point kernel).
-static void resolve_clear_host(pdhg_handle *h) {
-  drop_staging(h);
-  h->pend_x = h->pend_y = false;             // a deferred update belongs to the sums being discarded
-  h->pend_w = 0.0;
-  h->sum_x_count = h->sum_y_count = 0;
-  h->sum_x_weights = h->sum_y_weights = 0.0;
-  h->restart_version += 1;                   // the restart point is zeros again: whatever was cached of the old one is stale
-  h->state_version += 1;
-  fleet_forget(h);
-}
-// the point kernel's arguments for one handle: `in` = the given vectors on the device, x then y (only the given ones)
-static ResolvePointArgs resolve_point_args(pdhg_handle *h, const double *in, bool gx, bool gy) {
+// the point kernel's arguments for one handle, its given vectors placed at S (x, then y)
+static ResolvePointArgs resolve_point_args(pdhg_handle *h, ResolveStage &S, const double *x, const double *y) {
   const ResolveState &R = *h->rs;
   ResolvePointArgs a{};
-  a.n = (int)h->n; a.m = (int)h->m; a.zero_aty = gy ? 0 : 1;
-  if (gx) { a.in_x = in; in += h->n; }
-  if (gy) { a.in_y = in; in += h->m; }
+  a.n = (int)h->n; a.m = (int)h->m; a.zero_aty = y ? 0 : 1;
+  a.in_x = S.put(x, h->n); a.in_y = S.put(y, h->m);
   if (R.steps > 0) { a.cum_d = R.cum_d; a.cum_e = R.cum_e; }
   a.x = h->x; a.y = h->y; a.aty = h->aty;
-  a.zn[0] = h->sum_x; a.zn[1] = h->sum_x_alt; a.zn[2] = h->x_r; a.zn[3] = h->has_q ? h->qx : nullptr; a.zn[4] = h->has_q ? h->qx2 : nullptr;
-  a.zm[0] = h->sum_y; a.zm[1] = h->sum_y_alt; a.zm[2] = h->y_r;
+  a.z = resolve_fresh_zeros(h);
   return a;
 }
 
@@ -129,15 +77,13 @@ int pdhg_warm_start(pdhg_handle *h, const double *x, const double *y) {
   if ((rc = check_handle(h))) return rc;
   const Shards L = shards_of(h);
   ResolveState &R = *h->rs;
-  int64_t len = 0;
-  if (x) { if (h->n > 0) memcpy(R.stage_host, x, sizeof(double) * (size_t)h->n); len += h->n; }
-  if (y) { if (h->m > 0) memcpy(R.stage_host + len, y, sizeof(double) * (size_t)h->m); len += h->m; }
-  if (len > 0) HIP_TRY(hipMemcpyAsync(R.stage_dev, R.stage_host, sizeof(double) * (size_t)len, hipMemcpyHostToDevice, h->stream));
+  ResolveStage S{R.stage_host, R.stage_dev};
+  const ResolvePointArgs a = resolve_point_args(h, S, x, y);
+  if (S.off > 0) HIP_TRY(hipMemcpyAsync(R.stage_dev, R.stage_host, sizeof(double) * S.off, hipMemcpyHostToDevice, h->stream));
   resolve_clear_host(h);
-  const ResolvePointArgs a = resolve_point_args(h, R.stage_dev, x != nullptr, y != nullptr);
   hipLaunchKernelGGL(resolve_point_kernel, dim3(h->ew_grid_nm), dim3(TPB), 0, h->stream, a);
   HIP_TRY(hipGetLastError());
-  if (y && (rc = dual_product(L, [](pdhg_handle *s) { return (const double *)s->y; }, [](pdhg_handle *s) { return s->aty; }))) return rc;
+  if (y && (rc = resolve_own_aty(h))) return rc;
   return sync_all(L);
 }
 
@@ -183,23 +129,21 @@ int pdhg_fleet_update_problem_vectors(pdhg_handle *fleet, const double *const *c
     n_items += (size_t)resolve_chunks(h);
     n_data += (size_t)((pc ? h->n : 0) + (pl ? h->n : 0) + (pu ? h->n : 0) + (pb ? h->m : 0));
   }
-  F.rsv_carried = (int64_t)carried.size();
-  F.rsv_single = 0;
+  F.rsv.carried = (int64_t)carried.size();
+  F.rsv.single = 0;
   if (carried.empty()) return 0;
   HIP_TRY(hipSetDevice(fleet->device));
   const size_t item_bytes = sizeof(FleetResolveReplayItem) * n_items, bytes = item_bytes + sizeof(double) * n_data;
   if ((rc = fleet_resolve_reserve(fleet, bytes))) return rc;
   FleetResolveReplayItem *items = (FleetResolveReplayItem *)F.rsv_host;
-  double *data_host = (double *)((char *)F.rsv_host + item_bytes);
-  const double *data_dev = (const double *)((const char *)F.rsv_dev + item_bytes);
-  size_t placed = 0, off = 0;
+  ResolveStage S{(double *)((char *)F.rsv_host + item_bytes), (const double *)((const char *)F.rsv_dev + item_bytes)};
+  size_t placed = 0;
   for (int k : carried) {
     pdhg_handle *h = F.mem[(size_t)k];
     const double *pc = resolve_entry(c, k), *pb = resolve_entry(b, k), *pl = resolve_entry(lb, k), *pu = resolve_entry(ub, k);
     if ((rc = check_handle(h))) return rc;
     { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
-    const ResolveReplayArgs a = resolve_replay_args(h, data_dev + off, pc != nullptr, pb != nullptr, pl != nullptr, pu != nullptr);
-    off += (size_t)resolve_pack_vectors(h, data_host + off, pc, pb, pl, pu);
+    const ResolveReplayArgs a = resolve_replay_args(h, S, pc, pb, pl, pu);
     const int64_t len = std::max(h->n, h->m);
     for (int64_t lo = 0; lo < len; lo += RESOLVE_CHUNK)
       items[placed++] = FleetResolveReplayItem{a, (int)lo, (int)std::min<int64_t>(lo + RESOLVE_CHUNK, len)};
@@ -209,16 +153,9 @@ int pdhg_fleet_update_problem_vectors(pdhg_handle *fleet, const double *const *c
     hipLaunchKernelGGL(fleet_resolve_replay_kernel, dim3((unsigned)placed), dim3(TPB), 0, fleet->stream,
                        (const FleetResolveReplayItem *)F.rsv_dev, (int)placed);
     HIP_TRY(hipGetLastError());
-    F.rsv_launches += 1;
+    F.rsv.launches += 1;
   }
-  for (int k : carried) {
-    pdhg_handle *h = F.mem[(size_t)k];
-    h->state_version += 1;
-    fleet_forget(h);
-    // K view rebuilds -- each a synchronisation, allocations and a round trip -- would undo the shared launch: the views
-    // are rebuilt where they are next read (bounds_fresh); the one-workgroup kernels read the dense arrays and never do
-    if (resolve_entry(lb, k) || resolve_entry(ub, k)) h->bnd_dirty = true;
-  }
+  for (int k : carried) resolve_member_updated(F.mem[(size_t)k], resolve_entry(lb, k) || resolve_entry(ub, k));
   HIP_TRY(hipStreamSynchronize(fleet->stream));         // (the table is free for the next call)
   return 0;
 }
@@ -242,26 +179,23 @@ int pdhg_fleet_warm_start(pdhg_handle *fleet, const double *const *x, const doub
     n_items += (size_t)resolve_chunks(h);
     n_data += (size_t)((px ? h->n : 0) + (py ? h->m : 0));
   }
-  F.rsv_carried = (int64_t)carried.size();
-  F.rsv_single = 0;
+  F.rsv.carried = (int64_t)carried.size();
+  F.rsv.single = 0;
   if (carried.empty()) return 0;
   HIP_TRY(hipSetDevice(fleet->device));
   const size_t item_bytes = sizeof(FleetResolvePointItem) * n_items, bytes = item_bytes + sizeof(double) * n_data;
   if ((rc = fleet_resolve_reserve(fleet, bytes))) return rc;
   FleetResolvePointItem *items = (FleetResolvePointItem *)F.rsv_host;
-  double *data_host = (double *)((char *)F.rsv_host + item_bytes);
-  const double *data_dev = (const double *)((const char *)F.rsv_dev + item_bytes);
-  size_t placed = 0, off = 0;
+  ResolveStage S{(double *)((char *)F.rsv_host + item_bytes), (const double *)((const char *)F.rsv_dev + item_bytes)};
+  size_t placed = 0;
   std::vector<FleetPointArgs> products;        // A'y of the members of the check class, in the launch pdhg_fleet_eval_points uses
-  std::vector<int> own;                        // ... and the members served by their own dual_product
+  std::vector<int> own;                        // ... and the members that take their own (resolve_own_aty)
   for (int k : carried) {
     pdhg_handle *h = F.mem[(size_t)k];
     const double *px = resolve_entry(x, k), *py = resolve_entry(y, k);
     if ((rc = check_handle(h))) return rc;
     resolve_clear_host(h);
-    const ResolvePointArgs a = resolve_point_args(h, data_dev + off, px != nullptr, py != nullptr);
-    if (px) { if (h->n > 0) memcpy(data_host + off, px, sizeof(double) * (size_t)h->n); off += (size_t)h->n; }
-    if (py) { if (h->m > 0) memcpy(data_host + off, py, sizeof(double) * (size_t)h->m); off += (size_t)h->m; }
+    const ResolvePointArgs a = resolve_point_args(h, S, px, py);
     const int64_t len = std::max(h->n, h->m);
     for (int64_t lo = 0; lo < len; lo += RESOLVE_CHUNK)
       items[placed++] = FleetResolvePointItem{a, (int)lo, (int)std::min<int64_t>(lo + RESOLVE_CHUNK, len)};
@@ -281,15 +215,12 @@ int pdhg_fleet_warm_start(pdhg_handle *fleet, const double *const *x, const doub
     hipLaunchKernelGGL(fleet_resolve_point_kernel, dim3((unsigned)placed), dim3(TPB), 0, fleet->stream,
                        (const FleetResolvePointItem *)F.rsv_dev, (int)placed);
     HIP_TRY(hipGetLastError());
-    F.rsv_launches += 1;
+    F.rsv.launches += 1;
   }
   if ((rc = fleet_check_launch(fleet, 0, products, fleet_point_products_kernel, TPB, 0))) return rc;
-  F.rsv_single = (int64_t)own.size();
-  for (int k : own) {
-    pdhg_handle *h = F.mem[(size_t)k];
-    Shards L = shards_of(h);
-    if ((rc = dual_product(L, [](pdhg_handle *s) { return (const double *)s->y; }, [](pdhg_handle *s) { return s->aty; }))) return rc;
-  }
+  F.rsv.single = (int64_t)own.size();
+  for (int k : own)
+    if ((rc = resolve_own_aty(F.mem[(size_t)k]))) return rc;
   HIP_TRY(hipStreamSynchronize(fleet->stream));
   return 0;
 }
@@ -297,7 +228,6 @@ int pdhg_fleet_warm_start(pdhg_handle *fleet, const double *const *x, const doub
 int pdhg_fleet_resolve_info(pdhg_handle *fleet, int64_t out[4]) {
   if (!out) return fail(-1, "out == NULL");
   if (!fleet_of(fleet)) return fail(-1, "pdhg_fleet_resolve_info: not a fleet handle");
-  const FleetState &F = *fleet->fleet;
-  out[0] = F.rsv_launches; out[1] = F.rsv_carried; out[2] = F.rsv_single; out[3] = F.rsv_view_rebuilds;
+  resolve_info(fleet->fleet->rsv, out);
   return 0;
 }

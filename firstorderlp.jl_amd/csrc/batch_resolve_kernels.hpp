@@ -25,19 +25,13 @@ namespace {
 constexpr int BATCH_RESOLVE_TILE = 4;
 static_assert(BATCH_MAX % BATCH_RESOLVE_TILE == 0, "the replay's member table is padded to whole tiles inside BATCH_MAX entries");
 
-// One carried member of a replay.  in_* == nullptr: that vector keeps what it holds -- no load, no store.  An entry that
-// pads the last tile is all nullptr.
-struct BatchReplayMember {
-  const double *in_c, *in_lb, *in_ub, *in_b;      // create space (device staging)
-  double *c, *lb, *ub, *b;                        // the member's working vectors
-};
-
+// table: one ResolveReplayMember per carried member; an entry that pads the last tile is all nullptr
 __global__ __launch_bounds__(TPB) void batch_resolve_replay_kernel(int n, int m, int steps, const double *__restrict__ rec,
-                                                                   const BatchReplayMember *__restrict__ table) {
+                                                                   const ResolveReplayMember *__restrict__ table) {
   constexpr int T = BATCH_RESOLVE_TILE;
   const int tid = blockIdx.x * TPB + threadIdx.x, st = gridDim.x * TPB;
   const int64_t stride = (int64_t)n + m;
-  BatchReplayMember M[T];
+  ResolveReplayMember M[T];
   bool cols = false, rows = false;
 #pragma unroll
   for (int t = 0; t < T; ++t) {
@@ -83,14 +77,12 @@ __global__ __launch_bounds__(TPB) void batch_resolve_replay_kernel(int n, int m,
     }
 }
 
-// One carried member of a warm start: resolve_point_col / _row's work (resolve_kernels.hpp) -- x_s = x * cum_d,
-// y_s = y * cum_e (in_* == nullptr: zeros), +0.0 in the vectors a fresh handle holds zeros in (zn / zm; nullptr: not
-// allocated), +0.0 in A'y when no y was given.  pack_k >= 0: the scaled y also goes to Y[i * Kp + pack_k], where the
-// batched product A' Y gathers it (batch_spmv_kernel<MODE_PLAIN>, batch_kernels.hpp).
+// One carried member of a warm start (resolve_point_col / _row's P, resolve_kernels.hpp).  pack_k >= 0: the scaled y also
+// goes to Y[i * Kp + pack_k], where the batched product A' Y gathers it (batch_spmv_kernel<MODE_PLAIN>, batch_kernels.hpp).
 struct BatchPointMember {
   const double *in_x, *in_y;
   double *x, *y, *aty;
-  double *zn[5], *zm[3];
+  ResolveZeros z;
   int zero_aty, pack_k;
 };
 
@@ -101,29 +93,15 @@ __global__ __launch_bounds__(TPB) void batch_resolve_point_kernel(int n, int m, 
                                                                   double *__restrict__ Y, int shift) {
   const BatchPointMember a = table[blockIdx.y];
   const int tid = blockIdx.x * TPB + threadIdx.x, st = gridDim.x * TPB;
-  for (int j = tid; j < n; j += st) {
-    double v = 0.0;
-    if (a.in_x) { v = a.in_x[j]; if (cum_d) v = v * cum_d[j]; }
-    a.x[j] = v;
-    if (a.zero_aty) a.aty[j] = 0.0;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) if (a.zn[q]) a.zn[q][j] = 0.0;
-  }
-  for (int i = tid; i < m; i += st) {
-    double v = 0.0;
-    if (a.in_y) { v = a.in_y[i]; if (cum_e) v = v * cum_e[i]; }
-    a.y[i] = v;
-    if (a.pack_k >= 0) Y[((size_t)i << shift) + a.pack_k] = v;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) if (a.zm[q]) a.zm[q][i] = 0.0;
-  }
+  for (int j = tid; j < n; j += st) resolve_point_col(a, cum_d, j);
+  for (int i = tid; i < m; i += st) resolve_point_row(a, cum_e, i, Y, shift, a.pack_k);
 }
 
 // The front of a batch's staging buffers (pinned and device): the table of one call's carried members -- replay or
 // point entries -- and, behind it, where the members' A'y are, by member slot (the batched product's output table).
 constexpr size_t BATCH_RESOLVE_TABLE_BYTES = sizeof(BatchPointMember) * BATCH_MAX;
 constexpr size_t BATCH_RESOLVE_HEAD_BYTES = BATCH_RESOLVE_TABLE_BYTES + sizeof(double *) * BATCH_MAX;
-static_assert(sizeof(BatchReplayMember) <= sizeof(BatchPointMember), "the replay table fits where the point table does");
+static_assert(sizeof(ResolveReplayMember) <= sizeof(BatchPointMember), "the replay table fits where the point table does");
 static_assert(BATCH_RESOLVE_HEAD_BYTES % sizeof(double) == 0, "the vectors behind the head are aligned");
 
 }  // namespace

@@ -27,11 +27,10 @@ struct FleetState {
   int64_t chk_launches = 0, chk_carried = 0, chk_single = 0, chk_misses = 0;
   bool chk_serving = false;                                     // inside a fleet call's own per-member calls
   // re-solves in shared launches (abi_resolve.hpp): one table per call -- the items, then the members' vectors -- in
-  // pinned memory and its device copy; shared launches so far, members carried by / given a product of their own by the
-  // last call, lazy view rebuilds so far
+  // pinned memory and its device copy; what the calls did (`other`: lazy view rebuilds so far)
   void *rsv_dev = nullptr, *rsv_host = nullptr;
   size_t rsv_cap = 0;
-  int64_t rsv_launches = 0, rsv_carried = 0, rsv_single = 0, rsv_view_rebuilds = 0;
+  ResolveCounters rsv;
 };
 
 // ---- what a fleet's check calls leave in a member (pdhg_handle::fc_eval / fc_tr): pdhg_eval_point and
@@ -299,19 +298,4 @@ int fleet_policy_launch(pdhg_handle *f, std::vector<FleetCarry> &carry) {
   for (const FleetCarry &c : carry)
     if ((rc = small_policy_collect(F.mem[(size_t)c.k], c.seq, *c.pio))) return rc;
   return 0;
-}
-
-// ---- re-solves (abi_resolve.hpp): what the rest of the host side needs of them ----
-// a member's views rebuilt where they were next read (bounds_fresh), counted on its fleet
-void resolve_count_view_rebuild(pdhg_handle *h) {
-  if (h->fleet_of && h->fleet_of->fleet) h->fleet_of->fleet->rsv_view_rebuilds += 1;
-}
-// the retained record and the staging buffers of a handle (destroy_shard; the handle's device is current)
-void resolve_release(pdhg_handle *h) {
-  ResolveState *R = h->rs;
-  if (!R) return;
-  for (double *p : {R->rec, R->cum_d, R->cum_e, R->stage_dev}) if (p) (void)hipFree(p);
-  if (R->stage_host) (void)hipHostFree(R->stage_host);
-  delete R;
-  h->rs = nullptr;
 }

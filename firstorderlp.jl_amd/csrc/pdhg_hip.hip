@@ -58,6 +58,14 @@
 #include "batch_resolve_kernels.hpp"
 
 namespace { struct DistGroup; struct FleetState; struct ResolveState; }
+namespace {
+// What the re-solve calls on a fleet or a batch did (host_resolve.hpp; FleetState and BatchState hold one): shared
+// launches so far; members the last update / warm start carried; members the last warm start gave a product of their
+// own; `other`: a fleet's lazy view rebuilds so far, a batch's "the last warm start ran the batched product".
+struct ResolveCounters {
+  int64_t launches = 0, carried = 0, single = 0, other = 0;
+};
+}
 struct BatchState;
 
 struct pdhg_handle {
@@ -285,6 +293,7 @@ struct pdhg_handle {
 namespace {
 
 void destroy_shard(pdhg_handle *h);
+void resolve_release(pdhg_handle *h);      // (host_resolve.hpp)
 
 inline const char *prof_scope_name(int kid) {
   static const char *names[PDHG_K_COUNT] = {"pdhg:primal (K1+K2)", "pdhg:A*xbar + dual step (K3+K4)", "pdhg:A'*y' + interaction sums (K5+K6)",
@@ -577,7 +586,7 @@ int bounds_rebuild(pdhg_handle *h) {
 
 // The views of a handle whose lb / ub a fleet's shared update wrote (bnd_dirty), rebuilt where they are next read: before
 // h->bnd goes into a primal_kernel launch or a graph's primal node, and before it is described.
-void resolve_count_view_rebuild(pdhg_handle *h);
+void resolve_count_view_rebuild(pdhg_handle *h);      // (host_resolve.hpp)
 int bounds_fresh(pdhg_handle *h) {
   if (!h->bnd_dirty) return 0;
   resolve_count_view_rebuild(h);
@@ -814,6 +823,7 @@ int launch_final(pdhg_handle *h, int n_int, int n_dy, int q_count, bool to_host 
 #include "host_fleet.hpp"
 #include "host_trial_graph_build.hpp"
 #include "host_shards.hpp"
+#include "host_resolve.hpp"
 }  // namespace
 
 // ================================================================== C ABI

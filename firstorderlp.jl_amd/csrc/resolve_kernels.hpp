@@ -32,74 +32,89 @@ __global__ __launch_bounds__(TPB) void resolve_record_kernel(int n, int m, const
   }
 }
 
-// What one element of a replay does.  in_* == nullptr: that vector keeps what it holds.
+// One member of a replay.  in_* == nullptr: that vector keeps what it holds -- no load, no store.
+struct ResolveReplayMember {
+  const double *in_c, *in_lb, *in_ub, *in_b;      // create space (device staging)
+  double *c, *lb, *ub, *b;                        // the member's working vectors
+};
 struct ResolveReplayArgs {
   int n, m, steps;
   const double *rec;                              // [steps][n + m]
-  const double *in_c, *in_lb, *in_ub, *in_b;      // create space (device staging)
-  double *c, *lb, *ub, *b;                        // the handle's working vectors
+  ResolveReplayMember v;
 };
 
+// What one element of a replay does.  (The batch's replay, batch_resolve_kernels.hpp, is this arithmetic over a tile of
+// members; the two are not one template: instantiated at a tile of 1 it costs these kernels two more VGPRs than this
+// form does, profiles/resolve_throughput.txt.)
 __device__ __forceinline__ void resolve_replay_col(const ResolveReplayArgs &a, int j) {
   const int64_t stride = (int64_t)a.n + a.m;
-  double vc = a.in_c ? a.in_c[j] : 0.0, vl = a.in_lb ? a.in_lb[j] : 0.0, vu = a.in_ub ? a.in_ub[j] : 0.0;
+  const ResolveReplayMember &v = a.v;
+  double vc = v.in_c ? v.in_c[j] : 0.0, vl = v.in_lb ? v.in_lb[j] : 0.0, vu = v.in_ub ? v.in_ub[j] : 0.0;
   const double *f = a.rec + j;
   for (int s = 0; s < a.steps; ++s, f += stride) {
     const double d = *f;
     vc = vc / d; vu = vu * d; vl = vl * d;
   }
-  if (a.in_c) a.c[j] = vc;
-  if (a.in_lb) a.lb[j] = vl;
-  if (a.in_ub) a.ub[j] = vu;
+  if (v.in_c) v.c[j] = vc;
+  if (v.in_lb) v.lb[j] = vl;
+  if (v.in_ub) v.ub[j] = vu;
 }
 __device__ __forceinline__ void resolve_replay_row(const ResolveReplayArgs &a, int i) {
   const int64_t stride = (int64_t)a.n + a.m;
-  double vb = a.in_b[i];
+  double vb = a.v.in_b[i];
   const double *f = a.rec + a.n + i;
   for (int s = 0; s < a.steps; ++s, f += stride) vb = vb / *f;
-  a.b[i] = vb;
+  a.v.b[i] = vb;
 }
 
 __global__ __launch_bounds__(TPB) void resolve_replay_kernel(ResolveReplayArgs a) {
   const int tid = blockIdx.x * TPB + threadIdx.x, st = gridDim.x * TPB;
-  if (a.in_c || a.in_lb || a.in_ub)
+  if (a.v.in_c || a.v.in_lb || a.v.in_ub)
     for (int j = tid; j < a.n; j += st) resolve_replay_col(a, j);
-  if (a.in_b)
+  if (a.v.in_b)
     for (int i = tid; i < a.m; i += st) resolve_replay_row(a, i);
 }
 
 // A starting point in create space to the working space: x_s = x * cum_d, y_s = y * cum_e (the output divides by these,
 // preprocess.jl); cum_* == nullptr (nothing was rescaled): a copy.  in_x / in_y == nullptr: zeros.  zero_aty: A'y of
 // y = 0 as a fresh handle holds it, +0.0 (the product itself could leave -0.0 in a column of negative entries).
-// zn / zm: the n- / m-vectors a fresh handle holds zeros in (the running sums, their alternates, the restart point, a
-// QP's kept Q x), zeroed in the same pass; nullptr: not allocated yet.
+// ResolveZeros: the n- / m-vectors a fresh handle holds zeros in (resolve_fresh_zeros, host_resolve.hpp, names them),
+// zeroed in the same pass; nullptr: not allocated yet.
+struct ResolveZeros {
+  double *zn[5], *zm[3];
+};
 struct ResolvePointArgs {
   int n, m, zero_aty;
   const double *in_x, *in_y, *cum_d, *cum_e;
   double *x, *y, *aty;
-  double *zn[5], *zm[3];
+  ResolveZeros z;
 };
 
-__device__ __forceinline__ void resolve_point_col(const ResolvePointArgs &a, int j) {
+// What one element of a warm start does; P: ResolvePointArgs, or a batch's BatchPointMember (the running products are the
+// batch's).  pack_k >= 0: the scaled y also goes to Y[(i << shift) + pack_k] (a batch's interleaved Y).
+template <class P>
+__device__ __forceinline__ void resolve_point_col(const P &a, const double *cum_d, int j) {
   double v = 0.0;
-  if (a.in_x) { v = a.in_x[j]; if (a.cum_d) v = v * a.cum_d[j]; }
+  if (a.in_x) { v = a.in_x[j]; if (cum_d) v = v * cum_d[j]; }
   a.x[j] = v;
   if (a.zero_aty) a.aty[j] = 0.0;
 #pragma unroll
-  for (int q = 0; q < 5; ++q) if (a.zn[q]) a.zn[q][j] = 0.0;
+  for (int q = 0; q < 5; ++q) if (a.z.zn[q]) a.z.zn[q][j] = 0.0;
 }
-__device__ __forceinline__ void resolve_point_row(const ResolvePointArgs &a, int i) {
+template <class P>
+__device__ __forceinline__ void resolve_point_row(const P &a, const double *cum_e, int i, double *Y = nullptr, int shift = 0, int pack_k = -1) {
   double v = 0.0;
-  if (a.in_y) { v = a.in_y[i]; if (a.cum_e) v = v * a.cum_e[i]; }
+  if (a.in_y) { v = a.in_y[i]; if (cum_e) v = v * cum_e[i]; }
   a.y[i] = v;
+  if (pack_k >= 0) Y[((size_t)i << shift) + pack_k] = v;
 #pragma unroll
-  for (int q = 0; q < 3; ++q) if (a.zm[q]) a.zm[q][i] = 0.0;
+  for (int q = 0; q < 3; ++q) if (a.z.zm[q]) a.z.zm[q][i] = 0.0;
 }
 
 __global__ __launch_bounds__(TPB) void resolve_point_kernel(ResolvePointArgs a) {
   const int tid = blockIdx.x * TPB + threadIdx.x, st = gridDim.x * TPB;
-  for (int j = tid; j < a.n; j += st) resolve_point_col(a, j);
-  for (int i = tid; i < a.m; i += st) resolve_point_row(a, i);
+  for (int j = tid; j < a.n; j += st) resolve_point_col(a, a.cum_d, j);
+  for (int i = tid; i < a.m; i += st) resolve_point_row(a, a.cum_e, i);
 }
 
 // ---- the fleet forms: one workgroup per (member, chunk) item; elements [lo, hi) of the member's max(n, m) ----
@@ -118,9 +133,9 @@ __global__ __launch_bounds__(TPB) void fleet_resolve_replay_kernel(const FleetRe
   if ((int)blockIdx.x >= count) return;
   const FleetResolveReplayItem it = table[blockIdx.x];
   const ResolveReplayArgs &a = it.a;
-  if (a.in_c || a.in_lb || a.in_ub)
+  if (a.v.in_c || a.v.in_lb || a.v.in_ub)
     for (int j = it.lo + threadIdx.x; j < min(it.hi, a.n); j += TPB) resolve_replay_col(a, j);
-  if (a.in_b)
+  if (a.v.in_b)
     for (int i = it.lo + threadIdx.x; i < min(it.hi, a.m); i += TPB) resolve_replay_row(a, i);
 }
 
@@ -128,17 +143,8 @@ __global__ __launch_bounds__(TPB) void fleet_resolve_point_kernel(const FleetRes
   if ((int)blockIdx.x >= count) return;
   const FleetResolvePointItem it = table[blockIdx.x];
   const ResolvePointArgs &a = it.a;
-  for (int j = it.lo + threadIdx.x; j < min(it.hi, a.n); j += TPB) resolve_point_col(a, j);
-  for (int i = it.lo + threadIdx.x; i < min(it.hi, a.m); i += TPB) resolve_point_row(a, i);
+  for (int j = it.lo + threadIdx.x; j < min(it.hi, a.n); j += TPB) resolve_point_col(a, a.cum_d, j);
+  for (int i = it.lo + threadIdx.x; i < min(it.hi, a.m); i += TPB) resolve_point_row(a, a.cum_e, i);
 }
-
-// ---- what pdhg_resolve_retain hangs on a handle (host side: abi_resolve.hpp) ----
-struct ResolveState {
-  int64_t steps = 0, cap = 0;                      // applied steps in the record / steps it has room for
-  double *rec = nullptr;                           // [cap][n + m], device
-  double *cum_d = nullptr, *cum_e = nullptr;       // the running products (n, m), 1.0 until a step is applied
-  // one upload per call: the given vectors side by side in pinned memory, one copy to the device staging
-  double *stage_host = nullptr, *stage_dev = nullptr;     // 3 n + m doubles each
-};
 
 }  // namespace

@@ -566,7 +566,10 @@ class _MemberEngine(HipPdhgEngine):
 
 class _MemberOwner:
     """What ``HipPdhgBatch`` and ``HipPdhgFleet`` share: the library ``_L``, the owning handle ``_h``, ``members``
-    (``_MemberEngine`` views, freed with the handle) and the marshalling of their ``take_steps_*`` calls."""
+    (``_MemberEngine`` views, freed with the handle), the marshalling of their ``take_steps_*`` calls and the re-solves
+    of all members in one launch each.  For these a subclass names ``_noun`` (what its messages call it),
+    ``_resolve_calls`` (the library's update, warm start and info entry points) and ``_resolve_other`` (the fourth
+    key of ``resolve_info``)."""
 
     def close(self):
         if getattr(self, "_h", None):
@@ -622,3 +625,61 @@ class _MemberOwner:
         _lib.check(call(self._h, n_steps, float(downscaling_factor), float(breaking_factor), float(interpolation_coefficient),
                         _pd(ss), _pd(ratio), _pd(pw), _pi(it), _pd(kkt), err.ctypes.data_as(_int_p), _pi(done)))
         return ss, ratio, it, kkt, err.astype(bool), done
+
+    # ---- re-solves of all members in one launch each (include/pdhg_hip_resolve.h, pdhg_hip_batch_resolve.h) ----
+    def _live(self):
+        if not getattr(self, "_h", None):
+            raise _lib.PdhgHipError(f"the {self._noun} is closed")
+        return self._h
+
+    def _pointer_table(self, name, values, lengths):
+        """An array of K pointers (NULL: the member's entry is None) over ``values`` = None or a list of K vectors /
+        None, ``lengths[k]`` entries for member k; also returns the arrays, which must outlive the call."""
+        if values is None:
+            return None, []
+        values = list(values)
+        K = len(self.members)
+        if len(values) != K:
+            raise ValueError(f"{name} has {len(values)} entries, the {self._noun} has {K} members")
+        keep = []
+        table = (_dp * K)()
+        for k, (v, length) in enumerate(zip(values, lengths)):
+            if v is None:
+                continue
+            v = _d(v)
+            if v.shape != (length,):
+                raise ValueError(f"{name}[{k}] has {v.shape} entries, member {k} needs ({length},)")
+            keep.append(v)
+            table[k] = v.ctypes.data_as(_dp)
+        return table, keep
+
+    def update_problem_vectors(self, objective_vectors=None, right_hand_sides=None, variable_lower_bounds=None,
+                               variable_upper_bounds=None):
+        """New vectors of the members' ORIGINAL problems, all members in ONE launch: each argument is None or a list of
+        K vectors / None (None: keep).  A member's working vectors become, bit for bit, those of a fresh member created
+        from the updated problem and rescaled with the same parameters; a member whose bounds were given rebuilds its
+        compact bound views where they are next read."""
+        h = self._live()
+        ns, ms = [e.n for e in self.members], [e.m for e in self.members]
+        tables = [self._pointer_table(name, v, lens) for name, v, lens in (
+            ("objective_vectors", objective_vectors, ns), ("right_hand_sides", right_hand_sides, ms),
+            ("variable_lower_bounds", variable_lower_bounds, ns), ("variable_upper_bounds", variable_upper_bounds, ns))]
+        _lib.check(self._resolve_calls()[0](h, *[t for t, _ in tables]))
+
+    def warm_start(self, xs=None, ys=None):
+        """Member k starts from (xs[k], ys[k]) in its original problem's space with everything else as on a fresh
+        member, all members in ONE launch.  A member whose two entries are None is left as it is; with one entry given
+        the other means zeros; ``xs`` and ``ys`` both None: every member starts from zeros."""
+        h = self._live()
+        tx = self._pointer_table("xs", xs, [e.n for e in self.members])
+        ty = self._pointer_table("ys", ys, [e.m for e in self.members])
+        _lib.check(self._resolve_calls()[1](h, tx[0], ty[0]))
+
+    def resolve_info(self):
+        """dict(shared_launches, carried, single, <``_resolve_other``>): shared re-solve launches so far; members the
+        last ``update_problem_vectors`` / ``warm_start`` carried; members the last ``warm_start`` gave a product of
+        their own; a fleet's lazy rebuilds of bound views so far, or whether a batch's last ``warm_start`` ran the
+        batched product."""
+        info = np.zeros(4, dtype=np.int64)
+        _lib.check(self._resolve_calls()[2](self._live(), _pi(info)))
+        return dict(zip(["shared_launches", "carried", "single", self._resolve_other], info.tolist()))

@@ -26,7 +26,7 @@ import time as _time
 import numpy as np
 
 from . import _lib
-from .engine import _dp, _int_p, _MemberEngine, _MemberOwner, _d, _i, _pd, _pi
+from .engine import _int_p, _MemberEngine, _MemberOwner, _d, _i, _pd, _pi
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams,
                                           MalitskyPockStepsizeParameters, _check_inputs, _constant_step_estimate,
                                           _device_scaled_problem, _drive_solves, _host_scaled_problem, _initial_point,
@@ -152,56 +152,11 @@ class HipPdhgFleet(_MemberOwner):
         _lib.check(self._L.pdhg_fleet_info(self._h, _pi(info)))
         return dict(zip(["check_launches", "carried", "single", "misses"], info[4:8].tolist()))
 
-    # ---- re-solves in shared launches (include/pdhg_hip_resolve.h) ----
-    def _pointer_table(self, name, values, lengths):
-        """An array of K pointers (NULL: the member's entry is None) over ``values`` = None or a list of K vectors /
-        None; also returns the arrays, which must outlive the call."""
-        if not getattr(self, "_h", None):
-            raise _lib.PdhgHipError("the fleet is closed")
-        if values is None:
-            return None, []
-        values = list(values)
-        if len(values) != self.K:
-            raise ValueError(f"{name} has {len(values)} entries, the fleet has {self.K} members")
-        keep = []
-        table = (_dp * self.K)()
-        for k, (v, length) in enumerate(zip(values, lengths)):
-            if v is None:
-                continue
-            v = _d(v)
-            if v.shape != (length,):
-                raise ValueError(f"{name}[{k}] has {v.shape} entries, member {k} needs ({length},)")
-            keep.append(v)
-            table[k] = v.ctypes.data_as(_dp)
-        return table, keep
+    # ---- re-solves in shared launches (include/pdhg_hip_resolve.h): ``_MemberOwner``'s, over these ----
+    _noun, _resolve_other = "fleet", "view_rebuilds"
 
-    def update_problem_vectors(self, objective_vectors=None, right_hand_sides=None, variable_lower_bounds=None,
-                               variable_upper_bounds=None):
-        """``members[k].update_problem_vectors(...)`` for every k, all in ONE launch: each argument is None or a list
-        of K vectors / None (None: keep).  A member whose bounds were given rebuilds its compact bound views where they
-        are next read."""
-        ns, ms = [e.n for e in self.members], [e.m for e in self.members]
-        tables = [self._pointer_table(name, v, lens) for name, v, lens in (
-            ("objective_vectors", objective_vectors, ns), ("right_hand_sides", right_hand_sides, ms),
-            ("variable_lower_bounds", variable_lower_bounds, ns), ("variable_upper_bounds", variable_upper_bounds, ns))]
-        _lib.check(self._L.pdhg_fleet_update_problem_vectors(self._h, *[t for t, _ in tables]))
-
-    def warm_start(self, xs=None, ys=None):
-        """``members[k].warm_start(xs[k], ys[k])`` for every k in ONE launch.  A member whose two entries are None is
-        left as it is; ``xs`` and ``ys`` both None: every member starts from zeros."""
-        ns, ms = [e.n for e in self.members], [e.m for e in self.members]
-        tx, ty = self._pointer_table("xs", xs, ns), self._pointer_table("ys", ys, ms)
-        _lib.check(self._L.pdhg_fleet_warm_start(self._h, tx[0], ty[0]))
-
-    def resolve_info(self):
-        """dict(shared_launches, carried, single, view_rebuilds): shared re-solve launches so far; members the last
-        ``update_problem_vectors`` / ``warm_start`` carried; members the last ``warm_start`` gave a product of their
-        own; lazy rebuilds of bound views so far."""
-        if not getattr(self, "_h", None):
-            raise _lib.PdhgHipError("the fleet is closed")
-        info = np.zeros(4, dtype=np.int64)
-        _lib.check(self._L.pdhg_fleet_resolve_info(self._h, _pi(info)))
-        return dict(zip(["shared_launches", "carried", "single", "view_rebuilds"], info.tolist()))
+    def _resolve_calls(self):
+        return (self._L.pdhg_fleet_update_problem_vectors, self._L.pdhg_fleet_warm_start, self._L.pdhg_fleet_resolve_info)
 
 
 def _default_fleet_factory(problems):

@@ -134,7 +134,37 @@ class _Member:
         return output
 
 
-class PdhgSession:
+class _Session:
+    """What the three sessions share: ``_held`` -- the member, or the list of members; None once closed -- and ``_owner``,
+    whatever ``close`` has to close (the engine, the fleet, the batch)."""
+
+    _held = _owner = None
+
+    def _live(self):
+        if self._held is None:
+            raise RuntimeError("the session is closed")
+        return self._held
+
+    def close(self):
+        owner, self._owner, self._held = self._owner, None, None
+        if owner is not None and hasattr(owner, "close"):
+            owner.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PdhgSession(_Session):
     """One problem kept on the device across solves.
 
     ``PdhgSession(params, problem, engine_factory=None)`` creates the engine, retains the rescaling steps, rescales and
@@ -147,20 +177,17 @@ class PdhgSession:
         _check_inputs(params, [problem])
         factory = engine_factory or _default_engine_factory
         self.params = params
-        self._member = None
         on_device = _rescales_on_device(factory)
-        engine = None
         try:
             if on_device:
-                engine = factory(problem)
-                self._member = _Member(params, problem, engine, True)
+                self._owner = factory(problem)
+                self._held = _Member(params, problem, self._owner, True)
             else:
                 host_scaled = _host_scaled_problem(params, problem)
-                engine = factory(host_scaled[0].scaled_qp)
-                self._member = _Member(params, problem, engine, False, host_scaled)
+                self._owner = factory(host_scaled[0].scaled_qp)
+                self._held = _Member(params, problem, self._owner, False, host_scaled)
         except Exception:
-            if engine is not None and hasattr(engine, "close"):
-                engine.close()
+            self.close()
             raise
 
     @property
@@ -171,11 +198,6 @@ class PdhgSession:
     @property
     def engine(self):
         return self._live().engine
-
-    def _live(self):
-        if self._member is None:
-            raise RuntimeError("the session is closed")
-        return self._member
 
     def update(self, objective_vector=None, right_hand_side=None, variable_lower_bound=None, variable_upper_bound=None):
         """New vectors of the problem (``None``: keep).  The updated problem is validated before any device work; if
@@ -196,70 +218,20 @@ class PdhgSession:
         mb.engine.warm_start(*mb.engine_point(point))
         return mb.solved(_drive_solve(mb.new_solve()))
 
-    def close(self):
-        mb, self._member = self._member, None
-        if mb is not None and hasattr(mb.engine, "close"):
-            mb.engine.close()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PdhgFleetSession:
-    """Many independent problems kept on the device across solves: ``PdhgSession`` over a fleet
-    (``fleet.optimize_many``).  A fleet with ``update_problem_vectors`` / ``warm_start`` of its own (``HipPdhgFleet``)
-    takes the updates and the warm starts of all members in one launch each; any other fleet member by member."""
-
-    def __init__(self, params, problems, fleet_factory=None):
-        problems = list(problems)
-        if not problems:
-            raise ValueError("a fleet session needs at least one problem")
-        _check_inputs(params, problems)
-        factory = fleet_factory or _default_fleet_factory
-        self.params = params
-        self._fleet = None
-        self._members = None
-        on_device = _rescales_on_device(factory)
-        fleet = None
-        try:
-            if on_device:
-                fleet = factory(problems)
-                self._members = [_Member(params, p, eng, True) for p, eng in zip(problems, fleet.members)]
-            else:
-                host_scaled = [_host_scaled_problem(params, p) for p in problems]
-                fleet = factory([s.scaled_qp for s, _ in host_scaled])
-                self._members = [_Member(params, p, eng, False, hs)
-                                 for p, eng, hs in zip(problems, fleet.members, host_scaled)]
-            self._fleet = fleet
-        except Exception:
-            self._members = None
-            if fleet is not None and hasattr(fleet, "close"):
-                fleet.close()
-            raise
-
-    @property
-    def fleet(self):
-        self._live()
-        return self._fleet
+class _GroupSession(_Session):
+    """A session over a group of problems on one owner (a fleet, a batch): ``update`` and the front half of ``solve``.
+    A subclass opens the group in its ``__init__`` (``_owner``, ``_held``), says in ``_group_takes(call, members)``
+    whether the owner itself takes the members' ``update_problem_vectors`` / ``warm_start`` calls (original-space
+    vectors, one launch each) and drives the started solves in ``_drive(members)``."""
 
     @property
     def problems(self):
         return [mb.problem for mb in self._live()]
 
-    def _live(self):
-        if self._members is None:
-            raise RuntimeError("the session is closed")
-        return self._members
+    def _group(self):
+        self._live()
+        return self._owner
 
     def update(self, updates):
         """``updates``: one entry per problem -- ``None`` (keep the problem) or a dict with any of ``objective_vector``,
@@ -272,8 +244,8 @@ class PdhgFleetSession:
         staged = [None if u is None else mb.staged_update(**u) for mb, u in zip(members, updates)]
         vectors = [None if st is None or not st[1] else mb.engine_vectors(st[1], st[2]) for mb, st in zip(members, staged)]
         if any(v is not None for v in vectors):
-            if hasattr(self._fleet, "update_problem_vectors"):
-                self._fleet.update_problem_vectors(*[[None if v is None else v[k] for v in vectors] for k in _UPDATE_FIELDS])
+            if self._group_takes("update_problem_vectors", members):
+                self._owner.update_problem_vectors(*[[None if v is None else v[k] for v in vectors] for k in _UPDATE_FIELDS])
             else:
                 for mb, v in zip(members, vectors):
                     if v is not None:
@@ -283,9 +255,9 @@ class PdhgFleetSession:
                 mb.committed(st[0], st[2])
 
     def solve(self, warm_start=None):
-        """Solve every problem as updated so far; returns what ``optimize_many`` returns.  ``warm_start``: ``None``
-        (everyone from zeros), ``True`` (everyone from its previous solution) or a list with one entry per problem --
-        ``None`` (zeros) or ``(x0, y0)``."""
+        """Solve every problem as updated so far; returns what the group's one-shot driver (``optimize_many``,
+        ``optimize_batch``) returns.  ``warm_start``: ``None`` (everyone from zeros), ``True`` (everyone from its
+        previous solution) or a list with one entry per problem -- ``None`` (zeros) or ``(x0, y0)``."""
         members = self._live()
         if warm_start is None or warm_start is True:
             warm_start = [warm_start] * len(members)
@@ -293,44 +265,61 @@ class PdhgFleetSession:
         if len(warm_start) != len(members):
             raise ValueError(f"warm_start has {len(warm_start)} entries for {len(members)} problems")
         points = [mb.engine_point(_warm_point(mb.problem, w, mb.last)) for mb, w in zip(members, warm_start)]
-        if hasattr(self._fleet, "warm_start"):
+        if self._group_takes("warm_start", members):
             if all(x is None and y is None for x, y in points):
-                self._fleet.warm_start(None, None)
+                self._owner.warm_start(None, None)
             else:
                 # a member whose two entries are None would be left as it is: zeros are given as zeros
                 xs = [np.zeros(mb.engine.n) if x is None and y is None else x for mb, (x, y) in zip(members, points)]
-                self._fleet.warm_start(xs, [y for _, y in points])
+                self._owner.warm_start(xs, [y for _, y in points])
         else:
             for mb, (x, y) in zip(members, points):
                 mb.engine.warm_start(x, y)
-        fleet, policy = self._fleet, self.params.step_size_policy_params
+        return [mb.solved(out) for mb, out in zip(members, self._drive(members))]
+
+
+class PdhgFleetSession(_GroupSession):
+    """Many independent problems kept on the device across solves: ``PdhgSession`` over a fleet
+    (``fleet.optimize_many``).  A fleet with ``update_problem_vectors`` / ``warm_start`` of its own (``HipPdhgFleet``)
+    takes the updates and the warm starts of all members in one launch each; any other fleet member by member."""
+
+    def __init__(self, params, problems, fleet_factory=None):
+        problems = list(problems)
+        if not problems:
+            raise ValueError("a fleet session needs at least one problem")
+        _check_inputs(params, problems)
+        factory = fleet_factory or _default_fleet_factory
+        self.params = params
+        members = None
+        try:
+            # the members rescale one by one (_Member): each has a matrix of its own
+            if _rescales_on_device(factory):
+                self._owner = factory(problems)
+                members = [_Member(params, p, eng, True) for p, eng in zip(problems, self._owner.members)]
+            else:
+                host_scaled = [_host_scaled_problem(params, p) for p in problems]
+                self._owner = factory([s.scaled_qp for s, _ in host_scaled])
+                members = [_Member(params, p, eng, False, hs) for p, eng, hs in zip(problems, self._owner.members, host_scaled)]
+            self._held = members
+        except Exception:
+            self.close()
+            raise
+
+    fleet = property(_GroupSession._group)
+
+    def _group_takes(self, call, members):
+        return hasattr(self._owner, call)
+
+    def _drive(self, members):
+        fleet, policy = self._owner, self.params.step_size_policy_params
         solves = [mb.new_solve() for mb in members]
         checks = None
         if hasattr(fleet, "eval_points") and hasattr(fleet, "trust_region_bounds"):
             checks = lambda pending: _fleet_checks(fleet, solves, pending)      # noqa: E731
-        outputs = _drive_solves(solves, lambda requests: _step_fleet(fleet, solves, policy, requests), checks)
-        return [mb.solved(out) for mb, out in zip(members, outputs)]
-
-    def close(self):
-        fleet, self._fleet, self._members = self._fleet, None, None
-        if fleet is not None and hasattr(fleet, "close"):
-            fleet.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _drive_solves(solves, lambda requests: _step_fleet(fleet, solves, policy, requests), checks)
 
 
-class PdhgBatchSession:
+class PdhgBatchSession(_GroupSession):
     """Problems that share the constraint matrix (and the objective matrix) kept on the device across solves:
     ``PdhgSession`` over a batch (``batch.optimize_batch``, whose preconditions hold here: 1..32 problems, one matrix,
     the adaptive or the constant policy).  A batch with ``retain_rescaling`` / ``update_problem_vectors`` / ``warm_start``
@@ -346,93 +335,35 @@ class PdhgBatchSession:
             raise ValueError(f"a batch session does not support the step-size policy {type(policy).__name__}")
         factory = batch_factory or _default_batch_factory
         self.params = params
-        self._batch = None
-        self._members = None
         self._estimate = None
-        batch = None
         try:
             if _rescales_on_device(factory):
-                batch = factory(problems)
+                # the batch rescales once, on the shared matrix, and hands (E, D, max_abs) to its members
+                batch = self._owner = factory(problems)
                 if hasattr(batch, "retain_rescaling"):
                     batch.retain_rescaling()
                 E, D = batch.rescale(params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
                 max_abs = batch.members[0].matrix_max_abs()
-                self._members = [_Member(params, p, eng, True, rescaled=(E.copy(), D.copy(), max_abs))
-                                 for p, eng in zip(problems, batch.members)]
+                members = [_Member(params, p, eng, True, rescaled=(E.copy(), D.copy(), max_abs))
+                           for p, eng in zip(problems, batch.members)]
             else:
                 host_scaled = [_host_scaled_problem(params, p) for p in problems]
-                batch = factory([s.scaled_qp for s, _ in host_scaled])
-                self._members = [_Member(params, p, eng, False, (s, host_scaled[0][1]))
-                                 for p, eng, (s, _) in zip(problems, batch.members, host_scaled)]
-            self._batch = batch
+                batch = self._owner = factory([s.scaled_qp for s, _ in host_scaled])
+                members = [_Member(params, p, eng, False, (s, host_scaled[0][1]))
+                           for p, eng, (s, _) in zip(problems, batch.members, host_scaled)]
+            self._held = members
         except Exception:
-            self._members = None
-            if batch is not None and hasattr(batch, "close"):
-                batch.close()
+            self.close()
             raise
 
-    @property
-    def batch(self):
-        self._live()
-        return self._batch
+    batch = property(_GroupSession._group)
 
-    @property
-    def problems(self):
-        return [mb.problem for mb in self._live()]
+    def _group_takes(self, call, members):
+        return all(mb.on_device for mb in members) and hasattr(self._owner, "update_problem_vectors") and \
+            hasattr(self._owner, "warm_start")
 
-    def _live(self):
-        if self._members is None:
-            raise RuntimeError("the session is closed")
-        return self._members
-
-    def _shared(self, members):
-        """Does the batch itself take the updates and the warm starts (original-space vectors, one launch each)?"""
-        return all(mb.on_device for mb in members) and hasattr(self._batch, "update_problem_vectors") and \
-            hasattr(self._batch, "warm_start")
-
-    def update(self, updates):
-        """``updates``: one entry per problem -- ``None`` (keep the problem) or a dict with any of ``objective_vector``,
-        ``right_hand_side``, ``variable_lower_bound``, ``variable_upper_bound``.  Every updated problem is validated
-        before any device work; if one raises, the session is as it was."""
-        members = self._live()
-        updates = list(updates)
-        if len(updates) != len(members):
-            raise ValueError(f"updates has {len(updates)} entries for {len(members)} problems")
-        staged = [None if u is None else mb.staged_update(**u) for mb, u in zip(members, updates)]
-        vectors = [None if st is None or not st[1] else mb.engine_vectors(st[1], st[2]) for mb, st in zip(members, staged)]
-        if any(v is not None for v in vectors):
-            if self._shared(members):
-                self._batch.update_problem_vectors(*[[None if v is None else v[k] for v in vectors] for k in _UPDATE_FIELDS])
-            else:
-                for mb, v in zip(members, vectors):
-                    if v is not None:
-                        mb.engine.update_problem_vectors(**v)
-        for mb, st in zip(members, staged):
-            if st is not None:
-                mb.committed(st[0], st[2])
-
-    def solve(self, warm_start=None):
-        """Solve every problem as updated so far; returns what ``optimize_batch`` returns.  ``warm_start``: ``None``
-        (everyone from zeros), ``True`` (everyone from its previous solution) or a list with one entry per problem --
-        ``None`` (zeros) or ``(x0, y0)``."""
-        members = self._live()
-        if warm_start is None or warm_start is True:
-            warm_start = [warm_start] * len(members)
-        warm_start = list(warm_start)
-        if len(warm_start) != len(members):
-            raise ValueError(f"warm_start has {len(warm_start)} entries for {len(members)} problems")
-        points = [mb.engine_point(_warm_point(mb.problem, w, mb.last)) for mb, w in zip(members, warm_start)]
-        if self._shared(members):
-            if all(x is None and y is None for x, y in points):
-                self._batch.warm_start(None, None)
-            else:
-                # a member whose two entries are None would be left as it is: zeros are given as zeros
-                xs = [np.zeros(mb.engine.n) if x is None and y is None else x for mb, (x, y) in zip(members, points)]
-                self._batch.warm_start(xs, [y for _, y in points])
-        else:
-            for mb, (x, y) in zip(members, points):
-                mb.engine.warm_start(x, y)
-        batch, policy = self._batch, self.params.step_size_policy_params
+    def _drive(self, members):
+        batch, policy = self._owner, self.params.step_size_policy_params
         solves = [_Solve(self.params, mb.problem, mb.scaled_problem, mb.engine, mb.matrix_max_abs) for mb in members]
         if isinstance(policy, ConstantStepsizeParams) and self._estimate is None:
             # the power method sees the matrix only: once per session, on member 0's operators (as optimize_batch runs
@@ -440,23 +371,4 @@ class PdhgBatchSession:
             self._estimate = _constant_step_estimate(solves[0])
         for solve in solves:
             solve.start(self._estimate)
-        outputs = _drive_solves(solves, lambda requests: _step_batch(batch, policy, requests))
-        return [mb.solved(out) for mb, out in zip(members, outputs)]
-
-    def close(self):
-        batch, self._batch, self._members = self._batch, None, None
-        if batch is not None and hasattr(batch, "close"):
-            batch.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _drive_solves(solves, lambda requests: _step_batch(batch, policy, requests))

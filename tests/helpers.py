@@ -1,12 +1,16 @@
 """Shared test helpers: the reference's test LPs
 (test/shared_test_qp_problems.jl) restated as data, and glue between the
 product's problem type and the CPU oracle."""
+import dataclasses
+
 import numpy as np
+import pytest
 import scipy.sparse as sp
 
 from firstorderlp_jl_amd import (QuadraticProgrammingProblem,
                                  linear_programming_problem)
 from oracle.oracle import OracleState
+from tests.oracle_engine import OracleEngine
 
 INF = np.inf
 
@@ -287,3 +291,74 @@ def rows_with_lens(lens, n, seed, num_eq=None):
     lb[fixed] = ub[fixed] = rng.standard_normal(int(fixed.sum()))
     return linear_programming_problem(lb, ub, rng.standard_normal(n), 0.0, A, rng.standard_normal(m),
                                       m // 3 if num_eq is None else int(num_eq))
+
+
+# ---- what the re-solve tests share (test_resolve_host, test_batch_resolve_host, test_gpu_resolve, test_gpu_batch_resolve) ----
+def stats_key(s):
+    d = dataclasses.asdict(s)
+    d.pop("cumulative_time_sec")
+    d["method_specific_stats"] = {k: v for k, v in d["method_specific_stats"].items() if "time" not in k}
+    return repr(d)
+
+
+def assert_same_output(got, want):
+    assert got.termination_reason == want.termination_reason
+    assert got.iteration_count == want.iteration_count
+    assert np.array_equal(got.primal_solution, want.primal_solution, equal_nan=True)
+    assert np.array_equal(got.dual_solution, want.dual_solution, equal_nan=True)
+    assert [stats_key(s) for s in got.iteration_stats] == [stats_key(s) for s in want.iteration_stats]
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def same_bits(got, want, label=""):
+    for name, g, w in zip(("c", "b", "lb", "ub"), got, want):
+        assert np.array_equal(bits(g), bits(w)), f"{label}: {name} differs at {np.nonzero(bits(g) != bits(w))[0][:5]}"
+
+
+def edge_bounds(n, rng):
+    """Bounds that hold -inf, +inf, +0.0, -0.0 and lb == ub."""
+    lb = rng.choice([-np.inf, 0.0, -0.0, -1.5, 0.25], size=n)
+    free = np.isneginf(lb)
+    ub = np.where(free, 0.0, lb) + rng.choice([np.inf, 0.0, 2.0, 0.125], size=n)
+    ub[free] = rng.choice([np.inf, 0.0, -0.0, 3.0], size=int(free.sum()))
+    return lb, ub
+
+
+def raises_naming(exc, words, call):
+    with pytest.raises(exc) as info:
+        call()
+    assert any(w in str(info.value) for w in words), str(info.value)
+
+
+class ResolveOracleEngine(OracleEngine):
+    """``OracleEngine`` with the two calls a session needs, in numpy: the oracle holds the problem's vectors in its own
+    state and has no setter for them, so an update builds a new oracle state over the same matrix; a warm start is a new
+    state too (everything empty) at the given point."""
+
+    def __init__(self, constraint_matrix, objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound,
+                 num_equalities, objective_matrix=None):
+        super().__init__(constraint_matrix, objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound,
+                         num_equalities, objective_matrix)
+        self._vectors = [np.array(v, dtype=np.float64) for v in (objective_vector, right_hand_side, variable_lower_bound,
+                                                                 variable_upper_bound)]
+        self._num_eq, self._Qm = num_equalities, objective_matrix
+
+    def _rebuild(self):
+        self.st.close()
+        OracleEngine.__init__(self, self._A, *self._vectors, self._num_eq, self._Qm)
+
+    def update_problem_vectors(self, objective_vector=None, right_hand_side=None, variable_lower_bound=None,
+                               variable_upper_bound=None):
+        for k, v in enumerate((objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound)):
+            if v is not None:
+                assert np.shape(v) == self._vectors[k].shape
+                self._vectors[k] = np.array(v, dtype=np.float64)
+        self._rebuild()
+
+    def warm_start(self, x=None, y=None):
+        self._rebuild()
+        if x is not None or y is not None:
+            self.set_current(x, y)

@@ -21,6 +21,7 @@ from firstorderlp_jl_amd.quadratic_programming import linear_programming_problem
 from firstorderlp_jl_amd.saddle_point import (RestartScheme, RestartToCurrentMetric,  # noqa: E402
                                               construct_restart_parameters)
 from firstorderlp_jl_amd.termination import construct_termination_criteria  # noqa: E402
+from tests.helpers import ResolveOracleEngine, assert_same_output as _assert_same  # noqa: E402
 from tests.oracle_engine import OracleEngine  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,37 +54,6 @@ def _family():
             _lp([3.0, 1.0, 0.5, -1.0], [2.0, 0.1, 0.7, 3.0, 1.0])]
 
 
-class _ResolveOracleEngine(OracleEngine):
-    """``OracleEngine`` with the two calls a session needs, in numpy: the oracle holds the problem's vectors in its own
-    state, so an update builds a new oracle state over the same matrix; a warm start is a new state (everything empty)
-    at the given point."""
-
-    def __init__(self, constraint_matrix, objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound,
-                 num_equalities, objective_matrix=None):
-        super().__init__(constraint_matrix, objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound,
-                         num_equalities, objective_matrix)
-        self._vectors = [np.array(v, dtype=np.float64) for v in (objective_vector, right_hand_side, variable_lower_bound,
-                                                                 variable_upper_bound)]
-        self._num_eq, self._Qm = num_equalities, objective_matrix
-
-    def _rebuild(self):
-        self.st.close()
-        OracleEngine.__init__(self, self._A, *self._vectors, self._num_eq, self._Qm)
-
-    def update_problem_vectors(self, objective_vector=None, right_hand_side=None, variable_lower_bound=None,
-                               variable_upper_bound=None):
-        for k, v in enumerate((objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound)):
-            if v is not None:
-                assert np.shape(v) == self._vectors[k].shape
-                self._vectors[k] = np.array(v, dtype=np.float64)
-        self._rebuild()
-
-    def warm_start(self, x=None, y=None):
-        self._rebuild()
-        if x is not None or y is not None:
-            self.set_current(x, y)
-
-
 class _OracleBatch:
     """The batch interface of HipPdhgBatch over K oracle engines (trial_step / accept per active member); it has none
     of the batch's own re-solve calls, so a session serves it member by member."""
@@ -111,22 +81,7 @@ class _OracleBatch:
 
 
 class _ResolveOracleBatch(_OracleBatch):
-    engine = _ResolveOracleEngine
-
-
-def _stats_key(s):
-    d = dataclasses.asdict(s)
-    d.pop("cumulative_time_sec")
-    d["method_specific_stats"] = {k: v for k, v in d["method_specific_stats"].items() if "time" not in k}
-    return repr(d)
-
-
-def _assert_same(got, want):
-    assert got.termination_reason == want.termination_reason
-    assert got.iteration_count == want.iteration_count
-    assert np.array_equal(got.primal_solution, want.primal_solution, equal_nan=True)
-    assert np.array_equal(got.dual_solution, want.dual_solution, equal_nan=True)
-    assert [_stats_key(s) for s in got.iteration_stats] == [_stats_key(s) for s in want.iteration_stats]
+    engine = ResolveOracleEngine
 
 
 # ---- the exports ----

@@ -23,6 +23,8 @@ from firstorderlp_jl_amd.saddle_point import (RestartScheme, RestartToCurrentMet
                                               construct_restart_parameters)
 from firstorderlp_jl_amd.termination import construct_termination_criteria
 from tests import helpers as H
+from tests.helpers import (assert_same_output as _assert_same, bits as _bits, edge_bounds as _edge_bounds,
+                           raises_naming as _raises_naming, same_bits as _same_bits)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,43 +42,10 @@ def _params(policy=None, tol=1e-6, limit=64, freq=8, steps=12):
     return PdhgParameters(ruiz, l2, pc, 1.0, True, 0, True, freq, tc, rp, policy or AdaptiveStepsizeParams(0.3, 0.6))
 
 
-def _stats_key(s):
-    d = dataclasses.asdict(s)
-    d.pop("cumulative_time_sec")
-    d["method_specific_stats"] = {k: v for k, v in d["method_specific_stats"].items() if "time" not in k}
-    return repr(d)
-
-
-def _assert_same(got, want):
-    assert got.termination_reason == want.termination_reason
-    assert got.iteration_count == want.iteration_count
-    assert np.array_equal(got.primal_solution, want.primal_solution, equal_nan=True)
-    assert np.array_equal(got.dual_solution, want.dual_solution, equal_nan=True)
-    assert [_stats_key(s) for s in got.iteration_stats] == [_stats_key(s) for s in want.iteration_stats]
-
-
 def _assert_all_same(got, want):
     assert len(got) == len(want)
     for g, w in zip(got, want):
         _assert_same(g, w)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same_bits(got, want, label=""):
-    for name, g, w in zip(("c", "b", "lb", "ub"), got, want):
-        assert np.array_equal(_bits(g), _bits(w)), f"{label}: {name} differs at {np.nonzero(_bits(g) != _bits(w))[0][:5]}"
-
-
-def _edge_bounds(n, rng):
-    """Bounds that hold -inf, +inf, +0.0, -0.0 and lb == ub."""
-    lb = rng.choice([-np.inf, 0.0, -0.0, -1.5, 0.25], size=n)
-    free = np.isneginf(lb)
-    ub = np.where(free, 0.0, lb) + rng.choice([np.inf, 0.0, 2.0, 0.125], size=n)
-    ub[free] = rng.choice([np.inf, 0.0, -0.0, 3.0], size=int(free.sum()))
-    return lb, ub
 
 
 def _edge_vectors(m, n, rng):
@@ -467,12 +436,6 @@ def test_the_bound_views_of_a_member_follow_its_bounds(gpu_required, monkeypatch
 
 
 # ---- refusals launch nothing ----
-
-def _raises_naming(exc, words, call):
-    with pytest.raises(exc) as info:
-        call()
-    assert any(w in str(info.value) for w in words), str(info.value)
-
 
 @pytest.mark.short_rows
 def test_refusals_launch_nothing_and_leave_the_batch_usable(gpu_required):

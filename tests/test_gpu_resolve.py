@@ -24,6 +24,8 @@ from firstorderlp_jl_amd.saddle_point import (RestartScheme, RestartToCurrentMet
 from firstorderlp_jl_amd.solve_log import RestartChoice
 from firstorderlp_jl_amd.termination import construct_termination_criteria
 from tests import helpers as H
+from tests.helpers import (assert_same_output as _assert_same, bits as _bits, edge_bounds as _edge_bounds,
+                           raises_naming as _raises_naming, same_bits as _same_bits)
 from tests.oracle_engine import OracleEngine
 
 pytestmark = pytest.mark.gpu
@@ -40,30 +42,6 @@ def _params(policy=None, tol=1e-6, limit=64, freq=8, steps=12):
     return PdhgParameters(ruiz, l2, pc, 1.0, True, 0, True, freq, tc, rp, policy or AdaptiveStepsizeParams(0.3, 0.6))
 
 
-def _stats_key(s):
-    d = dataclasses.asdict(s)
-    d.pop("cumulative_time_sec")
-    d["method_specific_stats"] = {k: v for k, v in d["method_specific_stats"].items() if "time" not in k}
-    return repr(d)
-
-
-def _assert_same(got, want):
-    assert got.termination_reason == want.termination_reason
-    assert got.iteration_count == want.iteration_count
-    assert np.array_equal(got.primal_solution, want.primal_solution, equal_nan=True)
-    assert np.array_equal(got.dual_solution, want.dual_solution, equal_nan=True)
-    assert [_stats_key(s) for s in got.iteration_stats] == [_stats_key(s) for s in want.iteration_stats]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same_bits(got, want, label=""):
-    for name, g, w in zip(("c", "b", "lb", "ub"), got, want):
-        assert np.array_equal(_bits(g), _bits(w)), f"{label}: {name} differs at {np.nonzero(_bits(g) != _bits(w))[0][:5]}"
-
-
 def _edge_lp(m, n, seed):
     """An m x n LP (m may be 0) with up to three entries per row and bounds that hold -inf, +inf, +0.0, -0.0 and
     lb == ub."""
@@ -74,14 +52,6 @@ def _edge_lp(m, n, seed):
     A = sp.csc_matrix((rng.uniform(0.2, 3.0, m * k) * rng.choice([-1.0, 1.0], m * k), (rows, cols)), shape=(m, n))
     lb, ub = _edge_bounds(n, rng)
     return linear_programming_problem(lb, ub, rng.standard_normal(n), 0.0, A, rng.standard_normal(m), m // 2)
-
-
-def _edge_bounds(n, rng):
-    lb = rng.choice([-np.inf, 0.0, -0.0, -1.5, 0.25], size=n)
-    free = np.isneginf(lb)
-    ub = np.where(free, 0.0, lb) + rng.choice([np.inf, 0.0, 2.0, 0.125], size=n)
-    ub[free] = rng.choice([np.inf, 0.0, -0.0, 3.0], size=int(free.sum()))
-    return lb, ub
 
 
 def _new_vectors(problem, seed):
@@ -503,12 +473,6 @@ def test_fleet_sessions_of_one_and_of_more_members_than_compute_units(gpu_requir
 
 
 # ---- refusals launch nothing ----
-
-def _raises_naming(exc, words, call):
-    with pytest.raises(exc) as info:
-        call()
-    assert any(w in str(info.value) for w in words), str(info.value)
-
 
 def test_refusals_launch_nothing_and_leave_the_handle_usable(gpu_required):
     problem = random_lp(27, 32, 4, seed=1)

@@ -21,6 +21,7 @@ from firstorderlp_jl_amd.saddle_point import (RestartScheme, RestartToCurrentMet
 from firstorderlp_jl_amd.solve_log import TerminationReason  # noqa: E402
 from firstorderlp_jl_amd.termination import construct_termination_criteria  # noqa: E402
 from tests import helpers as H  # noqa: E402
+from tests.helpers import ResolveOracleEngine, assert_same_output as _assert_same  # noqa: E402
 from tests.oracle_engine import OracleEngine  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,37 +34,6 @@ def _params(policy=None, tol=1e-8, limit=2000, freq=5, ruiz=10, pc=1.0):
     return PdhgParameters(ruiz, False, pc, 1.0, True, 0, True, freq, tc, rp, policy or AdaptiveStepsizeParams(0.3, 0.6))
 
 
-class ResolveOracleEngine(OracleEngine):
-    """``OracleEngine`` with the two calls a session needs, in numpy: the oracle holds the problem's vectors in its own
-    state and has no setter for them, so an update builds a new oracle state over the same matrix; a warm start is a new
-    state too (everything empty) at the given point."""
-
-    def __init__(self, constraint_matrix, objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound,
-                 num_equalities, objective_matrix=None):
-        super().__init__(constraint_matrix, objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound,
-                         num_equalities, objective_matrix)
-        self._vectors = [np.array(v, dtype=np.float64) for v in (objective_vector, right_hand_side, variable_lower_bound,
-                                                                 variable_upper_bound)]
-        self._num_eq, self._Qm = num_equalities, objective_matrix
-
-    def _rebuild(self):
-        self.st.close()
-        OracleEngine.__init__(self, self._A, *self._vectors, self._num_eq, self._Qm)
-
-    def update_problem_vectors(self, objective_vector=None, right_hand_side=None, variable_lower_bound=None,
-                               variable_upper_bound=None):
-        for k, v in enumerate((objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound)):
-            if v is not None:
-                assert np.shape(v) == self._vectors[k].shape
-                self._vectors[k] = np.array(v, dtype=np.float64)
-        self._rebuild()
-
-    def warm_start(self, x=None, y=None):
-        self._rebuild()
-        if x is not None or y is not None:
-            self.set_current(x, y)
-
-
 class _ResolveOracleFleet:
     def __init__(self, problems):
         self.members = [ResolveOracleEngine.from_problem(p) for p in problems]
@@ -71,21 +41,6 @@ class _ResolveOracleFleet:
     def close(self):
         for eng in self.members:
             eng.close()
-
-
-def _stats_key(s):
-    d = dataclasses.asdict(s)
-    d.pop("cumulative_time_sec")
-    d["method_specific_stats"] = {k: v for k, v in d["method_specific_stats"].items() if "time" not in k}
-    return repr(d)
-
-
-def _assert_same(got, want):
-    assert got.termination_reason == want.termination_reason
-    assert got.iteration_count == want.iteration_count
-    assert np.array_equal(got.primal_solution, want.primal_solution, equal_nan=True)
-    assert np.array_equal(got.dual_solution, want.dual_solution, equal_nan=True)
-    assert [_stats_key(s) for s in got.iteration_stats] == [_stats_key(s) for s in want.iteration_stats]
 
 
 def _small_problems():
