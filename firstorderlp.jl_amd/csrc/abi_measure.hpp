@@ -338,10 +338,10 @@ static std::string describe_matrix(const pdhg_handle *h, const CsrDev &D0, int m
   char b[512];
   std::string out = "{";
   snprintf(b, sizeof b, "\"rows\": %d, \"cols\": %d, \"nnz\": %lld, \"segments\": %d, \"kernels\": \"%s\"", D0.rows, D0.cols, (long long)D0.nnz,
-           (int)D0.segs.size(), product_kernels(D0, mode, tag).c_str());
+           (int)D0.segs.size(), product_kernels(h, D0, mode, tag).c_str());
   out += b;
-  const char *kind = D.tiled ? "sweep" : ((D.sj.on() || (!D.slabs.empty() && D.slabs.front().sj.on())) ? "sliced jagged"
-                     : ((D.pipe_grid > 0 || (!D.slabs.empty() && D.slabs.front().pipe_grid > 0)) ? "row blocks, pipelined" : "row blocks"));
+  static const char *kinds[] = {"sweep", "sliced jagged", "row blocks, pipelined", "row blocks"};      // (ProductKind's order)
+  const char *kind = kinds[product_kind(D)];
   snprintf(b, sizeof b, ", \"layout\": \"%s\", \"row_blocks\": %d, \"long_rows\": %d, \"long_threshold\": %d, \"column_slabs\": %d, \"max_row_nnz\": %lld",
            kind, D.nblk, D.nlong, D.long_thr, (int)D.slabs.size(), (long long)D0.max_row_nnz);
   out += b;
@@ -357,7 +357,7 @@ static std::string describe_matrix(const pdhg_handle *h, const CsrDev &D0, int m
     }
     out += "]}";
   }
-  const SjDev *J = D.sj.on() ? &D.sj : ((!D.slabs.empty() && D.slabs.front().sj.on()) ? &D.slabs.front().sj : nullptr);
+  const SjDev *J = product_kind(D) != PRODUCT_SJ ? nullptr : (D.slabs.empty() ? &D.sj : &D.slabs.front().sj);
   if (J) {
     int64_t hub = 0, hub_nnz = 0;
     if (D.sj.on()) { hub = D.sj.nhub; hub_nnz = D.sj.hub_nnz; }
@@ -453,8 +453,8 @@ int pdhg_layout_info(pdhg_handle *h, int64_t info[16]) {
   // bit 8 of the slab counts: the product runs on the sliced jagged layout (sj_kernels.hpp)
   for (int k = 0; k < 2; ++k) {
     const CsrDev &D = first(*Ms[k]);
-    if (D.sj.on() || (!D.slabs.empty() && D.slabs.front().sj.on())) info[12 + k] += 256;
-    if (D.pipe_grid > 0 || (!D.slabs.empty() && D.slabs.front().pipe_grid > 0)) info[12 + k] += 512;   // bit 9: spmv_stream_pipe_kernel
+    if (product_kind(D) == PRODUCT_SJ) info[12 + k] += 256;
+    if (product_kind(D) == PRODUCT_PIPE) info[12 + k] += 512;   // bit 9: spmv_stream_pipe_kernel
   }
   return 0;
 }

@@ -1,37 +1,31 @@
 // host_trial_graph.hpp -- part of the single translation unit pdhg_hip.hip (included there, at the place its text used to stand).
-// the trial step as a HIP graph: node construction, parameter updates, launch (host side).
+// the trial step as a HIP graph: the helpers that add a kernel node / give one new parameters, and the pinned result words
+// (host side).  Which nodes a fused product has is not decided here: host_product.hpp states its steps, the sinks in
+// host_trial_graph_build.hpp call these helpers.
 
 // ---- the trial step as a HIP graph ---------------------------------------------------
 
-template <typename... Args>
-hipError_t graph_add_kernel_lds(hipGraph_t g, hipGraphNode_t *node, const std::vector<hipGraphNode_t> &deps,
-                                const void *func, dim3 grid, dim3 block, size_t lds, Args... args) {
-  void *params[] = {(void *)&args...};
+// a kernel node's description; `params` points at the arguments, which outlive the call that consumes it
+inline hipKernelNodeParams kernel_node_params(const void *func, dim3 grid, dim3 block, size_t lds, void **params) {
   hipKernelNodeParams p{};
   p.func = const_cast<void *>(func);
   p.gridDim = grid; p.blockDim = block; p.sharedMemBytes = (unsigned)lds;
   p.kernelParams = params; p.extra = nullptr;
-  return hipGraphAddKernelNode(node, g, deps.empty() ? nullptr : deps.data(), deps.size(), &p);
+  return p;
 }
 template <typename... Args>
 hipError_t graph_add_kernel(hipGraph_t g, hipGraphNode_t *node, const std::vector<hipGraphNode_t> &deps,
                             const void *func, dim3 grid, dim3 block, Args... args) {
-  return graph_add_kernel_lds(g, node, deps, func, grid, block, 0, args...);
-}
-template <typename... Args>
-hipError_t graph_set_kernel_lds(hipGraphExec_t exec, hipGraphNode_t node, const void *func, dim3 grid, dim3 block,
-                                size_t lds, Args... args) {
   void *params[] = {(void *)&args...};
-  hipKernelNodeParams p{};
-  p.func = const_cast<void *>(func);
-  p.gridDim = grid; p.blockDim = block; p.sharedMemBytes = (unsigned)lds;
-  p.kernelParams = params; p.extra = nullptr;
-  return hipGraphExecKernelNodeSetParams(exec, node, &p);
+  const hipKernelNodeParams p = kernel_node_params(func, grid, block, 0, params);
+  return hipGraphAddKernelNode(node, g, deps.empty() ? nullptr : deps.data(), deps.size(), &p);
 }
 template <typename... Args>
 hipError_t graph_set_kernel(hipGraphExec_t exec, hipGraphNode_t node, const void *func, dim3 grid, dim3 block,
                             Args... args) {
-  return graph_set_kernel_lds(exec, node, func, grid, block, 0, args...);
+  void *params[] = {(void *)&args...};
+  const hipKernelNodeParams p = kernel_node_params(func, grid, block, 0, params);
+  return hipGraphExecKernelNodeSetParams(exec, node, &p);
 }
 
 // pinned, host-coherent result words of the one-launch paths (grid_sync.hpp): [0..5) sums, [5] the barriers' error word

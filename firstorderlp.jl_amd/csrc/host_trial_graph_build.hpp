@@ -1,6 +1,7 @@
 // host_trial_graph_build.hpp -- part of the single translation unit pdhg_hip.hip (included there, at the place its text used to stand).
-// The trial step as a HIP graph, second part: eligibility, the nodes of a fused product (stream / sliced jagged / pipelined / slab
-// passes / sweep + the long-row pair), building, parameter updates and launch (host side; the node helpers are in host_trial_graph.hpp).
+// The trial step as a HIP graph, second part: eligibility, the two sinks that turn a fused product's steps (host_product.hpp:
+// which kernels, in which form, with which arguments) into graph nodes and into parameter updates, building and launch (host
+// side; the node helpers are in host_trial_graph.hpp).
 
 bool graph_eligible(pdhg_handle *h) {
   if (h->graph_mode < 0) {
@@ -33,175 +34,66 @@ struct GraphArgs {
   }
 };
 
-// the sweep kernel of a layout for graph nodes: function pointer (with the dynamic-LDS opt-in done)
-template <int MODE>
-int tiled_node_func(pdhg_handle *h, const CsrDev &D, const void **fn, size_t *lds) {
-  *lds = tiled_lds_bytes(D);
-  *fn = D.tw_mode == 1   ? (const void *)spmv_tiled_kernel<MODE, 1>
-        : D.tw_mode == 2 ? (const void *)spmv_tiled_kernel<MODE, 2>
-        : D.tw_mode == 3 ? (const void *)spmv_tiled_kernel<MODE, 3>
-        : D.tw_mode == 4 ? (const void *)spmv_tiled_kernel<MODE, 4>
-                         : (const void *)spmv_tiled_kernel<MODE, 0>;
-  return ensure_lds_limit(h, MODE, D.tw_mode, *lds, *fn);
-}
+// (code placement, third list: see spmv_placement_a in pdhg_hip.hip)
+[[maybe_unused]] const void *const spmv_placement_c[] = {
+    (const void *)spmv_stream_pipe_kernel<1, true, 0>, (const void *)spmv_stream_kernel<1, true, 0>, (const void *)spmv_stream_pipe_kernel<1, false, 0>,
+    (const void *)spmv_stream_kernel<1, false, 0>, (const void *)spmv_long_final_kernel<1>};
 
-// nodes of one fused SpMV: stream kernel (one node) or its column-slab passes (a chain),
-// beside the long-row pair.  `done` receives the nodes the next stage must wait for;
+// A fused product's steps (host_product.hpp) as graph nodes: the chain's passes depend on one another, the long-row pair
+// is a parallel branch off `deps`.
+struct GraphAddSink {
+  static constexpr bool issues = true;
+  hipGraph_t graph;
+  const std::vector<hipGraphNode_t> &deps;
+  hipGraphNode_t chain = nullptr, epi = nullptr, part = nullptr, fin = nullptr;      // the chain's last node so far; the roles' nodes
+  template <class... P>
+  int operator()(StepRole role, const KernelRef<P...> &k, dim3 grid, dim3 block, size_t lds, const step_arg_t<P> &...args) {
+    const bool lng = role == STEP_LONG_PARTIAL || role == STEP_LONG_FINAL;
+    const hipGraphNode_t after = role == STEP_LONG_FINAL ? part : (lng ? nullptr : chain);
+    hipGraphNode_t &nd = role == STEP_LONG_FINAL ? fin : (lng ? part : chain);
+    void *params[] = {const_cast<void *>((const void *)&args)...};
+    const hipKernelNodeParams p = kernel_node_params((const void *)k.fn, grid, block, lds, params);
+    HIP_TRY(hipGraphAddKernelNode(&nd, graph, after ? &after : (deps.empty() ? nullptr : deps.data()), after ? 1 : deps.size(), &p));
+    if (role == STEP_EPILOGUE) epi = nd;
+    return 0;
+  }
+};
+
+// nodes of one fused SpMV.  `done` receives the nodes the next stage must wait for;
 // main_node / long_node (optional) receive the nodes that carry the epilogue's scalars.
 template <int MODE, int TAG>
 int graph_add_spmv(pdhg_handle *h, hipGraph_t graph, const CsrDev &D, const double *xin, const EpiArgs &e,
                    const std::vector<hipGraphNode_t> &deps, std::vector<hipGraphNode_t> &done,
                    hipGraphNode_t *main_node, hipGraphNode_t *long_node) {
-  const int rm = h->remap ? 1 : 0, rx = h->relaxed ? 1 : 0;
-  if (D.tiled) {
-    if (D.grid > 0) {
-      const void *fn;
-      size_t lds;
-      int rc = tiled_node_func<MODE>(h, D, &fn, &lds);
-      if (rc) return rc;
-      hipGraphNode_t nd = nullptr;
-      const int per_xcd = tiled_per_xcd(h, D, D.grid);
-      HIP_TRY(graph_add_kernel_lds(graph, &nd, deps, fn, dim3(per_xcd > 0 ? per_xcd * NUM_XCD : D.grid), dim3(TW_WPB * WAVE), lds,
-                                   (const int2 *)D.wave_rows, (const int *)D.wave_ent, (const int *)D.wave_step_off,
-                                   (const int *)D.step_tile, (const int *)D.wg_step_off, D.nwaves, D.tile_shift, D.tw_rows,
-                                   (const unsigned *)D.pk, (const double *)D.tv, xin, e, D.grid, per_xcd));
-      if (main_node) *main_node = nd;
-      done.push_back(nd);
-    }
-  } else if (!D.slabs.empty()) {
-    const int P = (int)D.slabs.size();
-    std::vector<hipGraphNode_t> prev = deps;
-    for (int p = 0; p < P; ++p) {
-      const SlabDev &S = D.slabs[(size_t)p];
-      hipGraphNode_t nd = nullptr;
-      if (S.sj.on()) {
-        EpiArgs pe{};
-        pe.out = D.slab_partial;
-        pe.init = D.slab_partial;
-        EpiArgs le = e;
-        le.init = D.slab_partial;
-        if (p + 1 < P) {
-          const void *fn = p == 0 ? sj_kernel_fn<MODE_PLAIN, false, TAG>(S.sj) : sj_kernel_fn<MODE_PLAIN, true, TAG>(S.sj);
-          HIP_TRY(graph_add_kernel(graph, &nd, prev, fn, dim3(S.sj.grid), dim3(TPB), sj_view(S.sj, rx), xin, rm, 0, pe));
-        } else {
-          HIP_TRY(graph_add_kernel(graph, &nd, prev, sj_kernel_fn<MODE, true, TAG>(S.sj), dim3(S.sj.grid), dim3(TPB),
-                                   sj_view(S.sj, rx), xin, rm, S.grid, le));
-          if (main_node) *main_node = nd;
-        }
-        prev.assign(1, nd);
-        continue;
-      }
-      if (S.pipe_grid > 0) {
-        EpiArgs pe{};
-        pe.out = D.slab_partial;
-        pe.init = D.slab_partial;
-        EpiArgs le = e;
-        le.init = D.slab_partial;
-        if (p + 1 < P) {
-          const void *fn = p == 0 ? (const void *)spmv_stream_pipe_kernel<MODE_PLAIN, false, TAG> : (const void *)spmv_stream_pipe_kernel<MODE_PLAIN, true, TAG>;
-          HIP_TRY(graph_add_kernel(graph, &nd, prev, fn, dim3(S.pipe_grid), dim3(TPB), S.view(D.rows), xin, (const int4 *)S.ext, S.nblk,
-                                   S.per_xcd, rm, rx, 0, pe));
-        } else {
-          HIP_TRY(graph_add_kernel(graph, &nd, prev, (const void *)spmv_stream_pipe_kernel<MODE, true, TAG>, dim3(S.pipe_grid), dim3(TPB),
-                                   S.view(D.rows), xin, (const int4 *)S.ext, S.nblk, S.per_xcd, rm, rx, S.grid, le));
-          if (main_node) *main_node = nd;
-        }
-        prev.assign(1, nd);
-        continue;
-      }
-      if (p + 1 < P) {
-        EpiArgs pe{};
-        pe.out = D.slab_partial;
-        pe.init = D.slab_partial;
-        const void *fn = p == 0 ? (const void *)spmv_stream_kernel<MODE_PLAIN, false, TAG> : (const void *)spmv_stream_kernel<MODE_PLAIN, true, TAG>;
-        HIP_TRY(graph_add_kernel(graph, &nd, prev, fn, dim3(S.grid), dim3(TPB), S.view(D.rows), xin, (const int2 *)S.blks, (const int4 *)S.ext,
-                                 S.nblk, S.per_xcd, rm, rx | 2, pe));
-      } else {
-        EpiArgs le = e;
-        le.init = D.slab_partial;
-        HIP_TRY(graph_add_kernel(graph, &nd, prev, (const void *)spmv_stream_kernel<MODE, true, TAG>, dim3(S.grid), dim3(TPB),
-                                 S.view(D.rows), xin, (const int2 *)S.blks, (const int4 *)S.ext, S.nblk, S.per_xcd, rm, rx | 2, le));
-        if (main_node) *main_node = nd;
-      }
-      prev.assign(1, nd);
-    }
-    done.push_back(prev[0]);
-  } else if (D.sj.on()) {
-    hipGraphNode_t nd = nullptr;
-    HIP_TRY(graph_add_kernel(graph, &nd, deps, sj_kernel_fn<MODE, false, TAG>(D.sj), dim3(D.sj.grid), dim3(TPB),
-                             sj_view(D.sj, rx), xin, rm, D.grid, e));
-    if (main_node) *main_node = nd;
-    done.push_back(nd);
-  } else if (D.pipe_grid > 0) {
-    hipGraphNode_t nd = nullptr;
-    HIP_TRY(graph_add_kernel(graph, &nd, deps, (const void *)spmv_stream_pipe_kernel<MODE, false, TAG>, dim3(D.pipe_grid), dim3(TPB),
-                             D.view(), xin, (const int4 *)D.ext, D.nblk, D.per_xcd, rm, rx, D.grid, e));
-    if (main_node) *main_node = nd;
-    done.push_back(nd);
-  } else if (D.grid > 0) {
-    hipGraphNode_t nd = nullptr;
-    HIP_TRY(graph_add_kernel(graph, &nd, deps, (const void *)spmv_stream_kernel<MODE, false, TAG>, dim3(D.grid), dim3(TPB),
-                             D.view(), xin, (const int2 *)D.blks, (const int4 *)D.ext, D.nblk, D.per_xcd, rm, rx, e));
-    if (main_node) *main_node = nd;
-    done.push_back(nd);
-  }
-  if (D.nlong > 0) {
-    hipGraphNode_t part = nullptr, fin = nullptr;
-    HIP_TRY(graph_add_kernel(graph, &part, deps, (const void *)spmv_long_partial_kernel<TAG>, dim3(D.nchunks), dim3(TPB),
-                             D.view(), xin, (const int *)D.chunk_row, (const int *)D.chunk_off, D.chunk_partial));
-    HIP_TRY(graph_add_kernel(graph, &fin, {part}, (const void *)spmv_long_final_kernel<MODE>, dim3(D.long_grid), dim3(TPB),
-                             (const int *)D.long_row, (const int *)D.long_chunk_ptr, D.nlong,
-                             (const double *)D.chunk_partial, e, D.grid));
-    if (long_node) *long_node = fin;
-    done.push_back(fin);
-  }
+  GraphAddSink sink{graph, deps};
+  if (int rc = product_steps<MODE, TAG>(h, D, xin, e, sink)) return rc;
+  if (sink.chain) done.push_back(sink.chain);
+  if (sink.fin) done.push_back(sink.fin);
+  if (main_node && sink.epi) *main_node = sink.epi;
+  if (long_node && sink.fin) *long_node = sink.fin;
   return 0;
 }
 
-// the dual stream node's parameters again, with a new sigma
-int graph_set_dual(pdhg_handle *h, pdhg_handle::TrialGraph &G, const EpiArgs &dual_epi) {
-  const CsrDev &A = h->A;
-  const int rm = h->remap ? 1 : 0, rx = h->relaxed ? 1 : 0;
-  if (G.n_dual) {
-    if (A.tiled) {
-      const void *fn;
-      size_t lds;
-      int rc = tiled_node_func<MODE_DUAL>(h, A, &fn, &lds);
-      if (rc) return rc;
-      const int per_xcd = tiled_per_xcd(h, A, A.grid);
-      HIP_TRY(graph_set_kernel_lds(G.exec, G.n_dual, fn, dim3(per_xcd > 0 ? per_xcd * NUM_XCD : A.grid), dim3(TW_WPB * WAVE), lds,
-                                   (const int2 *)A.wave_rows, (const int *)A.wave_ent, (const int *)A.wave_step_off,
-                                   (const int *)A.step_tile, (const int *)A.wg_step_off, A.nwaves, A.tile_shift, A.tw_rows,
-                                   (const unsigned *)A.pk, (const double *)A.tv, (const double *)h->xbar, dual_epi, A.grid, per_xcd));
-    } else if (!A.slabs.empty()) {
-      const SlabDev &S = A.slabs.back();
-      EpiArgs le = dual_epi;
-      le.init = A.slab_partial;
-      if (S.sj.on())
-        HIP_TRY(graph_set_kernel(G.exec, G.n_dual, sj_kernel_fn<MODE_DUAL, true, 0>(S.sj), dim3(S.sj.grid), dim3(TPB),
-                                 sj_view(S.sj, rx), (const double *)h->xbar, rm, S.grid, le));
-      else if (S.pipe_grid > 0)
-        HIP_TRY(graph_set_kernel(G.exec, G.n_dual, (const void *)spmv_stream_pipe_kernel<MODE_DUAL, true, 0>, dim3(S.pipe_grid), dim3(TPB),
-                                 S.view(A.rows), (const double *)h->xbar, (const int4 *)S.ext, S.nblk, S.per_xcd, rm, rx, S.grid, le));
-      else
-        HIP_TRY(graph_set_kernel(G.exec, G.n_dual, (const void *)spmv_stream_kernel<MODE_DUAL, true, 0>, dim3(S.grid), dim3(TPB),
-                                 S.view(A.rows), (const double *)h->xbar, (const int2 *)S.blks, (const int4 *)S.ext, S.nblk, S.per_xcd, rm, rx | 2, le));
-    } else if (A.sj.on()) {
-      HIP_TRY(graph_set_kernel(G.exec, G.n_dual, sj_kernel_fn<MODE_DUAL, false, 0>(A.sj), dim3(A.sj.grid), dim3(TPB),
-                               sj_view(A.sj, rx), (const double *)h->xbar, rm, A.grid, dual_epi));
-    } else if (A.pipe_grid > 0) {
-      HIP_TRY(graph_set_kernel(G.exec, G.n_dual, (const void *)spmv_stream_pipe_kernel<MODE_DUAL, false, 0>, dim3(A.pipe_grid), dim3(TPB),
-                               A.view(), (const double *)h->xbar, (const int4 *)A.ext, A.nblk, A.per_xcd, rm, rx, A.grid, dual_epi));
-    } else {
-      HIP_TRY(graph_set_kernel(G.exec, G.n_dual, (const void *)spmv_stream_kernel<MODE_DUAL, false, 0>, dim3(A.grid), dim3(TPB),
-                               A.view(), (const double *)h->xbar, (const int2 *)A.blks, (const int4 *)A.ext, A.nblk, A.per_xcd, rm, rx, dual_epi));
-    }
+// the same walk again with a new epilogue: only the nodes that carry it get new parameters
+struct GraphSetSink {
+  static constexpr bool issues = true;
+  hipGraphExec_t exec;
+  hipGraphNode_t epi, fin;
+  template <class... P>
+  int operator()(StepRole role, const KernelRef<P...> &k, dim3 grid, dim3 block, size_t lds, const step_arg_t<P> &...args) {
+    const hipGraphNode_t nd = role == STEP_EPILOGUE ? epi : (role == STEP_LONG_FINAL ? fin : nullptr);
+    if (!nd) return 0;
+    void *params[] = {const_cast<void *>((const void *)&args)...};
+    const hipKernelNodeParams p = kernel_node_params((const void *)k.fn, grid, block, lds, params);
+    HIP_TRY(hipGraphExecKernelNodeSetParams(exec, nd, &p));
+    return 0;
   }
-  if (G.n_dual_long)
-    HIP_TRY(graph_set_kernel(G.exec, G.n_dual_long, (const void *)spmv_long_final_kernel<MODE_DUAL>,
-                             dim3(A.long_grid), dim3(TPB), (const int *)A.long_row, (const int *)A.long_chunk_ptr,
-                             A.nlong, (const double *)A.chunk_partial, dual_epi, A.grid));
-  return 0;
+};
+
+// the dual product's nodes again, with a new sigma
+int graph_set_dual(pdhg_handle *h, pdhg_handle::TrialGraph &G, const EpiArgs &dual_epi) {
+  GraphSetSink sink{G.exec, G.n_dual, G.n_dual_long};
+  return product_steps<MODE_DUAL, 0>(h, h->A, h->xbar, dual_epi, sink);
 }
 
 int graph_build(pdhg_handle *h, pdhg_handle::TrialGraph &G, double tau, double theta, double sigma) {

@@ -323,7 +323,7 @@ struct ProfScope {
 // The opt-in for > 64 KiB of dynamic LDS is per device and per kernel instance,
 // and must only ever grow: another handle on the same device may need more than
 // this one (hipFuncSetAttribute sets the limit, it does not raise it).
-int ensure_lds_limit(pdhg_handle *h, int mode, int chunk_mode, size_t lds, const void *func) {
+int ensure_lds_limit(const pdhg_handle *h, int mode, int chunk_mode, size_t lds, const void *func) {
   static size_t limit[64][3][5] = {};
   static std::mutex mu;            // handles may be created / driven from several host threads (shard pool, Julia tasks)
   std::lock_guard<std::mutex> lock(mu);
@@ -356,30 +356,30 @@ int tiled_per_xcd(const pdhg_handle *h, const CsrDev &D, int ngroups) {
   return (h->remap && on && ngroups >= 2 * NUM_XCD) ? (ngroups + NUM_XCD - 1) / NUM_XCD : 0;
 }
 
-// the tiled kernel's five chunk variants behind one call
+// Code placement.  The code object holds the kernels in the order in which this file first names their instances, and the
+// sweep is sensitive to where it lies (NOTEBOOK, "tried and rejected": 11 % once; with the instances named from inside
+// product_steps alone, 1M x 1M launch by launch ran 0.23 % slower, every kernel's ISA unchanged).  The three lists
+// spmv_placement_a / _b / _c name the spmv_* instances where launch_spmv_plain_part, launch_dual and graph_set_dual first
+// named them before host_product.hpp existed, so the order is that one.  They launch nothing and decide nothing: an
+// instance missing here is still built, and simply lies where product_steps names it.
+[[maybe_unused]] const void *const spmv_placement_a[] = {
+    (const void *)spmv_long_partial_kernel<1>, (const void *)spmv_long_final_kernel<0>, (const void *)spmv_tiled_kernel<0, 1>,
+    (const void *)spmv_tiled_kernel<0, 2>, (const void *)spmv_tiled_kernel<0, 3>, (const void *)spmv_tiled_kernel<0, 4>,
+    (const void *)spmv_tiled_kernel<0, 0>, (const void *)spmv_sj_kernel<0, false, 2, SJ_WIDE_G>, (const void *)spmv_sj_kernel<0, false, 2, 1>,
+    (const void *)spmv_sj_kernel<0, true, 2, SJ_WIDE_G>, (const void *)spmv_sj_kernel<0, true, 2, 1>, (const void *)spmv_stream_pipe_kernel<0, false, 2>,
+    (const void *)spmv_stream_pipe_kernel<0, true, 2>, (const void *)spmv_stream_kernel<0, false, 2>, (const void *)spmv_stream_kernel<0, true, 2>,
+    (const void *)spmv_long_partial_kernel<2>};
+
+#include "host_product.hpp"
+
+// the sweep's workgroups [g0, g1) alone (the caller checks hipGetLastError: tune_tiled_variant times these)
 template <int MODE>
 int launch_tiled(pdhg_handle *h, const CsrDev &D, const double *xin, const EpiArgs &e, int g0, int g1) {
-  const size_t lds = tiled_lds_bytes(D);
-  const int w0 = g0 * TW_WPB;
-  const int per_xcd = tiled_per_xcd(h, D, g1 - g0);
-  const int grid = per_xcd > 0 ? per_xcd * NUM_XCD : g1 - g0;
-  int rc;
-#define PDHG_TILED(CH)                                                                                              \
-  do {                                                                                                             \
-    if ((rc = ensure_lds_limit(h, MODE, CH, lds, (const void *)spmv_tiled_kernel<MODE, CH>))) return rc;           \
-    hipLaunchKernelGGL((spmv_tiled_kernel<MODE, CH>), dim3(grid), dim3(TW_WPB * WAVE), lds, h->stream,             \
-                       D.wave_rows + w0, D.wave_ent, D.wave_step_off + w0, D.step_tile, D.wg_step_off + g0,        \
-                       D.nwaves - w0, D.tile_shift, D.tw_rows, D.pk, D.tv, xin, e, g1 - g0, per_xcd);              \
-  } while (0)
-  if (D.tw_mode == 1) PDHG_TILED(1);
-  else if (D.tw_mode == 2) PDHG_TILED(2);
-  else if (D.tw_mode == 3) PDHG_TILED(3);
-  else if (D.tw_mode == 4) PDHG_TILED(4);
-  else PDHG_TILED(0);
-#undef PDHG_TILED
-  return 0;
+  LaunchSink sink{h->stream};
+  return sweep_step<MODE>(h, D, xin, e, g0, g1, sink);
 }
 
+// One fused product as direct launches on h->stream (the steps: host_product.hpp).
 // TAG: 0 the constraint matrix, 1 its transpose, 2 the objective matrix (profiler names)
 // init != nullptr: the row sums start from init[row] -- a later COLUMN-CHUNK pass of a shard group's A_p xbar (the chunks of
 // xbar arrive one after the other, dist.hpp: every chunk's product runs while the next chunk is still on the links).  For
@@ -407,89 +407,8 @@ int launch_spmv(pdhg_handle *h, const CsrDev &D, const double *xin, EpiArgs e, c
     }
     return 0;
   }
-  const int rx = h->relaxed ? 1 : 0;
-  if (D.tiled) {
-    if (D.grid > 0) {
-      int rc = launch_tiled<MODE>(h, D, xin, e, 0, D.grid);
-      if (rc) return rc;
-    }
-  } else if (!D.slabs.empty()) {
-    // column-slab passes, ascending: partial row sums travel through slab_partial
-    const int P = (int)D.slabs.size(), rm = h->remap ? 1 : 0;
-    for (int p = 0; p < P; ++p) {
-      const SlabDev &S = D.slabs[(size_t)p];
-      if (S.sj.on()) {        // the slab in the sliced jagged layout (sj_kernels.hpp)
-        EpiArgs pe{};
-        pe.out = D.slab_partial;
-        pe.init = D.slab_partial;
-        EpiArgs le = e;
-        le.init = D.slab_partial;
-        if (p + 1 < P && p == 0)
-          launch_sj<MODE_PLAIN, false, TAG>(h->stream, S.sj, xin, rm, rx, 0, pe);
-        else if (p + 1 < P)
-          launch_sj<MODE_PLAIN, true, TAG>(h->stream, S.sj, xin, rm, rx, 0, pe);
-        else
-          launch_sj<MODE, true, TAG>(h->stream, S.sj, xin, rm, rx, S.grid, le);
-        continue;
-      }
-      if (S.pipe_grid > 0) {  // the slab's row blocks as a persistent pipelined launch (spmv_stream_pipe_kernel)
-        EpiArgs pe{};
-        pe.out = D.slab_partial;
-        pe.init = D.slab_partial;
-        EpiArgs le = e;
-        le.init = D.slab_partial;
-        if (p + 1 < P && p == 0)
-          hipLaunchKernelGGL((spmv_stream_pipe_kernel<MODE_PLAIN, false, TAG>), dim3(S.pipe_grid), dim3(TPB), 0, h->stream, S.view(D.rows), xin,
-                             (const int4 *)S.ext, S.nblk, S.per_xcd, rm, rx, 0, pe);
-        else if (p + 1 < P)
-          hipLaunchKernelGGL((spmv_stream_pipe_kernel<MODE_PLAIN, true, TAG>), dim3(S.pipe_grid), dim3(TPB), 0, h->stream, S.view(D.rows), xin,
-                             (const int4 *)S.ext, S.nblk, S.per_xcd, rm, rx, 0, pe);
-        else
-          hipLaunchKernelGGL((spmv_stream_pipe_kernel<MODE, true, TAG>), dim3(S.pipe_grid), dim3(TPB), 0, h->stream, S.view(D.rows), xin,
-                             (const int4 *)S.ext, S.nblk, S.per_xcd, rm, rx, S.grid, le);
-        continue;
-      }
-      if (p + 1 < P) {
-        EpiArgs pe{};
-        pe.out = D.slab_partial;
-        pe.init = D.slab_partial;
-        if (p == 0)
-          hipLaunchKernelGGL((spmv_stream_kernel<MODE_PLAIN, false, TAG>), dim3(S.grid), dim3(TPB), 0, h->stream,
-                             S.view(D.rows), xin, S.blks, (const int4 *)S.ext, S.nblk, S.per_xcd, rm, rx | 2, pe);
-        else
-          hipLaunchKernelGGL((spmv_stream_kernel<MODE_PLAIN, true, TAG>), dim3(S.grid), dim3(TPB), 0, h->stream,
-                             S.view(D.rows), xin, S.blks, (const int4 *)S.ext, S.nblk, S.per_xcd, rm, rx | 2, pe);
-      } else {
-        EpiArgs le = e;
-        le.init = D.slab_partial;
-        hipLaunchKernelGGL((spmv_stream_kernel<MODE, true, TAG>), dim3(S.grid), dim3(TPB), 0, h->stream,
-                           S.view(D.rows), xin, S.blks, (const int4 *)S.ext, S.nblk, S.per_xcd, rm, rx | 2, le);
-      }
-    }
-  } else if (D.sj.on()) {
-    if (init) launch_sj<MODE, true, TAG>(h->stream, D.sj, xin, h->remap ? 1 : 0, rx, D.grid, e);
-    else launch_sj<MODE, false, TAG>(h->stream, D.sj, xin, h->remap ? 1 : 0, rx, D.grid, e);
-  } else if (D.pipe_grid > 0) {
-    if (init)
-      hipLaunchKernelGGL((spmv_stream_pipe_kernel<MODE, true, TAG>), dim3(D.pipe_grid), dim3(TPB), 0, h->stream, D.view(), xin,
-                         (const int4 *)D.ext, D.nblk, D.per_xcd, h->remap ? 1 : 0, rx, D.grid, e);
-    else
-      hipLaunchKernelGGL((spmv_stream_pipe_kernel<MODE, false, TAG>), dim3(D.pipe_grid), dim3(TPB), 0, h->stream, D.view(), xin,
-                         (const int4 *)D.ext, D.nblk, D.per_xcd, h->remap ? 1 : 0, rx, D.grid, e);
-  } else if (D.grid > 0) {
-    if (init)
-      hipLaunchKernelGGL((spmv_stream_kernel<MODE, true, TAG>), dim3(D.grid), dim3(TPB), 0, h->stream,
-                         D.view(), xin, D.blks, (const int4 *)D.ext, D.nblk, D.per_xcd, h->remap ? 1 : 0, rx, e);
-    else
-      hipLaunchKernelGGL((spmv_stream_kernel<MODE, false, TAG>), dim3(D.grid), dim3(TPB), 0, h->stream,
-                         D.view(), xin, D.blks, (const int4 *)D.ext, D.nblk, D.per_xcd, h->remap ? 1 : 0, rx, e);
-  }
-  if (D.nlong > 0) {
-    hipLaunchKernelGGL(spmv_long_partial_kernel<TAG>, dim3(D.nchunks), dim3(TPB), 0, h->stream,
-                       D.view(), xin, D.chunk_row, D.chunk_off, D.chunk_partial);
-    hipLaunchKernelGGL(spmv_long_final_kernel<MODE>, dim3(D.long_grid), dim3(TPB), 0, h->stream,
-                       D.long_row, D.long_chunk_ptr, D.nlong, D.chunk_partial, e, D.grid);
-  }
+  LaunchSink sink{h->stream};
+  if (int rc = product_steps<MODE, TAG>(h, D, xin, e, sink)) return rc;
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -503,16 +422,10 @@ int launch_spmv_plain_part(pdhg_handle *h, const CsrDev &D, const double *xin, d
   if (!D.tiled) return fail(-1, "partial launch needs the tiled layout");
   EpiArgs e{};
   e.out = out;
-  if (with_long && D.nlong > 0) {
-    hipLaunchKernelGGL(spmv_long_partial_kernel<1>, dim3(D.nchunks), dim3(TPB), 0, h->stream,
-                       D.view(), xin, D.chunk_row, D.chunk_off, D.chunk_partial);
-    hipLaunchKernelGGL(spmv_long_final_kernel<MODE_PLAIN>, dim3(D.long_grid), dim3(TPB), 0, h->stream,
-                       D.long_row, D.long_chunk_ptr, D.nlong, D.chunk_partial, e, D.grid);
-  }
-  if (g1 > g0) {
-    int rc = launch_tiled<MODE_PLAIN>(h, D, xin, e, g0, g1);
-    if (rc) return rc;
-  }
+  LaunchSink sink{h->stream};
+  int rc = with_long ? long_steps<MODE_PLAIN, 1>(D, xin, e, sink) : 0;
+  if (!rc && g1 > g0) rc = sweep_step<MODE_PLAIN>(h, D, xin, e, g0, g1, sink);
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -719,6 +632,23 @@ FinalSpec trial_final_spec(const pdhg_handle *h, int n_int, int n_dy, int q_coun
   return sp;
 }
 
+// (code placement, second list: see spmv_placement_a)
+[[maybe_unused]] const void *const spmv_placement_b[] = {
+    (const void *)spmv_tiled_kernel<1, 1>, (const void *)spmv_tiled_kernel<1, 2>, (const void *)spmv_tiled_kernel<1, 3>,
+    (const void *)spmv_tiled_kernel<1, 4>, (const void *)spmv_tiled_kernel<1, 0>, (const void *)spmv_sj_kernel<0, false, 0, SJ_WIDE_G>,
+    (const void *)spmv_sj_kernel<0, false, 0, 1>, (const void *)spmv_sj_kernel<0, true, 0, SJ_WIDE_G>, (const void *)spmv_sj_kernel<0, true, 0, 1>,
+    (const void *)spmv_sj_kernel<1, true, 0, SJ_WIDE_G>, (const void *)spmv_sj_kernel<1, true, 0, 1>, (const void *)spmv_stream_pipe_kernel<0, false, 0>,
+    (const void *)spmv_stream_pipe_kernel<0, true, 0>, (const void *)spmv_stream_kernel<0, false, 0>, (const void *)spmv_stream_kernel<0, true, 0>,
+    (const void *)spmv_sj_kernel<1, false, 0, SJ_WIDE_G>, (const void *)spmv_sj_kernel<1, false, 0, 1>, (const void *)spmv_long_partial_kernel<0>,
+    (const void *)spmv_tiled_kernel<2, 1>, (const void *)spmv_tiled_kernel<2, 2>, (const void *)spmv_tiled_kernel<2, 3>,
+    (const void *)spmv_tiled_kernel<2, 4>, (const void *)spmv_tiled_kernel<2, 0>, (const void *)spmv_sj_kernel<0, false, 1, SJ_WIDE_G>,
+    (const void *)spmv_sj_kernel<0, false, 1, 1>, (const void *)spmv_sj_kernel<0, true, 1, SJ_WIDE_G>, (const void *)spmv_sj_kernel<0, true, 1, 1>,
+    (const void *)spmv_sj_kernel<2, true, 1, SJ_WIDE_G>, (const void *)spmv_sj_kernel<2, true, 1, 1>, (const void *)spmv_stream_pipe_kernel<0, false, 1>,
+    (const void *)spmv_stream_pipe_kernel<0, true, 1>, (const void *)spmv_stream_pipe_kernel<2, true, 1>, (const void *)spmv_stream_kernel<0, false, 1>,
+    (const void *)spmv_stream_kernel<0, true, 1>, (const void *)spmv_stream_kernel<2, true, 1>, (const void *)spmv_sj_kernel<2, false, 1, SJ_WIDE_G>,
+    (const void *)spmv_sj_kernel<2, false, 1, 1>, (const void *)spmv_stream_pipe_kernel<2, false, 1>, (const void *)spmv_stream_kernel<2, false, 1>,
+    (const void *)spmv_long_final_kernel<2>};
+
 // stage (pend_y is set; the launch_primal before it staged too): sum_y is read, sum_y_alt written with the pending term
 // and y' * stage_w, pend_y stays, and the staging is live once the launch is queued.
 int launch_dual(pdhg_handle *h, double sigma, bool stage = false, double stage_w = 0.0) {
@@ -833,39 +763,6 @@ extern "C" {
 const char *pdhg_last_error(void) { return g_last_error.c_str(); }
 int pdhg_abi_version(void) { return 11; }
 
-// The kernels behind one fused product, as rocprofv3 prints them (template arguments <MODE,
-// INIT, TAG> / <MODE, CH> / <TAG>; MODE 0 plain, 1 dual epilogue, 2 A'y epilogue; TAG 0 = A,
-// 1 = A'), joined by " + ": a profile of the separate launches adds up to the product by
-// summing these names (tools/rocprof_summary.py does).
-static std::string product_kernels(const CsrDev &D, int mode, int tag) {
-  if (!D.segs.empty())
-    return product_kernels(D.segs.front(), mode, tag) + " (x " + std::to_string(D.segs.size()) + " row segments)";
-  std::string out;
-  auto add = [&](const std::string &k) { out += (out.empty() ? "" : " + ") + k; };
-  const std::string m = std::to_string(mode), t = std::to_string(tag);
-  if (D.tiled) {
-    if (D.grid > 0) add("spmv_tiled_kernel<" + m + ", " + std::to_string(D.tw_mode) + ">");
-  } else if (!D.slabs.empty()) {
-    const SjDev &J = D.slabs.front().sj;
-    const std::string k = J.on() ? "spmv_sj_kernel<" : (D.slabs.front().pipe_grid > 0 ? "spmv_stream_pipe_kernel<" : "spmv_stream_kernel<");
-    const std::string g = J.on() ? ", " + std::to_string(J.G) + ">" : ">";      // the sliced jagged kernel's fourth argument: its form (sj_kernels.hpp)
-    add(k + "0, false, " + t + g);
-    if (D.slabs.size() > 2) add(k + "0, true, " + t + g);
-    add(k + m + ", true, " + t + g);
-  } else if (D.sj.on()) {
-    add("spmv_sj_kernel<" + m + ", false, " + t + ", " + std::to_string(D.sj.G) + ">");
-  } else if (D.pipe_grid > 0) {
-    add("spmv_stream_pipe_kernel<" + m + ", false, " + t + ">");
-  } else if (D.grid > 0) {
-    add("spmv_stream_kernel<" + m + ", false, " + t + ">");
-  }
-  if (D.nlong > 0) {
-    add("spmv_long_partial_kernel<" + t + ">");
-    add("spmv_long_final_kernel<" + m + ">");
-  }
-  return out.empty() ? "(no kernel: empty matrix)" : out;
-}
-
 const char *pdhg_kernel_name(pdhg_handle *h, int kernel_id) {
   static thread_local std::string buf;
   const bool fused = !(h && h->grp);
@@ -876,15 +773,15 @@ const char *pdhg_kernel_name(pdhg_handle *h, int kernel_id) {
       if (h->grp && h->grp->ag_chunks > 1 && !h->has_q && !h->Achunk.empty()) {
         // a shard group with the all-gather in column chunks: one carried pass per chunk (the stream kernels' later passes
         // are their INIT instances, <.., true, ..>: a label for people, not for tools/rocprof_summary.py)
-        buf = std::to_string(h->Achunk.size()) + " column-chunk passes with carried row sums: " + product_kernels(h->Achunk.front(), MODE_PLAIN, 0) +
-              " ... " + product_kernels(h->Achunk.back(), MODE_DUAL, 0);
+        buf = std::to_string(h->Achunk.size()) + " column-chunk passes with carried row sums: " + product_kernels(h, h->Achunk.front(), MODE_PLAIN, 0) +
+              " ... " + product_kernels(h, h->Achunk.back(), MODE_DUAL, 0);
         return buf.c_str();
       }
-      buf = product_kernels(h->A, MODE_DUAL, 0);
+      buf = product_kernels(h, h->A, MODE_DUAL, 0);
       return buf.c_str();
     case PDHG_K_SPMV_ATY:
       if (!h) return "spmv_stream_kernel<2, false, 1>";
-      buf = product_kernels(h->At, fused ? MODE_ATY : MODE_PLAIN, 1);
+      buf = product_kernels(h, h->At, fused ? MODE_ATY : MODE_PLAIN, 1);
       return buf.c_str();
     case PDHG_K_FINAL: return "final_reduce_kernel";
     case PDHG_K_ACCEPT: return "accept_kernel";

@@ -352,17 +352,6 @@ __global__ __launch_bounds__(TPB) void spmv_sj_kernel(SjView J, const double *__
   }
 }
 
-// the form a copy was built in picks the kernel instance
-template <int MODE, bool INIT, int TAG>
-inline const void *sj_kernel_fn(const SjDev &J) {
-  return J.G > 1 ? (const void *)spmv_sj_kernel<MODE, INIT, TAG, SJ_WIDE_G> : (const void *)spmv_sj_kernel<MODE, INIT, TAG, 1>;
-}
-template <int MODE, bool INIT, int TAG>
-inline void launch_sj(hipStream_t stream, const SjDev &J, const double *xin, int remap, int relaxed, int stream_slots, const EpiArgs &e) {
-  if (J.G > 1)
-    hipLaunchKernelGGL((spmv_sj_kernel<MODE, INIT, TAG, SJ_WIDE_G>), dim3(J.grid), dim3(TPB), 0, stream, sj_view(J, relaxed), xin, remap, stream_slots, e);
-  else
-    hipLaunchKernelGGL((spmv_sj_kernel<MODE, INIT, TAG, 1>), dim3(J.grid), dim3(TPB), 0, stream, sj_view(J, relaxed), xin, remap, stream_slots, e);
-}
+// (the form a copy was built in, SjDev::G, picks the kernel instance: pass_step, host_product.hpp)
 
 }  // namespace

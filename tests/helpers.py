@@ -127,6 +127,20 @@ def skewed_lp(m, n, seed, dense_rows=1, dense_cols=1, base_nnz=4):
     return linear_programming_problem(lb, ub, c, 0.0, A, b, num_eq)
 
 
+def with_dense_rows_and_columns(m, n, k, seed):
+    """random_lp plus two dense rows and two dense columns (long rows in both layouts)."""
+    from firstorderlp_jl_amd import linear_programming_problem
+    from firstorderlp_jl_amd.generators import random_lp
+    p = random_lp(m, n, k, seed)
+    rng = np.random.default_rng(seed + 1)
+    A = p.constraint_matrix.tocsr()
+    A = sp.vstack([sp.csr_matrix(rng.standard_normal((2, n))), A[2:]]).tocsc()
+    A = sp.hstack([sp.csc_matrix(rng.standard_normal((m, 2))), A[:, 2:]]).tocsc()
+    A.sort_indices()
+    return linear_programming_problem(p.variable_lower_bound, p.variable_upper_bound, p.objective_vector, 0.0,
+                                      A, p.right_hand_side, p.num_equalities)
+
+
 def bitexact_row_limit():
     """Rows of at most this many entries are bit-identical to the oracle's sequential sums in the row order the test runs
     in (conftest.row_order_mode sets PDHG_ROW_ORDER): 2048 (BLOCK_NNZ) in strict order, 256 (RELAXED_MIN_ROW) in the

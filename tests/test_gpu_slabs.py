@@ -17,20 +17,6 @@ from tests import helpers as H
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(300)]
 
 
-def _with_dense_rows_and_columns(m, n, k, seed):
-    """random_lp plus two dense rows and two dense columns (long rows in both layouts)."""
-    import scipy.sparse as sp
-    from firstorderlp_jl_amd import linear_programming_problem
-    p = random_lp(m, n, k, seed)
-    rng = np.random.default_rng(seed + 1)
-    A = p.constraint_matrix.tocsr()
-    A = sp.vstack([sp.csr_matrix(rng.standard_normal((2, n))), A[2:]]).tocsc()
-    A = sp.hstack([sp.csc_matrix(rng.standard_normal((m, 2))), A[:, 2:]]).tocsc()
-    A.sort_indices()
-    return linear_programming_problem(p.variable_lower_bound, p.variable_upper_bound, p.objective_vector, 0.0,
-                                      A, p.right_hand_side, p.num_equalities)
-
-
 def _engine(p, monkeypatch, slab_mb, graph="1"):
     monkeypatch.setenv("PDHG_SPMV", "stream")
     monkeypatch.setenv("PDHG_GRAPH", graph)
@@ -44,7 +30,7 @@ def _engine(p, monkeypatch, slab_mb, graph="1"):
 
 @pytest.mark.parametrize("maker,slab_mb", [(lambda: random_lp(200_000, 150_000, 8, seed=3), 0.5),
                                            (lambda: pagerank_lp(120_000, seed=4), 0.3),
-                                           (lambda: _with_dense_rows_and_columns(150_000, 140_000, 6, seed=7), 0.4)],
+                                           (lambda: H.with_dense_rows_and_columns(150_000, 140_000, 6, seed=7), 0.4)],
                          ids=["random", "pagerank", "skewed_long_rows"])
 def test_slab_passes_are_bit_identical(gpu_required, monkeypatch, maker, slab_mb):
     p = maker()
