@@ -56,6 +56,11 @@ BATCH_RESOLVE_EXPORTS = [
     "pdhg_batch_resolve_retain", "pdhg_batch_update_problem_vectors", "pdhg_batch_warm_start", "pdhg_batch_resolve_info",
 ]
 
+# every symbol include/pdhg_hip_matrix_update.h declares: new matrix values on a kept sparsity pattern
+MATRIX_UPDATE_EXPORTS = [
+    "pdhg_update_matrix_values",
+]
+
 ABI_VERSION = 11
 UNIQUE_ID_BYTES = 128
 (K_PRIMAL, K_SPMV_DUAL, K_SPMV_ATY, K_FINAL, K_ACCEPT, K_ALLGATHER, K_REDUCE_SCATTER,
@@ -67,7 +72,8 @@ def build(force=False, verbose=False):
     """Cross-compile the HIP library for gfx950 with hipcc (no GPU needed)."""
     hipcc = os.environ.get("HIPCC", "hipcc")
     sources = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))] + \
-              [os.path.join(INCLUDE, f) for f in ("pdhg_hip.h", "pdhg_hip_resolve.h", "pdhg_hip_batch_resolve.h")]
+              [os.path.join(INCLUDE, f) for f in ("pdhg_hip.h", "pdhg_hip_resolve.h", "pdhg_hip_batch_resolve.h",
+                                                 "pdhg_hip_matrix_update.h")]
     if not force and os.path.exists(LIB_PATH) and \
             os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in sources):
         return LIB_PATH
@@ -101,7 +107,8 @@ def build_sanitized(kind="asan", force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "hipcc")
     path, flags = SANITIZED[kind]
     sources = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))] + \
-              [os.path.join(INCLUDE, f) for f in ("pdhg_hip.h", "pdhg_hip_resolve.h", "pdhg_hip_batch_resolve.h")]
+              [os.path.join(INCLUDE, f) for f in ("pdhg_hip.h", "pdhg_hip_resolve.h", "pdhg_hip_batch_resolve.h",
+                                                 "pdhg_hip_matrix_update.h")]
     if not force and os.path.exists(path) and os.path.getmtime(path) >= max(os.path.getmtime(f) for f in sources):
         return path
     cmd = [hipcc, "-O1", "-g"] + HIPCC_FLAGS[1:] + flags + ["-fno-gpu-sanitize", "-I", INCLUDE, "-o", path, SRC_PATH] + LINK_FLAGS
@@ -135,7 +142,8 @@ def lib():
     d, i64, i32 = ctypes.c_double, ctypes.c_int64, ctypes.c_int
     # a stale library (older ABI: different out[] lengths, missing entry points)
     # must fail here, not as a buffer overrun deep inside a solve
-    missing = [name for name in EXPORTS + RESOLVE_EXPORTS + BATCH_RESOLVE_EXPORTS if not hasattr(L, name)]
+    missing = [name for name in EXPORTS + RESOLVE_EXPORTS + BATCH_RESOLVE_EXPORTS + MATRIX_UPDATE_EXPORTS
+               if not hasattr(L, name)]
     L.pdhg_abi_version.restype = i32
     L.pdhg_abi_version.argtypes = []
     version = L.pdhg_abi_version() if not missing or "pdhg_abi_version" not in missing else None
@@ -309,6 +317,9 @@ def lib():
     L.pdhg_batch_warm_start.argtypes = [_vp, _dpp, _dpp]
     L.pdhg_batch_resolve_info.restype = i32
     L.pdhg_batch_resolve_info.argtypes = [_vp, _ip]
+    # include/pdhg_hip_matrix_update.h
+    L.pdhg_update_matrix_values.restype = i32
+    L.pdhg_update_matrix_values.argtypes = [_vp, i64, _dp, i64, _dp, _dp, _dp, _dp, _dp]
     _lib = L
     return L
 

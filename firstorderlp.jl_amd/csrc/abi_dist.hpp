@@ -238,6 +238,7 @@ int pdhg_set_objective_matrix(pdhg_handle *h0, int64_t q_nnz, const int64_t *q_c
     h->local_mode = -1;
     h->graph_mode = -1;
     h->small_lp_mode = -1;
+    h->csc_ascending = -1;               // (pdhg_update_matrix_values looks at the new Q's columns too)
     graph_destroy(h->tgraph[0]); graph_destroy(h->tgraph[1]);
     if (h->has_q) { free_csr_dev(h->Q); free_csr_dev(h->Qt); h->has_q = false; }
     if (all_zero) continue;  // iszero(objective_matrix): LP path (pdhg.jl:536)

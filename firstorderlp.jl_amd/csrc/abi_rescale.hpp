@@ -52,6 +52,8 @@ static int resolve_reserve(pdhg_handle *h, int64_t extra) {
 }
 
 // one scale_problem step on every resident layout + the vectors of one shard
+// EVERY COPY OF A MATRIX MUST APPEAR IN scale_one BELOW AND IN place_matrix_values (abi_matrix_update.hpp), which gives
+// the same copies new values: a layout added to one and not to the other keeps unscaled or stale values.
 static int apply_scaling(pdhg_handle *h, RescaleTmp &t) {
   const int n = (int)h->n, m = (int)h->m;
   hipLaunchKernelGGL(resc_zero_to_one_inv_kernel, dim3(h->ew_grid_m), dim3(TPB), 0, h->stream, m, t.ev, t.inv_e, 0);

@@ -36,6 +36,7 @@
 #include "pdhg_hip.h"
 #include "pdhg_hip_resolve.h"
 #include "pdhg_hip_batch_resolve.h"
+#include "pdhg_hip_matrix_update.h"
 
 // The kernels and layout builders live in the headers below; they form ONE
 // translation unit with this file (the tiled kernel is sensitive to code
@@ -56,6 +57,7 @@
 #include "batch_kernels.hpp"
 #include "resolve_kernels.hpp"
 #include "batch_resolve_kernels.hpp"
+#include "matrix_update_kernels.hpp"
 
 namespace { struct DistGroup; struct FleetState; struct ResolveState; }
 namespace {
@@ -102,6 +104,9 @@ struct pdhg_handle {
   bool bnd_dirty = false;
   // re-solves (abi_resolve.hpp): the retained rescaling steps and the staging buffers; nullptr until pdhg_resolve_retain
   ResolveState *rs = nullptr;
+  // new matrix values in place (abi_matrix_update.hpp): do the columns given at create hold strictly ascending row indices?
+  // -1 not looked at yet (a handle's first pdhg_update_matrix_values looks), 0 no (that call refuses), 1 yes
+  int csc_ascending = -1;
   double *x = nullptr, *x_next = nullptr, *xbar = nullptr;
   double *y = nullptr, *y_next = nullptr;
   double *aty = nullptr, *aty_next = nullptr;  // n+1 each (slot n: exchange scalar)
@@ -879,4 +884,5 @@ static int batch_scale_members(pdhg_handle *h, const double *dv, const double *e
 #include "abi_fleet_checks.hpp"
 #include "abi_resolve.hpp"
 #include "abi_batch_resolve.hpp"
+#include "abi_matrix_update.hpp"
 }  // extern "C"

@@ -376,6 +376,22 @@ class HipPdhgEngine:
         ub = self._vector("variable_upper_bound", variable_upper_bound, self.n)
         _lib.check(self._L.pdhg_update_problem_vectors(h, _pd(c), _pd(b), _pd(lb), _pd(ub)))
 
+    def update_matrix_values(self, constraint_matrix_values, objective_matrix_values, objective_vector, right_hand_side,
+                             variable_lower_bound, variable_upper_bound):
+        """``pdhg_update_matrix_values`` (include/pdhg_hip_matrix_update.h): new values of the constraint matrix in the
+        order of the ``data`` the engine was created from, of the objective matrix likewise (``None`` on an LP), and all
+        four vectors of the ORIGINAL problem.  Afterwards every device array holds, bit for bit, what a fresh engine
+        created from the updated problem and given ``retain_rescaling`` holds: call ``rescale`` next, as after create."""
+        h = self._live()
+        a = _d(constraint_matrix_values).reshape(-1)
+        q = None if objective_matrix_values is None else _d(objective_matrix_values).reshape(-1)
+        c = self._vector("objective_vector", objective_vector, self.n)
+        b = self._vector("right_hand_side", right_hand_side, self.m)
+        lb = self._vector("variable_lower_bound", variable_lower_bound, self.n)
+        ub = self._vector("variable_upper_bound", variable_upper_bound, self.n)
+        _lib.check(self._L.pdhg_update_matrix_values(h, len(a), _pd(a), 0 if q is None else len(q), _pd(q),
+                                                     _pd(c), _pd(b), _pd(lb), _pd(ub)))
+
     def warm_start(self, x=None, y=None):
         """``pdhg_warm_start``: start from the point (x, y) of the ORIGINAL problem's space (``None``: zeros) with
         everything else as on a fresh engine -- empty averages, zero restart point, no pending accept."""

@@ -22,21 +22,64 @@ The reference has no warm start: a warm solve differs from a cold one in the sta
 import dataclasses
 
 import numpy as np
+import scipy.sparse as sp
 
 from .batch import _default_batch_factory, _step_batch, check_batch
 from .fleet import _default_fleet_factory, _fleet_checks, _step_fleet
 from .preprocess import validate
+from .quadratic_programming import as_csc
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams, _check_inputs, _constant_step_estimate,
                                           _default_engine_factory, _device_scaled_problem, _drive_solve, _drive_solves,
                                           _host_scaled_problem, _initial_point, _rescales_on_device, _Solve)
 
 _UPDATE_FIELDS = ("objective_vector", "right_hand_side", "variable_lower_bound", "variable_upper_bound")
+# new matrix ENTRIES on the kept sparsity pattern: {the problem's field (also the key that takes a whole matrix): the key that takes its values}
+_MATRIX_FIELDS = {"constraint_matrix": "constraint_matrix_values", "objective_matrix": "objective_matrix_values"}
+
+
+def _has_objective_matrix(problem):
+    """Does an engine created from ``problem`` hold an objective matrix?  (An all-zero one is an LP to the library.)"""
+    return bool(np.any(problem.objective_matrix.data != 0.0))
+
+
+def _matrix_with_values(problem, field, values, matrix):
+    """``problem``'s matrix ``field`` with new values on the same pattern: ``values`` in the order of its ``data`` (the
+    canonical CSC the problem keeps), or ``matrix``, canonicalised the same way, whose pattern must be the same."""
+    old, name = getattr(problem, field), _MATRIX_FIELDS[field]
+    if values is not None and matrix is not None:
+        raise ValueError(f"give {name} or {field}, not both")
+    if matrix is not None:
+        name = field
+        new = as_csc(matrix, old.shape)
+        if not np.array_equal(new.indptr, old.indptr):
+            column = int(np.nonzero(np.diff(new.indptr) != np.diff(old.indptr))[0][0])
+            raise ValueError(f"{field} has another sparsity pattern: column {column} holds {int(np.diff(new.indptr)[column])} "
+                             f"stored entries, the session's {int(np.diff(old.indptr)[column])}")
+        if not np.array_equal(new.indices, old.indices):
+            at = int(np.nonzero(new.indices != old.indices)[0][0])
+            column = int(np.searchsorted(old.indptr, at, side="right")) - 1
+            raise ValueError(f"{field} has another sparsity pattern: column {column} holds other row indices")
+        values = new.data
+    values = np.array(values, dtype=np.float64).reshape(-1)
+    if values.shape != old.data.shape:
+        raise ValueError(f"{name} has shape {values.shape}, the pattern holds {old.data.shape} stored entries")
+    if not np.all(np.isfinite(values)):
+        raise ValueError(f"NaN or Inf found in {name}")
+    if field == "objective_matrix":
+        if not _has_objective_matrix(problem):
+            raise ValueError(f"{name} on a problem without an objective matrix: an update cannot turn an LP into a QP")
+        if not np.any(values != 0.0):
+            raise ValueError(f"{name} are all zero: an update cannot turn a QP into an LP")
+    return sp.csc_matrix((values, old.indices.copy(), old.indptr.copy()), shape=old.shape)
 
 
 def _updated_problem(problem, objective_vector=None, right_hand_side=None, variable_lower_bound=None,
-                     variable_upper_bound=None):
-    """``problem`` with the given vectors replaced, validated on the host (``validate``, and no lower bound above its
-    upper bound); ``problem`` itself is not touched.  Returns (updated problem, {field: new vector})."""
+                     variable_upper_bound=None, constraint_matrix_values=None, objective_matrix_values=None,
+                     constraint_matrix=None, objective_matrix=None):
+    """``problem`` with the given vectors replaced -- and, on the same sparsity pattern, the given matrix values (explicit
+    zeros among them stay stored entries) -- validated on the host (shapes and finite values, no objective-matrix values
+    on an LP and no all-zero ones on a QP, ``validate``, no lower bound above its upper bound); ``problem`` itself is not
+    touched.  Returns (updated problem, {field: new vector or matrix})."""
     given = {k: v for k, v in zip(_UPDATE_FIELDS, (objective_vector, right_hand_side, variable_lower_bound,
                                                    variable_upper_bound)) if v is not None}
     changes = {}
@@ -45,11 +88,19 @@ def _updated_problem(problem, objective_vector=None, right_hand_side=None, varia
         if value.shape != getattr(problem, name).shape:
             raise ValueError(f"{name} has shape {value.shape}, the problem needs {getattr(problem, name).shape}")
         changes[name] = value
+    for field, values, matrix in (("constraint_matrix", constraint_matrix_values, constraint_matrix),
+                                  ("objective_matrix", objective_matrix_values, objective_matrix)):
+        if values is not None or matrix is not None:
+            changes[field] = _matrix_with_values(problem, field, values, matrix)
     updated = dataclasses.replace(problem, **changes)
     validate(updated)
     if np.any(updated.variable_lower_bound > updated.variable_upper_bound):
         raise ValueError("the update leaves a variable_lower_bound above its variable_upper_bound")
     return updated, changes
+
+
+def _matrix_changed(changes):
+    return any(field in changes for field in _MATRIX_FIELDS)
 
 
 def _warm_point(problem, warm_start, last):
@@ -100,6 +151,34 @@ class _Member:
         if self.on_device:
             return {k: changes.get(k) for k in _UPDATE_FIELDS}
         return {k: (getattr(host_scaled.scaled_qp, k) if k in changes else None) for k in _UPDATE_FIELDS}
+
+    def update_matrix(self, updated, host_scaled):
+        """New matrix values on the engine (``update_matrix_values``: every copy of every layout, the raw vectors), the
+        rescaling run again as at create, and what depends on the matrix measured again; ``committed`` follows."""
+        def q(problem):              # (an update keeps the class of the problem: the engine has Q where `updated` has)
+            return problem.objective_matrix.data if _has_objective_matrix(updated) else None
+        if self.on_device:
+            self.engine.update_matrix_values(updated.constraint_matrix.data, q(updated), updated.objective_vector,
+                                             updated.right_hand_side, updated.variable_lower_bound,
+                                             updated.variable_upper_bound)
+            self.E, self.D = self.engine.rescale(self.params.l_inf_ruiz_iterations, self.params.l2_norm_rescaling,
+                                                 self.params.pock_chambolle_alpha)
+            self.matrix_max_abs = self.engine.matrix_max_abs()
+        else:
+            # the host route: the engine lives in the host-rescaled problem's space and is not rescaled
+            sq = host_scaled.scaled_qp
+            self.engine.update_matrix_values(sq.constraint_matrix.data, q(sq), sq.objective_vector, sq.right_hand_side,
+                                             sq.variable_lower_bound, sq.variable_upper_bound)
+            data = sq.constraint_matrix.data
+            self.matrix_max_abs = float(np.max(np.abs(data))) if len(data) else 0.0
+        self.estimate = None                 # the constant policy's power method sees the matrix: it runs again
+
+    def apply(self, updated, changes, host_scaled):
+        """One member's staged update on its own engine."""
+        if _matrix_changed(changes):
+            self.update_matrix(updated, host_scaled)
+        elif changes:
+            self.engine.update_problem_vectors(**self.engine_vectors(changes, host_scaled))
 
     def committed(self, updated, host_scaled):
         self.problem = updated
@@ -171,7 +250,10 @@ class PdhgSession(_Session):
     measures the matrix once.  ``engine_factory`` as in ``optimize``; an engine of another kind must offer
     ``update_problem_vectors(objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound)`` and
     ``warm_start(x, y)`` in ITS problem's space (a factory that does not rescale on the device gets host-rescaled
-    vectors and points)."""
+    vectors and points) -- and, for updates of the matrix values, ``update_matrix_values(constraint_matrix_values,
+    objective_matrix_values, objective_vector, right_hand_side, variable_lower_bound, variable_upper_bound)`` in that
+    space too: the values in the order of the ``data`` of the matrices it was created from (``None`` for the objective
+    matrix of an LP) and all four vectors; an engine that rescales on the device is rescaled again afterwards."""
 
     def __init__(self, params, problem, engine_factory=None):
         _check_inputs(params, [problem])
@@ -199,15 +281,22 @@ class PdhgSession(_Session):
     def engine(self):
         return self._live().engine
 
-    def update(self, objective_vector=None, right_hand_side=None, variable_lower_bound=None, variable_upper_bound=None):
-        """New vectors of the problem (``None``: keep).  The updated problem is validated before any device work; if
-        that raises, the session is as it was."""
+    def update(self, objective_vector=None, right_hand_side=None, variable_lower_bound=None, variable_upper_bound=None,
+               constraint_matrix_values=None, objective_matrix_values=None, constraint_matrix=None, objective_matrix=None):
+        """New vectors of the problem (``None``: keep) and new matrix ENTRIES on the kept sparsity pattern:
+        ``constraint_matrix_values`` / ``objective_matrix_values`` in the order of ``session.problem.constraint_matrix.data``
+        / ``.objective_matrix.data`` (the canonical CSC the problem keeps; explicit zeros stay stored entries), or
+        ``constraint_matrix`` / ``objective_matrix``, canonicalised the same way -- another pattern raises ``ValueError``
+        naming the first column that differs.  After a matrix change the engine takes the new values in place, is
+        rescaled again and its matrix measured again; no layout is built and nothing is allocated.  The updated problem
+        is validated before any device work; if that raises, the session is as it was."""
         mb = self._live()
         updated, changes, host_scaled = mb.staged_update(
             objective_vector=objective_vector, right_hand_side=right_hand_side,
-            variable_lower_bound=variable_lower_bound, variable_upper_bound=variable_upper_bound)
-        if changes:
-            mb.engine.update_problem_vectors(**mb.engine_vectors(changes, host_scaled))
+            variable_lower_bound=variable_lower_bound, variable_upper_bound=variable_upper_bound,
+            constraint_matrix_values=constraint_matrix_values, objective_matrix_values=objective_matrix_values,
+            constraint_matrix=constraint_matrix, objective_matrix=objective_matrix)
+        mb.apply(updated, changes, host_scaled)
         mb.committed(updated, host_scaled)
 
     def solve(self, warm_start=None):
@@ -235,14 +324,21 @@ class _GroupSession(_Session):
 
     def update(self, updates):
         """``updates``: one entry per problem -- ``None`` (keep the problem) or a dict with any of ``objective_vector``,
-        ``right_hand_side``, ``variable_lower_bound``, ``variable_upper_bound``.  Every updated problem is validated
-        before any device work; if one raises, the session is as it was."""
+        ``right_hand_side``, ``variable_lower_bound``, ``variable_upper_bound`` and, where the group takes them
+        (``PdhgSession.update``), the matrix keys.  A member with new matrix values is served on its own engine -- it
+        has a matrix of its own and rescales alone, as at create; the others still ride the shared vector launch.
+        Every updated problem is validated before any device work; if one raises, the session is as it was."""
         members = self._live()
         updates = list(updates)
         if len(updates) != len(members):
             raise ValueError(f"updates has {len(updates)} entries for {len(members)} problems")
+        self._check_update_keys(updates)
         staged = [None if u is None else mb.staged_update(**u) for mb, u in zip(members, updates)]
-        vectors = [None if st is None or not st[1] else mb.engine_vectors(st[1], st[2]) for mb, st in zip(members, staged)]
+        for mb, st in zip(members, staged):
+            if st is not None and _matrix_changed(st[1]):
+                mb.update_matrix(st[0], st[2])
+        vectors = [None if st is None or not st[1] or _matrix_changed(st[1]) else mb.engine_vectors(st[1], st[2])
+                   for mb, st in zip(members, staged)]
         if any(v is not None for v in vectors):
             if self._group_takes("update_problem_vectors", members):
                 self._owner.update_problem_vectors(*[[None if v is None else v[k] for v in vectors] for k in _UPDATE_FIELDS])
@@ -253,6 +349,9 @@ class _GroupSession(_Session):
         for mb, st in zip(members, staged):
             if st is not None:
                 mb.committed(st[0], st[2])
+
+    def _check_update_keys(self, updates):
+        """(a group that cannot take every key of ``update`` says so here, before anything is staged)"""
 
     def solve(self, warm_start=None):
         """Solve every problem as updated so far; returns what the group's one-shot driver (``optimize_many``,
@@ -357,6 +456,15 @@ class PdhgBatchSession(_GroupSession):
             raise
 
     batch = property(_GroupSession._group)
+
+    def _check_update_keys(self, updates):
+        # the members share one matrix, and its layouts are lent between their handles: new values for one member have
+        # no meaning, and new values for all of them are not built yet
+        for k, u in enumerate(updates):
+            given = [] if u is None else [key for pair in _MATRIX_FIELDS.items() for key in pair if u.get(key) is not None]
+            if given:
+                raise ValueError(f"updates[{k}] gives {given[0]}: a batch session cannot change matrix values (its problems "
+                                 "share one matrix); open a new session, or use PdhgSession / PdhgFleetSession")
 
     def _group_takes(self, call, members):
         return all(mb.on_device for mb in members) and hasattr(self._owner, "update_problem_vectors") and \

@@ -4,6 +4,7 @@
                                   [--ticks 20] [--reps 5] [--iteration-limit 5000] [--profile-k 256] [--no-profile]
                                   [--out profiles/resolve_throughput.txt]
                                   [--batch pagerank,l1svm,randomqp] [--batch-k 8] [--batch-qp-shape 1000000x1000000]
+                                  [--matrix] [--matrix-qp-shape 1000000x1000000]
 
 At every tick the right-hand side of every problem is perturbed by 1 % (a fixed seed per tick and member).  Per tick:
 
@@ -29,6 +30,14 @@ personalized PageRank at 1M nodes and its L1-SVM regularization path, and ``gene
 `PdhgBatchSession`.  Their kernels (batch_resolve_replay_kernel, batch_resolve_point_kernel) are timed the same way in a
 child whose updates give all four vectors of every member, so that the replay streams the whole record: its bytes per
 second are tiles * 8 * S * (n + m) over the kernel's average duration (tiles = ceil(K / 4), S = 11 recorded steps).
+
+--matrix runs the same legs (--shapes, --single, and one QP of ``generators.random_qp_family`` at --matrix-qp-shape) with
+another tick: every stored value of A is multiplied by 1 + 0.01 N(0, 1), and those of Q by one factor 1 + 0.01 N(0, 1)
+(it stays positive semidefinite), on the same sparsity pattern.  (a) creates and rescales again; (b), (c) are
+``session.update(constraint_matrix_values=...)`` -- new values placed into every resident copy, then the rescaling -- and
+a cold or warm solve.  Beside each row, timed on one engine of the row's first problem (best of three): the
+``update_matrix_values`` call alone, the ``rescale`` call alone, and a create of the same problem; and the durations of
+the placement kernels (mu_*_kernel, sj_fill_kernel) from a profiled child of their own.
 """
 import argparse
 import dataclasses
@@ -49,6 +58,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 KERNELS = ("fleet_resolve_replay_kernel", "fleet_resolve_point_kernel", "resolve_replay_kernel", "resolve_point_kernel",
            "batch_resolve_replay_kernel", "batch_resolve_point_kernel")
 BATCH_RESOLVE_TILE = 4          # csrc/batch_resolve_kernels.hpp
+MATRIX_KERNELS = r"\b((?:mu_[a-z]+_kernel|sj_fill_kernel|scale_csr_kernel|scale_long_kernel|scale_tiled_kernel)(?:<[^>]*>)?)\("
 
 
 def single_problem(name):
@@ -65,6 +75,26 @@ def tick_rhs(problem, tick, member):
     return problem.right_hand_side * (1.0 + 0.01 * rng.uniform(-1.0, 1.0, problem.num_constraints))
 
 
+def tick_matrix(problem, tick, member):
+    """The --matrix tick as ``update``'s keywords: new values on the same pattern."""
+    rng = np.random.default_rng([tick, member, 4321])
+    A, Q = problem.constraint_matrix, problem.objective_matrix
+    update = {"constraint_matrix_values": A.data * (1.0 + 0.01 * rng.standard_normal(A.nnz))}
+    if Q.nnz:
+        update["objective_matrix_values"] = Q.data * (1.0 + 0.01 * float(rng.standard_normal()))
+    return update
+
+
+def with_matrix_values(problem, update):
+    import scipy.sparse as sp
+    changes = {}
+    for field in ("constraint_matrix", "objective_matrix"):
+        if field + "_values" in update:
+            old = getattr(problem, field)
+            changes[field] = sp.csc_matrix((update[field + "_values"], old.indices, old.indptr), shape=old.shape)
+    return dataclasses.replace(problem, **changes)
+
+
 def _iterations(outs):
     return float(np.mean([o.iteration_count for o in outs]))
 
@@ -74,8 +104,9 @@ def batch_problems(config, K, qp_shape):
     return qp_members(qp_shape, K) if config == "randomqp" else members(config, K)
 
 
-def series(problems, params, ticks, route, single, batch=False):
-    """One series of `ticks` ticks by `route` ('a', 'b', 'c'): (seconds per tick, iterations per solve)."""
+def series(problems, params, ticks, route, single, batch=False, matrix=False):
+    """One series of `ticks` ticks by `route` ('a', 'b', 'c'): (seconds per tick, iterations per solve).  `matrix`: the
+    tick changes the matrix values instead of the right-hand side."""
     from firstorderlp_jl_amd import PdhgBatchSession, PdhgFleetSession, PdhgSession, optimize_batch, optimize_many
     from firstorderlp_jl_amd.primal_dual_hybrid_gradient import optimize
     if batch:
@@ -87,16 +118,20 @@ def series(problems, params, ticks, route, single, batch=False):
             session = PdhgSession(params, problems[0]) if single else (PdhgBatchSession if batch else PdhgFleetSession)(params, problems)
             session.solve()
         for tick in range(ticks):
-            rhs = [tick_rhs(p, tick, k) for k, p in enumerate(problems)]
-            updated = [dataclasses.replace(p, right_hand_side=b) for p, b in zip(problems, rhs)] if route == "a" else None
+            if matrix:
+                updates = [tick_matrix(p, tick, k) for k, p in enumerate(problems)]
+                updated = [with_matrix_values(p, u) for p, u in zip(problems, updates)] if route == "a" else None
+            else:
+                updates = [{"right_hand_side": tick_rhs(p, tick, k)} for k, p in enumerate(problems)]
+                updated = [dataclasses.replace(p, **u) for p, u in zip(problems, updates)] if route == "a" else None
             t0 = time.perf_counter()
             if route == "a":
                 outs = [optimize(params, updated[0])] if single else optimize_many(params, updated)
             elif single:
-                session.update(right_hand_side=rhs[0])
+                session.update(**updates[0])
                 outs = [session.solve(warm_start=True if route == "c" else None)]
             else:
-                session.update([{"right_hand_side": b} for b in rhs])
+                session.update(updates)
                 outs = session.solve(warm_start=True if route == "c" else None)
             seconds.append(time.perf_counter() - t0)
             iterations.append(_iterations(outs))
@@ -106,17 +141,79 @@ def series(problems, params, ticks, route, single, batch=False):
     return float(np.mean(seconds)), float(np.mean(iterations))
 
 
-def measure(problems, params, ticks, reps, single, batch=False):
+def measure(problems, params, ticks, reps, single, batch=False, matrix=False):
     """{route: (best ms per tick, worst / best over the repetitions, iterations per solve)}, the routes alternating."""
     runs = {r: [] for r in "abc"}
     for _ in range(reps):
         for route in "abc":
-            runs[route].append(series(problems, params, ticks, route, single, batch))
+            runs[route].append(series(problems, params, ticks, route, single, batch, matrix))
     out = {}
     for route, rs in runs.items():
         secs = [s for s, _ in rs]
         out[route] = (1e3 * min(secs), max(secs) / min(secs), rs[0][1])
     return out
+
+
+def matrix_single_timings(problem, params):
+    """(ms of ``update_matrix_values`` alone, of ``rescale`` alone, of a create of the same problem), best of three each,
+    on one engine of ``problem`` (a QP's create includes its objective matrix)."""
+    from firstorderlp_jl_amd import HipPdhgEngine
+    rescaling = (params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
+    create, place, rescale = [], [], []
+    eng = None
+    try:
+        for _ in range(3):
+            if eng is not None:
+                eng.close()
+            t0 = time.perf_counter()
+            eng = HipPdhgEngine.from_problem(problem)
+            create.append(time.perf_counter() - t0)
+        eng.retain_rescaling()
+        eng.rescale(*rescaling)
+        for tick in range(3):
+            u = tick_matrix(problem, tick, 0)
+            p = with_matrix_values(problem, u)
+            t0 = time.perf_counter()
+            eng.update_matrix_values(u["constraint_matrix_values"], u.get("objective_matrix_values"), p.objective_vector,
+                                     p.right_hand_side, p.variable_lower_bound, p.variable_upper_bound)
+            t1 = time.perf_counter()
+            eng.rescale(*rescaling)
+            t2 = time.perf_counter()
+            place.append(t1 - t0)
+            rescale.append(t2 - t1)
+    finally:
+        if eng is not None:
+            eng.close()
+    return 1e3 * min(place), 1e3 * min(rescale), 1e3 * min(create)
+
+
+def matrix_problem(name, qp_shape):
+    """A --matrix leg's single problem: --single's, or ``qp`` = one QP of ``random_qp_family`` at ``qp_shape``."""
+    if name != "qp":
+        return single_problem(name)
+    from firstorderlp_jl_amd.generators import random_qp_family
+    m, n = (int(v) for v in qp_shape.split("x"))
+    return random_qp_family(m, n, 1, seed=1)[0]
+
+
+def matrix_child(name, K, ticks, qp_shape):
+    """What the profiled child of a --matrix leg runs: `ticks` matrix updates and warm solves with a short iteration limit."""
+    from fleet_bench import members, solve_params
+    from firstorderlp_jl_amd import PdhgFleetSession, PdhgSession
+    if K > 1:
+        problems = members(name, K)
+        with PdhgFleetSession(solve_params(80), problems) as session:
+            session.solve()
+            for tick in range(ticks):
+                session.update([tick_matrix(p, tick, k) for k, p in enumerate(problems)])
+                session.solve(warm_start=True)
+        return
+    problem = matrix_problem(name, qp_shape)
+    with PdhgSession(solve_params(80), problem) as session:
+        session.solve()
+        for tick in range(ticks):
+            session.update(**tick_matrix(problem, tick, 0))
+            session.solve(warm_start=True)
 
 
 def child(shape, K, ticks):
@@ -146,22 +243,23 @@ def batch_child(config, K, ticks, qp_shape):
             session.solve(warm_start=True)
 
 
-def kernel_us(shape, K, ticks=4, timeout=400, extra=()):
+def kernel_us(shape, K, ticks=4, timeout=400, extra=(), flag="--child", pattern=None):
     """{kernel: (calls, average us)} of the re-solve kernels in a `rocprofv3 --kernel-trace --stats` run of a child of its
-    own, or a string saying why there is none.  `extra`: more arguments for the child (a batch leg's)."""
+    own, or a string saying why there is none.  `extra`: more arguments for the child (a batch leg's); `flag`, `pattern`:
+    another child and the kernels to pick from its trace (a --matrix leg's)."""
     from rocprof_summary import summarize
     rp = shutil.which("rocprofv3")
     if not rp:
         return "rocprofv3 not on PATH"
     work = tempfile.mkdtemp(prefix="pdhg_resolve_prof_", dir="/tmp")
     try:
-        cmd = [rp, "--kernel-trace", "--stats", "-d", work, "--", sys.executable, os.path.abspath(__file__), "--child", shape, str(K), str(ticks), *extra]
+        cmd = [rp, "--kernel-trace", "--stats", "-d", work, "--", sys.executable, os.path.abspath(__file__), flag, shape, str(K), str(ticks), *extra]
         r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), timeout=timeout, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
         if r.returncode != 0:
             return f"profiled child failed ({r.returncode}): {r.stderr.decode(errors='replace')[-200:]}"
         out = {}
         for k in summarize(work):
-            hit = re.search(r"\b(" + "|".join(KERNELS) + r")\(", k["name"])
+            hit = re.search(pattern or r"\b(" + "|".join(KERNELS) + r")\(", k["name"])
             if hit:
                 out[hit.group(1)] = (k.get("calls"), k["avg_us"])
         return out or "no re-solve kernel in the trace"
@@ -169,6 +267,45 @@ def kernel_us(shape, K, ticks=4, timeout=400, extra=()):
         return f"profiled child timed out after {timeout} s"
     finally:
         shutil.rmtree(work, ignore_errors=True)
+
+
+def matrix_legs(args, params, ks, emit):
+    """The --matrix table: the fleet shapes at every K, --single's problems and one QP."""
+    from fleet_bench import members
+    emit("# ms per tick: best series of `reps` (mean over its ticks); spread: worst / best series; it: iterations per solve")
+    emit("# --matrix: per tick every stored value of A times 1 + 0.01 N(0, 1) (Q times one such factor) on the kept pattern; (a) optimize / "
+         "optimize_many on the updated problems, (b) session.update(constraint_matrix_values=...) + cold solve, (c) the same + warm solve")
+    emit("# place / rescale / create: ms of update_matrix_values, of rescale and of a create of the row's first problem, each alone (best of 3)")
+    emit(f"{'problem':<15} {'K':>5} {'(a) ms':>9} {'spread':>6} {'it':>7} {'(b) ms':>9} {'spread':>6} {'it':>7} {'(c) ms':>9} {'spread':>6} {'it':>7} "
+         f"{'a/b':>6} {'a/c':>6} {'place':>8} {'rescale':>8} {'create':>8}")
+
+    def row(name, K, problems, single):
+        got = measure(problems, params, args.ticks, args.reps, single, matrix=True)
+        place, rescale, create = matrix_single_timings(problems[0], params)
+        a, b, c = got["a"], got["b"], got["c"]
+        ahead = a[0] / b[0] > max(a[1], b[1])
+        emit(f"{name:<15} {K:>5} {a[0]:>9.2f} {a[1]:>6.2f} {a[2]:>7.1f} {b[0]:>9.2f} {b[1]:>6.2f} {b[2]:>7.1f} {c[0]:>9.2f} {c[1]:>6.2f} "
+             f"{c[2]:>7.1f} {a[0] / b[0]:>6.2f} {a[0] / c[0]:>6.2f} {place:>8.2f} {rescale:>8.2f} {create:>8.2f}"
+             + ("" if a[2] == b[2] else "   # (a) and (b) DIFFER in iterations") + ("" if ahead else "   # (b) is NOT ahead of (a) by more than the spread"))
+
+    def kernels(name, K, extra):
+        if args.no_profile:
+            return
+        got = kernel_us(name, K, ticks=2, extra=extra, flag="--matrix-child", pattern=MATRIX_KERNELS)
+        if isinstance(got, str):
+            emit(f"# {name}: placement kernels at K = {K}: not measured ({got})")
+        else:
+            emit(f"# {name}: placement and scale kernels at K = {K} (rocprofv3 --kernel-trace --stats, a run of its own), calls x average us: "
+                 + "; ".join(f"{n} {c} x {us:.1f}" for n, (c, us) in sorted(got.items())))
+
+    for shape in [s for s in args.shapes.split(",") if s]:
+        problems = members(shape, max(ks))
+        for K in ks:
+            row(shape, K, problems[:K], False)
+        kernels(shape, min(args.profile_k, max(ks)), (args.matrix_qp_shape or "-",))
+    for name in [s for s in args.single.split(",") if s] + (["qp"] if args.matrix_qp_shape else []):
+        row(name, 1, [matrix_problem(name, args.matrix_qp_shape)], True)
+        kernels(name, 1, (args.matrix_qp_shape or "-",))
 
 
 def main(argv=None):
@@ -185,11 +322,17 @@ def main(argv=None):
     ap.add_argument("--batch", default="", help="batch legs: any of pagerank,l1svm,randomqp")
     ap.add_argument("--batch-k", type=int, default=8)
     ap.add_argument("--batch-qp-shape", default="1000000x1000000")
+    ap.add_argument("--matrix", action="store_true", help="the tick changes the matrix values on the kept pattern")
+    ap.add_argument("--matrix-qp-shape", default="1000000x1000000", help="--matrix: the QP leg's shape ('' for none)")
     ap.add_argument("--child", nargs="+", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--matrix-child", nargs="+", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     import folp_loader
     folp_loader.load()
     from fleet_bench import members, solve_params
+    if args.matrix_child:
+        matrix_child(args.matrix_child[0], int(args.matrix_child[1]), int(args.matrix_child[2]), args.matrix_child[3])
+        return
     if args.child and len(args.child) > 3:
         batch_child(args.child[0], int(args.child[1]), int(args.child[2]), args.child[3])
         return
@@ -204,7 +347,14 @@ def main(argv=None):
         lines.append(line)
 
     emit(f"# tools/resolve_bench.py --shapes {args.shapes} --ks {args.ks} --single {args.single} --ticks {args.ticks} --reps {args.reps} "
-         f"--iteration-limit {args.iteration_limit}")
+         f"--iteration-limit {args.iteration_limit}" + (f" --matrix --matrix-qp-shape {args.matrix_qp_shape}" if args.matrix else ""))
+    ks = [int(k) for k in args.ks.split(",") if k]
+    if args.matrix:
+        matrix_legs(args, params, ks, emit)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     emit("# per tick: b perturbed by 1 %; (a) optimize / optimize_many on the updated problems (create + rescale again), (b) session "
          "update + cold solve, (c) session update + warm solve from the last solution")
     emit("# ms per tick: best series of `reps` (mean over its ticks); spread: worst / best series; it: iterations per solve")
@@ -217,7 +367,6 @@ def main(argv=None):
         emit(f"{name:<15} {K:>5} {a[0]:>9.2f} {a[1]:>6.2f} {a[2]:>7.1f} {b[0]:>9.2f} {b[1]:>6.2f} {b[2]:>7.1f} {c[0]:>9.2f} {c[1]:>6.2f} "
              f"{c[2]:>7.1f} {a[0] / b[0]:>6.2f} {a[0] / c[0]:>6.2f}" + ("" if a[2] == b[2] else "   # (a) and (b) DIFFER in iterations"))
 
-    ks = [int(k) for k in args.ks.split(",") if k]
     for shape in [s for s in args.shapes.split(",") if s]:
         problems = members(shape, max(ks))
         for K in ks:
