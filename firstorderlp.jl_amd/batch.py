@@ -9,7 +9,9 @@ per-problem solve object (``primal_dual_hybrid_gradient._Solve``): only the step
 
 ``HipPdhgBatch`` is the device side: one ``pdhg_handle`` that owns the matrix plus K member handles that borrow it
 (``.members``: ``HipPdhgEngine`` views -- every single-LP method works on them).  With ``objective_matrix`` the members
-are QPs that borrow one objective matrix too (``pdhg_batch_set_objective_matrix``).  A batch that is solved again and
+are QPs that borrow one objective matrix too (``pdhg_batch_set_objective_matrix``).  With ``PDHG_BATCH_CHECKS=1`` the
+members' check products and evaluations share launches (``point_products`` / ``eval_points``,
+include/pdhg_hip_batch_checks.h; ``_batch_checks``); every member's own evaluator call still runs, and finds them.  A batch that is solved again and
 again keeps its handle (``retain_rescaling`` / ``update_problem_vectors`` / ``warm_start``,
 include/pdhg_hip_batch_resolve.h; ``session.PdhgBatchSession`` drives them).
 """
@@ -135,6 +137,37 @@ class HipPdhgBatch(_MemberOwner):
         return self._take_steps_adaptive(self._L.pdhg_batch_take_steps_adaptive, int(n_steps), reduction_exponent,
                                          growth_exponent, step_sizes, primal_weights, total_number_iterations,
                                          cumulative_kkt_passes, a.ctypes.data_as(_int_p))
+
+    # ---- the checks in shared launches (include/pdhg_hip_batch_checks.h) ----
+    def point_products(self, items):
+        """A x, A' y (and Q x) at ``point`` of member ``k`` for every item ``(k, point)``, from one read of the matrix
+        per point kind, into the members' own product caches: the members' ``eval_point`` / ``trust_region_bound(s)``
+        at those points then launch no product.  At most ``3 * MAX_BATCH`` items."""
+        items = list(items)
+        if not items:
+            return
+        ks = np.ascontiguousarray([k for k, _ in items], dtype=np.int32)
+        pts = np.ascontiguousarray([p for _, p in items], dtype=np.int32)
+        _lib.check(self._L.pdhg_batch_point_products(self._live(), len(items), ks.ctypes.data_as(_int_p),
+                                                     pts.ctypes.data_as(_int_p)))
+
+    def eval_points(self, points):
+        """``members[k].eval_point(points[k])`` for every k (-1: member k is left alone, its row stays zeros), all
+        members in shared launches: a (K, 24) array.  Every result is also left in its member: the member's own
+        ``eval_point`` with the same point answers from it until the member's state moves."""
+        pts = np.ascontiguousarray(np.broadcast_to(points, (self.K,)), dtype=np.int32)
+        out = np.zeros((self.K, 24))
+        _lib.check(self._L.pdhg_batch_eval_points(self._live(), pts.ctypes.data_as(_int_p), _pd(out)))
+        return out
+
+    def check_info(self):
+        """``pdhg_batch_check_info`` as a dict: calls, items whose products rode a batched launch (``batched``), items
+        with a product served by the member's own launch (``own``), items found ``cached``, members ``carried`` by
+        ``eval_points``, member evaluations ``served`` from a stored result, ``misses`` (member evaluations that
+        launched although the batch had been asked) and ``launches``; all since the batch was created."""
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(self._L.pdhg_batch_check_info(self._live(), _pi(info)))
+        return dict(zip(["calls", "batched", "own", "cached", "carried", "served", "misses", "launches"], info.tolist()))
 
     # ---- re-solves on the batch handle (include/pdhg_hip_batch_resolve.h): ``_MemberOwner``'s, over these ----
     _noun, _resolve_other = "batch", "batched_product"
@@ -284,6 +317,38 @@ def _step_batch(batch, policy, requests):
     return out
 
 
+def _batch_checks(batch, solves, pending):
+    """One sweep of a round's checks (``_check_round``), the counterpart of ``fleet._fleet_checks``: the members'
+    ``"iteration_stats"`` requests as ONE ``batch.eval_points``, and the points that their ``"bounds"`` requests'
+    trust-region problems name as ONE ``batch.point_products``.  The results stay with the members: each member's own
+    evaluator call, which follows unchanged, finds them.  (The searches themselves stay per member.)"""
+    points = np.full(len(batch.members), -1, dtype=np.int32)
+    items = []
+    for mb, (method, arguments) in pending:
+        k = _slot(batch, mb)
+        if method == "iteration_stats":
+            points[k] = arguments[0]
+        elif method == "bounds":
+            requests, _, _, norm, _ = arguments
+            for point in dict.fromkeys(int(point) for point, _, _ in mb.ev.tr_problems(requests, norm)):
+                items.append((k, point))
+    if (points >= 0).any():
+        batch.eval_points(points)
+    if items:
+        batch.point_products(items)
+
+
+def _checks_hook(batch, solves):
+    """``_drive_solves``' ``checks`` for a batch: ``_batch_checks`` when the batch offers both calls and
+    ``PDHG_BATCH_CHECKS=1`` is set (read at every solve; off by default: the path is new), else None -- every member
+    checks on its own, as before."""
+    if os.environ.get("PDHG_BATCH_CHECKS", "0") != "1":
+        return None
+    if not (hasattr(batch, "eval_points") and hasattr(batch, "point_products")):
+        return None
+    return lambda pending: _batch_checks(batch, solves, pending)
+
+
 def _initial_points(problems, initial_solutions):
     """``initial_solutions`` of ``optimize_batch`` checked on the host: one ``_initial_point`` result per problem."""
     if initial_solutions is None:
@@ -342,7 +407,7 @@ def optimize_batch(params, problems, batch_factory=None, initial_solutions=None)
         for mb in members:
             mb.start(estimate)
 
-        return _drive_solves(members, lambda requests: _step_batch(batch, policy, requests))
+        return _drive_solves(members, lambda requests: _step_batch(batch, policy, requests), _checks_hook(batch, members))
     finally:
         if batch is not None and hasattr(batch, "close"):
             batch.close()

@@ -36,6 +36,18 @@ struct BatchState {
   int64_t trials = 0;
   // re-solves (abi_batch_resolve.hpp): what the calls did (`other`: whether the last warm start ran the batched product)
   ResolveCounters rsv;
+  // the checks in shared launches (abi_batch_checks.hpp), allocated by the first such call: what a call uploads (device copy,
+  // pinned staging, "the upload has been read"), the members' result words (BATCH_MAX x (EV_HOST_SLOTS + 2), pinned) and
+  // their sequence number, and pdhg_batch_check_info's counters 0-4 and 7 (5 and 6 are counted where a member answers:
+  // pdhg_handle::bchk_*)
+  struct Checks {
+    BatchCheckStage *stage_dev = nullptr, *stage_host = nullptr;
+    hipEvent_t uploaded = nullptr;
+    bool upload_pending = false;
+    double *res = nullptr;
+    unsigned long long seq = 0;
+    int64_t calls = 0, batched = 0, own = 0, cached = 0, carried = 0, launches = 0;
+  } chk;
 };
 
 static void batch_free_product(BatchProduct &P) {
@@ -72,8 +84,10 @@ static void batch_release(pdhg_handle *h) {
   batch_free_product(B->PT);
   for (void *p : {(void *)B->X, (void *)B->Y, (void *)B->mdev, (void *)B->act_dev, (void *)B->res_dev})
     if (p) (void)hipFree(p);
-  for (void *p : {(void *)B->mhost, (void *)B->act_host, (void *)B->res_host})
+  for (void *p : {(void *)B->mhost, (void *)B->act_host, (void *)B->res_host, (void *)B->chk.stage_host, (void *)B->chk.res})
     if (p) (void)hipHostFree(p);
+  if (B->chk.stage_dev) (void)hipFree(B->chk.stage_dev);
+  if (B->chk.uploaded) (void)hipEventDestroy(B->chk.uploaded);
   delete B;
   h->bat = nullptr;
 }

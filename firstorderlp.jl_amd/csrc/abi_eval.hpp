@@ -182,9 +182,9 @@ int pdhg_eval_point(pdhg_handle *h0, int point, double out[24]) {
   int rc = check_handle(h0);
   if (rc) return rc;
   if (!h0->has_original) return fail(-1, "pdhg_set_original_problem has not been called");
-  if (h0->fleet_of) {                                          // a fleet's member: did pdhg_fleet_eval_points leave this result here?
-    if (fleet_stored_eval(h0, point, out)) return 0;
-    fleet_count_miss(h0);
+  if (stored_checks_member(h0)) {                              // a fleet's or a batch's member: did pdhg_fleet_eval_points / pdhg_batch_eval_points leave this result here?
+    if (fleet_stored_eval(h0, point, out)) { stored_eval_served(h0); return 0; }
+    stored_eval_missed(h0);
   }
   const Shards L = shards_of(h0);
   if ((rc = flush_pending(L))) return rc;

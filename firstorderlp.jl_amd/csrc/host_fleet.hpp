@@ -93,6 +93,17 @@ void fleet_forget(pdhg_handle *h) {
 void fleet_count_miss(pdhg_handle *h) {
   if (h->fleet_of && h->fleet_of->fleet && !h->fleet_of->fleet->chk_serving) h->fleet_of->fleet->chk_misses += 1;
 }
+// The same path for a batch's member (`owner` = the batch; pdhg_batch_eval_points stores its results as a fleet's call
+// does): is the handle a member whose group can have left a result in it, and the group's counts of evaluations answered
+// from one / launched by the member although the batch had been asked
+inline bool stored_checks_member(const pdhg_handle *h) { return h->fleet_of != nullptr || h->owner != nullptr; }
+void stored_eval_served(pdhg_handle *h) {
+  if (h->owner) h->owner->bchk_served += 1;
+}
+void stored_eval_missed(pdhg_handle *h) {
+  fleet_count_miss(h);
+  if (h->owner && h->owner->bchk_asked && !h->owner->bchk_serving) h->owner->bchk_misses += 1;
+}
 
 // one carried member of a call
 struct FleetCarry {

@@ -37,6 +37,7 @@
 #include "pdhg_hip_resolve.h"
 #include "pdhg_hip_batch_resolve.h"
 #include "pdhg_hip_matrix_update.h"
+#include "pdhg_hip_batch_checks.h"
 
 // The kernels and layout builders live in the headers below; they form ONE
 // translation unit with this file (the tiled kernel is sensitive to code
@@ -57,6 +58,7 @@
 #include "batch_kernels.hpp"
 #include "resolve_kernels.hpp"
 #include "batch_resolve_kernels.hpp"
+#include "batch_check_kernels.hpp"
 #include "matrix_update_kernels.hpp"
 
 namespace { struct DistGroup; struct FleetState; struct ResolveState; }
@@ -266,6 +268,10 @@ struct pdhg_handle {
   // vectors); a member's A / At are the batch's layouts, borrowed (`owner` = the batch): it is freed with the batch.
   BatchState *bat = nullptr;
   pdhg_handle *owner = nullptr;
+  // a batch handle: its members' evaluations since pdhg_batch_eval_points was first called (abi_batch_checks.hpp) -- answered
+  // from the result that call stored / launched by the member itself; serving: inside the batch call's own per-member calls
+  int64_t bchk_served = 0, bchk_misses = 0;
+  bool bchk_asked = false, bchk_serving = false;
 
   // ---- fleets of independent small LPs (abi_fleet.hpp).  A fleet handle owns `fleet` (its members, the argument table
   // and the shared tables of powers of a many-LP launch) and runs no iterations of its own; a member is a complete
@@ -884,5 +890,6 @@ static int batch_scale_members(pdhg_handle *h, const double *dv, const double *e
 #include "abi_fleet_checks.hpp"
 #include "abi_resolve.hpp"
 #include "abi_batch_resolve.hpp"
+#include "abi_batch_checks.hpp"
 #include "abi_matrix_update.hpp"
 }  // extern "C"

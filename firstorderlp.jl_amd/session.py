@@ -24,7 +24,7 @@ import dataclasses
 import numpy as np
 import scipy.sparse as sp
 
-from .batch import _default_batch_factory, _step_batch, check_batch
+from .batch import _checks_hook, _default_batch_factory, _step_batch, check_batch
 from .fleet import _default_fleet_factory, _fleet_checks, _step_fleet
 from .preprocess import validate
 from .quadratic_programming import as_csc
@@ -479,4 +479,4 @@ class PdhgBatchSession(_GroupSession):
             self._estimate = _constant_step_estimate(solves[0])
         for solve in solves:
             solve.start(self._estimate)
-        return _drive_solves(solves, lambda requests: _step_batch(batch, policy, requests))
+        return _drive_solves(solves, lambda requests: _step_batch(batch, policy, requests), _checks_hook(batch, solves))
