@@ -25,10 +25,11 @@ import scipy.sparse as sp
 from . import _lib
 from .engine import _MemberEngine, _MemberOwner, _d, _i, _int_p, _pd, _pi
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams,
-                                          MalitskyPockStepsizeParameters, _check_inputs, _constant_step_estimate,
-                                          _device_scaled_problem, _drive_solves, _host_scaled_problem, _initial_point,
-                                          _pack_step_states, _rescales_on_device, _set_initial_point, _Solve,
-                                          _unpack_step_states, adaptive_step_rule)
+                                          MalitskyPockStepsizeParameters, _check_inputs, _check_requests,
+                                          _constant_step_estimate, _device_scaled_problem, _drive_solves,
+                                          _host_scaled_problem, _initial_point, _pack_step_states,
+                                          _rescales_on_device, _set_initial_point, _Solve, _unpack_step_states,
+                                          adaptive_step_rule)
 
 MAX_BATCH = 32
 
@@ -322,16 +323,8 @@ def _batch_checks(batch, solves, pending):
     ``"iteration_stats"`` requests as ONE ``batch.eval_points``, and the points that their ``"bounds"`` requests'
     trust-region problems name as ONE ``batch.point_products``.  The results stay with the members: each member's own
     evaluator call, which follows unchanged, finds them.  (The searches themselves stay per member.)"""
-    points = np.full(len(batch.members), -1, dtype=np.int32)
-    items = []
-    for mb, (method, arguments) in pending:
-        k = _slot(batch, mb)
-        if method == "iteration_stats":
-            points[k] = arguments[0]
-        elif method == "bounds":
-            requests, _, _, norm, _ = arguments
-            for point in dict.fromkeys(int(point) for point, _, _ in mb.ev.tr_problems(requests, norm)):
-                items.append((k, point))
+    points, tr_items = _check_requests(pending, lambda mb: _slot(batch, mb), len(batch.members))
+    items = list(dict.fromkeys((k, int(point)) for k, point, *_ in tr_items))       # each once, first seen first
     if (points >= 0).any():
         batch.eval_points(points)
     if items:

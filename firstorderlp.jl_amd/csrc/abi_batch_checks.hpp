@@ -1,11 +1,11 @@
 // abi_batch_checks.hpp -- part of the single translation unit pdhg_hip.hip (included there, inside its extern "C" block, after
-// abi_batch_resolve.hpp).
+// abi_batch_resolve.hpp; what a check here shares with one handle's and a fleet's stands in host_checks.hpp).
 // C ABI: a batch's CHECKS in shared launches (include/pdhg_hip_batch_checks.h; kernels in batch_check_kernels.hpp).
 //
 //   pdhg_batch_point_products   A x, A' y (and Q x) at points of many members: one pass per point kind -- the points packed
 //                               member-interleaved into the batch's X / Y, then one plain batched product per matrix
-//                               straight into the members' per-point caches, whose keys are set as the member's own
-//                               point_products sets them: that call then finds them fresh and launches nothing
+//                               straight into the members' per-point caches, whose keys claim_point sets as it does for
+//                               the member's own point_products: that call then finds them fresh and launches nothing
 //   pdhg_batch_eval_points      the products, then pdhg_eval_point's one-handle form of all carried members in four
 //                               launches; every result is stored with its member (host_fleet.hpp: fleet_store_eval)
 //   pdhg_batch_check_info       what the calls did
@@ -18,9 +18,9 @@
 static int batch_checks_ensure(pdhg_handle *h) {
   BatchState::Checks &C = h->bat->chk;
   if (C.stage_dev) return 0;
-  const size_t words = (size_t)BATCH_MAX * (EV_HOST_SLOTS + 2);
-  HIP_TRY(hipHostMalloc((void **)&C.res, words * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
-  memset(C.res, 0, words * sizeof(double));
+  size_t cap = C.res ? BATCH_MAX : 0;
+  int rc = ensure_result_words(&C.res, &cap, BATCH_MAX, h->stream);
+  if (rc) return rc;
   HIP_TRY(hipHostMalloc((void **)&C.stage_host, sizeof(BatchCheckStage), hipHostMallocDefault));
   HIP_TRY(hipEventCreateWithFlags(&C.uploaded, hipEventDisableTiming));
   HIP_TRY(hipMalloc((void **)&C.stage_dev, sizeof(BatchCheckStage)));
@@ -32,10 +32,9 @@ struct BatchCheckCall {
   int count[3] = {0, 0, 0};             // entries of BatchCheckStage::pts[p]
   unsigned mask[3] = {0, 0, 0};         // members whose products pass p computes
   int slot[3][BATCH_MAX];               // member k's entry of pass p, or -1
+  PointRef pt[3][BATCH_MAX];            // where mask[p] names member k: the point and where its products go
   BatchCheckCall() { for (auto &row : slot) for (int &s : row) s = -1; }
 };
-
-static int batch_point_index(int point) { return point == PDHG_POINT_CURRENT ? 0 : (point == PDHG_POINT_AVERAGE ? 1 : 2); }
 
 // every argument error of one (member, point), before anything is touched
 static int batch_check_refuse(pdhg_handle *h, int k, int point, const std::string &who) {
@@ -44,58 +43,36 @@ static int batch_check_refuse(pdhg_handle *h, int k, int point, const std::strin
   pdhg_handle *m = B.mem[(size_t)k];
   int rc = check_handle(m);
   if (rc) return rc;
-  if (point != PDHG_POINT_CURRENT && point != PDHG_POINT_AVERAGE && point != PDHG_POINT_RESTART)
-    return fail(-1, who + ": unknown point selector");
-  if (point == PDHG_POINT_AVERAGE && (m->sum_x_count == 0 || m->sum_y_count == 0)) return fail(-1, who + ": average is empty");
-  return 0;
+  return point_error(m, point, who);
 }
 
-// select_point + point_products of member k at `point`, as bookkeeping (fleet_stage_point's statements): the average and the
-// caches are marked fresh exactly as the member's own calls mark them, and what has to be computed becomes an entry of the
-// point's pass.  products == false: the average only (the evaluation's distances).  *was_stale: the products are computed.
+// claim_point of member k at `point`, and what the claim asks for -- the average materialised, the products computed -- as
+// an entry of the point's pass.  products == false: the average only (the evaluation's distances).
 static int batch_check_stage(pdhg_handle *h, int k, int point, bool products, BatchCheckStage &S, BatchCheckCall &call,
-                             FleetMarks &marks, bool *was_stale) {
+                             CheckMarks &marks, PointClaim *c) {
   pdhg_handle *m = h->bat->mem[(size_t)k];
-  const int p = batch_point_index(point);
-  int rc;
-  marks.keep(m);
-  const bool need_div = p == 1 && m->avg_version != m->state_version;
-  bool stale = false;
-  if (products) {
-    if (p < 2) {
-      stale = m->ev_cversion[p] != m->state_version;
-      m->ev_cversion[p] = m->state_version;
-    } else {
-      const uint64_t key = (m->matrix_version << 32) + m->restart_version;
-      stale = m->ev_rkey != key;
-      m->ev_rkey = key;
-    }
-    if (m->has_q && !m->ev_cqx[p]) {
-      if ((rc = alloc_zero(&m->ev_cqx[p], m->n))) return rc;
-      stale = true;
-    }
-  }
-  if (was_stale) *was_stale = stale;
-  if (!need_div && !stale) return 0;
+  const int p = point_index(point);
+  int rc = claim_point(m, point, products, &marks, c);
+  if (rc) return rc;
+  if (!c->need_div && !c->stale) return 0;
   int &slot = call.slot[p][k];
   if (slot < 0) {
     slot = call.count[p]++;
     BatchCheckPoint e{};
     e.k = k;
-    if (p == 0) { e.src_x = m->x; e.src_y = m->y; }
-    else if (p == 2) { e.src_x = m->x_r; e.src_y = m->y_r; }
-    else if (need_div) {
+    e.src_x = c->px; e.src_y = c->py;
+    if (c->need_div) {
       e.do_div = 1;
       e.src_x = m->sum_x; e.src_y = m->sum_y; e.wx = m->sum_x_weights; e.wy = m->sum_y_weights;
       e.avg_x = m->px_avg; e.avg_y = m->py_avg;
-    } else { e.src_x = m->px_avg; e.src_y = m->py_avg; }
+    }
     S.pts[p][slot] = e;
   }
-  if (need_div) m->avg_version = m->state_version;
-  if (stale) {
+  if (c->stale) {
     S.pts[p][slot].pack = 1;
     call.mask[p] |= 1u << k;
-    S.out[p][0][k] = m->ev_cax[p]; S.out[p][1][k] = m->ev_caty[p]; S.out[p][2][k] = m->has_q ? m->ev_cqx[p] : nullptr;
+    call.pt[p][k] = *c;
+    S.out[p][0][k] = c->ax; S.out[p][1][k] = c->aty; S.out[p][2][k] = c->qx;
   }
   return 0;
 }
@@ -113,7 +90,7 @@ static int batch_check_stage_free(pdhg_handle *h) {
 
 // The upload and the passes of a call: per pass the pack kernel, then per matrix one batched product -- or, where the
 // batch's product has long rows, each masked member's own.  `carried` entries of S.ev travel with the same upload.
-static int batch_check_passes(pdhg_handle *h, BatchCheckCall &call, FleetMarks &marks) {
+static int batch_check_passes(pdhg_handle *h, BatchCheckCall &call, CheckMarks &marks) {
   BatchState &B = *h->bat;
   BatchState::Checks &C = B.chk;
   BatchCheckStage &S = *C.stage_host;
@@ -160,11 +137,11 @@ static int batch_check_passes(pdhg_handle *h, BatchCheckCall &call, FleetMarks &
     for (int k = 0; k < B.K; ++k) {
       if (!((mask >> k) & 1u)) continue;
       pdhg_handle *mb = B.mem[(size_t)k];
-      const double *px = p == 0 ? mb->x : (p == 1 ? mb->px_avg : mb->x_r), *py = p == 0 ? mb->y : (p == 1 ? mb->py_avg : mb->y_r);
+      const PointRef &pt = call.pt[p][k];
       EpiArgs e{};
-      if (oA) { e.out = mb->ev_cax[p]; if ((rc = launch_spmv<MODE_PLAIN, 0>(mb, mb->A, px, e))) return rc; C.launches += 1; }
-      if (oT) { if ((rc = launch_aty_plain(mb, py, mb->ev_caty[p]))) return rc; C.launches += 1; }
-      if (oQ) { e.out = mb->ev_cqx[p]; if ((rc = launch_spmv<MODE_PLAIN, 2>(mb, mb->Q, px, e))) return rc; C.launches += 1; }
+      if (oA) { e.out = pt.ax; if ((rc = launch_spmv<MODE_PLAIN, 0>(mb, mb->A, pt.px, e))) return rc; C.launches += 1; }
+      if (oT) { if ((rc = launch_aty_plain(mb, pt.py, pt.aty))) return rc; C.launches += 1; }
+      if (oQ) { e.out = pt.qx; if ((rc = launch_spmv<MODE_PLAIN, 2>(mb, mb->Q, pt.px, e))) return rc; C.launches += 1; }
     }
   }
   marks.issued = true;
@@ -209,11 +186,11 @@ int pdhg_batch_point_products(pdhg_handle *batch, int count, const int *member, 
   BatchState::Checks &C = h->bat->chk;
   C.calls += 1;
   BatchCheckCall call;
-  FleetMarks marks;
+  CheckMarks marks;
   for (int i = 0; i < count; ++i) {
-    bool stale = false;
-    if ((rc = batch_check_stage(h, member[i], point[i], true, *C.stage_host, call, marks, &stale))) return rc;
-    if (!stale) C.cached += 1;
+    PointClaim pt;
+    if ((rc = batch_check_stage(h, member[i], point[i], true, *C.stage_host, call, marks, &pt))) return rc;
+    if (!pt.stale) C.cached += 1;
   }
   if (!(call.count[0] | call.count[1] | call.count[2])) { marks.issued = true; return 0; }
   return batch_check_passes(h, call, marks);
@@ -240,22 +217,13 @@ int pdhg_batch_eval_points(pdhg_handle *batch, const int *points, double *out) {
   BatchState::Checks &C = B.chk;
   C.calls += 1;
   if (!members) return 0;
-  // The one-handle form with its prefetched distances is what the kernels here restate: with one of its development
-  // switches set, or a profiled member, every member is served by its own call inside this one (no miss of the caller's).
-  const char *pf = dev_env("PDHG_EVAL_PREFETCH");
-  bool shared = eval_host_word() && !(pf && pf[0] == '0') && dev_env("PDHG_NO_EVAL_CACHE") == nullptr;
+  // without the form the kernels here restate, or with a profiled member, every member is served by its own call inside this one
+  bool shared = eval_shared_form_in_force();
   for (int k = 0; k < B.K; ++k) if (((members >> k) & 1u) && B.mem[(size_t)k]->profile) shared = false;
   if (!shared) {
-    for (int k = 0; k < B.K; ++k) {
-      if (!((members >> k) & 1u)) continue;
-      pdhg_handle *m = B.mem[(size_t)k];
-      m->fc_eval.valid = false;
-      h->bchk_serving = true;
-      rc = pdhg_eval_point(m, points[k], out + (size_t)24 * k);
-      h->bchk_serving = false;
-      if (rc) return rc;
-      fleet_store_eval(m, points[k], out + (size_t)24 * k);
-    }
+    for (int k = 0; k < B.K; ++k)
+      if (((members >> k) & 1u) && (rc = serve_eval_by_own_call(h->bchk_serving, B.mem[(size_t)k], points[k], out + (size_t)24 * k)))
+        return rc;
     return 0;
   }
   if ((rc = batch_checks_ensure(h))) return rc;
@@ -263,7 +231,7 @@ int pdhg_batch_eval_points(pdhg_handle *batch, const int *points, double *out) {
   if ((rc = batch_check_stage_free(h))) return rc;
   BatchCheckStage &S = *C.stage_host;
   BatchCheckCall call;
-  FleetMarks marks;
+  CheckMarks marks;
   struct Carried { int k; bool have_avg; };
   std::vector<Carried> carried;
   const unsigned long long seq = ++C.seq;
@@ -271,23 +239,12 @@ int pdhg_batch_eval_points(pdhg_handle *batch, const int *points, double *out) {
   for (int k = 0; k < B.K; ++k) {
     if (!((members >> k) & 1u)) continue;
     pdhg_handle *m = B.mem[(size_t)k];
-    bool stale = false;
-    if ((rc = batch_check_stage(h, k, points[k], true, S, call, marks, &stale))) return rc;
-    if (!stale) C.cached += 1;
+    PointClaim pt, av;
+    if ((rc = batch_check_stage(h, k, points[k], true, S, call, marks, &pt))) return rc;
+    if (!pt.stale) C.cached += 1;
     const bool have_avg = m->sum_x_count != 0 && m->sum_y_count != 0;
-    if (have_avg && (rc = batch_check_stage(h, k, PDHG_POINT_AVERAGE, false, S, call, marks, nullptr))) return rc;
-    const int p = batch_point_index(points[k]);
-    FleetQpEvalArgs a{};
-    a.n = (int)m->n; a.m = (int)m->m; a.ne = (int)m->num_eq; a.grid = m->ev_grid; a.have_avg = have_avg ? 1 : 0;
-    a.pt_x = p == 0 ? m->x : (p == 1 ? m->px_avg : m->x_r); a.pt_y = p == 0 ? m->y : (p == 1 ? m->py_avg : m->y_r);
-    a.pt_ax = m->ev_cax[p]; a.pt_aty = m->ev_caty[p]; a.pt_qx = m->has_q ? m->ev_cqx[p] : nullptr;
-    a.E = m->E; a.b_o = m->b_o; a.Dv = m->Dv; a.c_o = m->c_o; a.lb_o = m->lb_o; a.ub_o = m->ub_o;
-    a.avg_x = have_avg ? m->px_avg : nullptr; a.avg_y = have_avg ? m->py_avg : nullptr;
-    a.x = m->x; a.y = m->y; a.x_r = m->x_r; a.y_r = m->y_r;
-    a.partials = m->ev_partials; a.scal = m->scal_dev;
-    a.host_out = C.res + carried.size() * words;
-    a.seq = seq;
-    S.ev[carried.size()] = a;
+    if (have_avg && (rc = batch_check_stage(h, k, PDHG_POINT_AVERAGE, false, S, call, marks, &av))) return rc;
+    S.ev[carried.size()] = eval_args_of(m, pt, have_avg, C.res + carried.size() * words, seq);
     carried.push_back(Carried{k, have_avg});
   }
   C.carried += (int64_t)carried.size();
@@ -310,15 +267,7 @@ int pdhg_batch_eval_points(pdhg_handle *batch, const int *points, double *out) {
                          "a batch's evaluation launch finished without publishing its results")))
       return rc;
     double *o = out + (size_t)24 * k;
-    // pdhg_eval_point's own statements on the 28 words
-    for (int q = 0; q < 6; ++q) m->chk_vals[q] = r[22 + q];
-    m->chk_state = m->state_version;
-    m->chk_restart = m->restart_version;
-    m->chk_point = points[k];
-    m->chk_have_avg = carried[j].have_avg;
-    for (int q = 0; q < 8; ++q) o[q] = r[q];
-    for (int q = 0; q < 6; ++q) { o[8 + q] = r[8 + q]; o[14 + q] = r[8 + 7 + q]; }
-    o[20] = r[8 + 6]; o[21] = r[8 + 13]; o[22] = o[23] = 0.0;
+    eval_unpack(m, points[k], true, carried[j].have_avg, r, o);
     fleet_store_eval(m, points[k], o);
   }
   return 0;

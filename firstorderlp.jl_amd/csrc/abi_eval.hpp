@@ -1,56 +1,11 @@
 // abi_eval.hpp -- part of the single translation unit pdhg_hip.hip (included there, at the place its text used to stand).
 // C ABI: the evaluation branch on the device (N1): point products, eval_point, distances, the trust-region searches.
+// What a check on one handle shares with a fleet's and a batch's shared launches stands in host_checks.hpp.
 
 // ---- evaluation branch on the device (N1) -----------------------------------
 
-static int ev_alloc(pdhg_handle *h) {
-  if (h->ev_partials) return 0;
-  int rc;
-  {
-    // the evaluation kernels reduce up to 30 quantities per workgroup and a second stage reads every workgroup's
-    // partials: two elements per thread and at most 1024 workgroups measured best (L1-SVM 229K elements: 448
-    // workgroups 67 us per trust-region call against 82 with 895; 2M elements: 977 workgroups 123 us against 147 with 2048)
-    static const int per_thread = dev_env("PDHG_EV_ELEMS") ? std::max(1, atoi(dev_env("PDHG_EV_ELEMS"))) : 2;
-    h->ev_grid = std::min(1024, ew_grid((h->n + h->m + per_thread) / per_thread));
-  }
-  if ((rc = alloc_zero(&h->ev_partials, (int64_t)EV_MAXQ * h->ev_grid))) return rc;
-  if ((rc = alloc_zero(&h->ev_ax, h->m))) return rc;
-  if ((rc = alloc_zero(&h->ev_aty, h->n_alloc))) return rc;
-  for (int k = 0; k < 3; ++k) {
-    if ((rc = alloc_zero(&h->ev_cax[k], h->m))) return rc;
-    if ((rc = alloc_zero(&h->ev_caty[k], h->n_alloc))) return rc;
-  }
-  if (h->grp && (rc = alloc_zero(&h->ev_xg, h->n_alloc))) return rc;
-  if ((rc = alloc_zero(&h->px_avg, h->n))) return rc;
-  if ((rc = alloc_zero(&h->py_avg, h->m))) return rc;
-  if ((rc = alloc_zero(&h->x_r, h->n))) return rc;   // zeros == the initial restart point (pdhg.jl:869)
-  if ((rc = alloc_zero(&h->y_r, h->m))) return rc;
-  return 0;
-}
-
 // second stage of every shard's block partials (ns sums then nm maxes), then the
 // combination over ranks in rank order
-// the pinned result words of the evaluation reductions (multi_final_kernel, tr_small_kernel): k values, checksum, sequence number
-static int ev_ensure_host(pdhg_handle *h) {
-  if (!h->ev_host) {
-    HIP_TRY(hipHostMalloc((void **)&h->ev_host, (EV_HOST_SLOTS + 2) * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
-    memset(h->ev_host, 0, (EV_HOST_SLOTS + 2) * sizeof(double));
-  }
-  return 0;
-}
-static int ev_wait_host(pdhg_handle *h, int k, unsigned long long seq, double *out) {
-  return wait_words(h->stream, h->ev_host, EV_HOST_SLOTS, k, seq, out, 40000000L,
-                    "evaluation reduction finished without publishing its results");
-}
-
-// The evaluation reductions publish into pinned host memory (one handle) unless PDHG_EVAL_HOST_WORD=0 (dev): decided in
-// ONE place and per call -- pdhg_eval_point's combined 22-quantity reduction (which needs the max mask) and ev_finish
-// must never disagree (a cached copy here once could: sums where maxima belong).
-static bool eval_host_word() {
-  const char *hw = dev_env("PDHG_EVAL_HOST_WORD");
-  return !(hw && hw[0] == '0');
-}
-
 static int ev_finish(const Shards &L, int ns, int nm, double *out, unsigned max_mask = 0) {
   if (ns + nm > EV_MAXQ) return fail(-1, "too many scalars in one reduction");
   const bool host_word = eval_host_word();
@@ -77,61 +32,44 @@ static int ev_finish(const Shards &L, int ns, int nm, double *out, unsigned max_
   return combine_scalars(L, ns + nm, ns, out);
 }
 
-// px: column vector (valid on the owned slice), py: this shard's rows
+// px_avg = sum_x / its weights on the owned column slice, py_avg likewise on this shard's rows
+static int divide_average(pdhg_handle *h) {
+  const int64_t o = h->clo;
+  hipLaunchKernelGGL(div_kernel, dim3(ew_grid(h->cn)), dim3(TPB), 0, h->stream, (int)h->cn, h->sum_x + o, h->sum_x_weights, h->px_avg + o);
+  hipLaunchKernelGGL(div_kernel, dim3(h->ew_grid_m), dim3(TPB), 0, h->stream, (int)h->m, h->sum_y, h->sum_y_weights, h->py_avg);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// px: column vector (valid on the owned slice), py: this shard's rows; the average is materialised when it is stale
 static int select_point(pdhg_handle *h, int point, const double **px, const double **py) {
-  int rc = ev_alloc(h);
+  PointClaim c;
+  int rc = claim_point(h, point, false, nullptr, &c);
   if (rc) return rc;
-  if (point == PDHG_POINT_CURRENT) { *px = h->x; *py = h->y; return 0; }
-  if (point == PDHG_POINT_RESTART) { *px = h->x_r; *py = h->y_r; return 0; }
-  if (point == PDHG_POINT_AVERAGE) {
-    if (h->sum_x_count == 0 || h->sum_y_count == 0) return fail(-1, "average is empty");
-    if (h->avg_version != h->state_version) {
-      const int64_t o = h->clo;
-      hipLaunchKernelGGL(div_kernel, dim3(ew_grid(h->cn)), dim3(TPB), 0, h->stream, (int)h->cn, h->sum_x + o, h->sum_x_weights, h->px_avg + o);
-      hipLaunchKernelGGL(div_kernel, dim3(h->ew_grid_m), dim3(TPB), 0, h->stream, (int)h->m, h->sum_y, h->sum_y_weights, h->py_avg);
-      HIP_TRY(hipGetLastError());
-      h->avg_version = h->state_version;
-    }
-    *px = h->px_avg; *py = h->py_avg;
-    return 0;
-  }
-  return fail(-1, "unknown point selector");
+  if (c.need_div && (rc = divide_average(h))) return rc;
+  *px = c.px; *py = c.py;
+  return 0;
 }
 
 // A*x (this shard's rows), A'*y (owned slice) and, for a QP, Q*x (full) at `point`
-// on every shard; cached for CURRENT / AVERAGE until the state changes.  Results in
+// on every shard; kept per point until the state changes (claim_point).  Results in
 // h->pt_ax / pt_aty / pt_qx together with the point itself in h->pt_x / pt_y.
 static int point_products(const Shards &L, int point) {
   int rc;
-  static const bool cache_off = dev_env("PDHG_NO_EVAL_CACHE") != nullptr;   // debugging aid
-  const bool cached = !cache_off && (point == PDHG_POINT_CURRENT || point == PDHG_POINT_AVERAGE ||
-                                     point == PDHG_POINT_RESTART);
-  bool fresh = true;
+  static const bool cache_off = dev_env("PDHG_NO_EVAL_CACHE") != nullptr;   // debugging aid: one set of buffers, always computed
+  bool stale = true;
   FOR_SHARDS(L, h) {
-    if ((rc = select_point(h, point, &h->pt_x, &h->pt_y))) return rc;
-    h->pt_ax = h->ev_ax; h->pt_aty = h->ev_aty;
-    double **dqx = &h->ev_qx;
-    bool f = true;
-    if (cached) {
-      const int k = point == PDHG_POINT_CURRENT ? 0 : (point == PDHG_POINT_AVERAGE ? 1 : 2);
-      h->pt_ax = h->ev_cax[k]; h->pt_aty = h->ev_caty[k]; dqx = &h->ev_cqx[k];
-      if (k < 2) {
-        f = h->ev_cversion[k] != h->state_version;
-        h->ev_cversion[k] = h->state_version;
-      } else {
-        const uint64_t key = (h->matrix_version << 32) + h->restart_version;
-        f = h->ev_rkey != key;
-        h->ev_rkey = key;
-      }
+    PointClaim c;
+    if ((rc = claim_point(h, point, !cache_off, nullptr, &c))) return rc;
+    if (c.need_div && (rc = divide_average(h))) return rc;
+    if (cache_off) {
+      if (h->has_q && !h->ev_qx && (rc = alloc_zero(&h->ev_qx, h->n))) return rc;
+      h->pt_x = c.px; h->pt_y = c.py; h->pt_ax = h->ev_ax; h->pt_aty = h->ev_aty; h->pt_qx = h->has_q ? h->ev_qx : nullptr;
+      c.stale = true;
     }
-    if (h->has_q && !*dqx) {
-      if ((rc = alloc_zero(dqx, h->n))) return rc;
-      f = true;
-    }
-    h->pt_qx = h->has_q ? *dqx : nullptr;
-    fresh = f;              // shards move in lock step: the same answer on all of them
+    stale = c.stale;        // shards move in lock step: the same answer on all of them
   }
-  if (!fresh) return 0;
+  if (!stale) return 0;
   // full x at the point on every shard (a plain handle's vectors are full already)
   if (L.g) {
     if ((rc = gather_cols_device(L, [](pdhg_handle *s) { return s->pt_x; }, [](pdhg_handle *s) { return s->ev_xg; }))) return rc;
@@ -204,8 +142,7 @@ int pdhg_eval_point(pdhg_handle *h0, int point, double out[24]) {
     // rides in the same reduction: three more launches of dist2_kernel, partials behind the 22, ONE second stage, one
     // round trip.  pdhg_distance_to_restart / pdhg_point_sumsq answer from these until the state moves -- the same
     // kernel, grid and per-quantity second stage as their own launches: the same bits.  (three round trips of a check's six)
-    const char *pf = dev_env("PDHG_EVAL_PREFETCH");                   // dev knob, read per call: the test compares both forms in one process
-    const bool pre = !(pf && pf[0] == '0');
+    const bool pre = eval_prefetch();
     bool have_avg = false;
     if (pre) {
       have_avg = h->sum_x_count != 0 && h->sum_y_count != 0;
@@ -226,16 +163,7 @@ int pdhg_eval_point(pdhg_handle *h0, int point, double out[24]) {
     double r[28];
     // quantities 0-3 sums, 4-7 maxes (rows); 8-14 sums, 15-21 maxes (columns); 22-27 sums (the prefetched scalars)
     if ((rc = ev_finish(L, pre ? 28 : 22, 0, r, 0xF0u | (0x7Fu << 15)))) return rc;
-    if (pre) {
-      for (int q = 0; q < 6; ++q) h->chk_vals[q] = r[22 + q];
-      h->chk_state = h->state_version;
-      h->chk_restart = h->restart_version;
-      h->chk_point = point;
-      h->chk_have_avg = have_avg;
-    }
-    for (int q = 0; q < 8; ++q) out[q] = r[q];
-    for (int q = 0; q < 6; ++q) { out[8 + q] = r[8 + q]; out[14 + q] = r[8 + 7 + q]; }
-    out[20] = r[8 + 6]; out[21] = r[8 + 13]; out[22] = out[23] = 0.0;
+    eval_unpack(h, point, pre, have_avg, r, out);
     return 0;
   }
   FOR_SHARDS(L, h) {
@@ -317,9 +245,6 @@ int pdhg_get_point(pdhg_handle *h0, int point, double *x, double *y) {
   return sync_all(L);
 }
 
-static inline uint64_t d2bits(double v) { uint64_t b; memcpy(&b, &v, 8); return b; }
-static inline double bits2d(uint64_t b) { double v; memcpy(&v, &b, 8); return v; }
-
 // ---- the trust-region problem as ONE persistent launch (tr_coop_kernel.hpp) ----
 // Decided once per handle: a single handle (no shard group) whose n + m elements fit PDHG_TR_COOP_MAX (default 1M;
 // measured per call, 5 passes: n + m = 40K 94 -> 73 us, 229K (L1-SVM) 104 -> 80, 500K 138 -> 90, 1M 143 -> 110, 2M 167 -> 160:
@@ -360,10 +285,7 @@ static int tr_coop_call(pdhg_handle *h, double wp, double wd, double radius, int
   int rc = ev_ensure_host(h);
   if (rc) return rc;
   TrCoopArgs a{};
-  a.n = (int)h->n; a.m = (int)h->m; a.ne = (int)h->num_eq; a.range = range; a.approximate = approximate ? 1 : 0;
-  a.px = h->pt_x; a.py = h->pt_y; a.aty = h->pt_aty; a.qx = h->pt_qx; a.ax = h->pt_ax;
-  a.c = h->c; a.b = h->b; a.lb = h->lb; a.ub = h->ub;
-  a.wp = wp; a.wd = wd; a.radius = radius;
+  tr_problem_fill(a, h, point_in_handle(h), wp, wd, radius, range, approximate);
   a.gdv = h->tr_g; a.wd2v = h->tr_dir; a.thr = h->tr_thr;
   a.partials = h->tr_partials;
   a.sync = h->tr_sync;
@@ -412,21 +334,9 @@ int pdhg_trust_region_bound(pdhg_handle *h0, int point, double primal_weight_nor
       HIP_TRY(hipSetDevice(h->device));
       if ((rc = ev_ensure_host(h))) return rc;
       const size_t lds = sizeof(double) * 3 * (size_t)(h->n + h->m);
-      {
-        static size_t limit[64] = {};
-        static std::mutex mu;
-        std::lock_guard<std::mutex> lock(mu);
-        size_t &cur = limit[h->device & 63];
-        if (cur < lds) {
-          HIP_TRY(hipFuncSetAttribute((const void *)tr_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-          cur = lds;
-        }
-      }
+      if ((rc = tr_small_lds.raise(h->device, lds))) return rc;
       TrSmallArgs a{};
-      a.n = (int)h->n; a.m = (int)h->m; a.ne = (int)h->num_eq; a.range = range; a.approximate = approximate ? 1 : 0;
-      a.px = h->pt_x; a.py = h->pt_y; a.aty = h->pt_aty; a.qx = h->pt_qx; a.ax = h->pt_ax;
-      a.c = h->c; a.b = h->b; a.lb = h->lb; a.ub = h->ub;
-      a.wp = wp; a.wd = wd; a.radius = radius;
+      tr_problem_fill(a, h, point_in_handle(h), wp, wd, radius, range, approximate);
       a.host_out = h->ev_host;
       a.seq = ++h->ev_seq;
       hipLaunchKernelGGL(tr_small_kernel, dim3(1), dim3(TRS_TPB), lds, h->stream, a);

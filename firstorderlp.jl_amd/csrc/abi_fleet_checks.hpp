@@ -1,4 +1,5 @@
-// abi_fleet_checks.hpp -- part of the single translation unit pdhg_hip.hip (included there, after abi_fleet.hpp).
+// abi_fleet_checks.hpp -- part of the single translation unit pdhg_hip.hip (included there, after abi_fleet.hpp; what a
+// check here shares with one handle's and a batch's stands in host_checks.hpp).
 // C ABI: a fleet's CHECKS in shared launches (fleet_check_kernels.hpp): pdhg_eval_point of many members in one call,
 // trust-region problems of many members in one call.  A member that suits the one-workgroup kernels rides in the shared
 // launch -- a small QP too, with PDHG_SMALL_QP=1, in launches of the QP kernels beside the LPs'; every other one is
@@ -8,12 +9,12 @@
 
 // Does the member ride in the shared check launches?  An LP on one handle, not profiled, n + m within the one-workgroup
 // trust-region kernel's reach, no row of A or A' beyond SMALL_MAX_ROW entries (small_row_sum's order is launch_spmv's up
-// to there), plain CSR layouts, and the evaluation reductions publishing into pinned memory.  Independent of
+// to there), plain CSR layouts, and the one-handle evaluation form the kernels restate in force.  Independent of
 // small_lp_eligible: the step kernel keeps nine vectors in LDS, these kernels at most three.
 // A QP with PDHG_SMALL_QP=1 alone (read per call, like the other switches here), when CSR(Q) suits small_row_sum as A must.
 // Q' is not read by a check: a long column of Q keeps a member out of the step class, not out of this one.
 static bool fleet_check_eligible(pdhg_handle *h) {
-  const char *se = dev_env("PDHG_SMALL_EVAL"), *pf = dev_env("PDHG_EVAL_PREFETCH");
+  const char *se = dev_env("PDHG_SMALL_EVAL");
   if (check_handle(h) != 0) return false;
   if (h->has_q) {
     const char *qv = getenv("PDHG_SMALL_QP");
@@ -23,7 +24,7 @@ static bool fleet_check_eligible(pdhg_handle *h) {
   return !h->grp && !h->profile && h->n + h->m >= 1 && h->n + h->m <= TRS_MAX &&
          h->A.max_row_nnz <= SMALL_MAX_ROW && h->At.max_row_nnz <= SMALL_MAX_ROW && h->A.segs.empty() && h->At.segs.empty() &&
          !h->A.tiled && !h->At.tiled && h->A.slabs.empty() && h->At.slabs.empty() && h->A.rowptr && h->At.rowptr &&
-         eval_host_word() && !(se && se[0] == '0') && !(pf && pf[0] == '0') && dev_env("PDHG_NO_EVAL_CACHE") == nullptr;
+         eval_shared_form_in_force() && !(se && se[0] == '0');
 }
 
 // the argument table of check kernel `which` with room for `items` entries of `bytes` each (fleet_reserve's way)
@@ -42,87 +43,32 @@ static int fleet_check_table(pdhg_handle *f, int which, size_t items, size_t byt
   return 0;
 }
 
-// one (member, point) of a call: the point's vectors and where its products live
-struct FleetPointRef { const double *px, *py; double *ax, *aty, *qx; };
 // the point items of a call: the LP members' and the QP members', each a launch of its kernel from its table
 struct FleetPointItems {
   std::vector<FleetPointArgs> lp;
   std::vector<FleetQpPointArgs> qp;
 };
 
-// The freshness marks of the members a call stages points of, as they were before.  fleet_stage_point marks a cache fresh
-// at once -- a later item of the same call at the same point of the same member must find it so -- but nothing has filled
-// it until fleet_point_products_kernel has been issued: a call that returns with an error before that (a later member's
-// flush_pending, a table that cannot be allocated, the launch itself) puts the marks back, and the member's next call
-// computes.  (ev_seq only ever advances: a number no kernel published is never waited for again.)
-struct FleetMarks {
-  struct Saved { pdhg_handle *h; uint64_t avg_version, cversion[2], rkey; };
-  std::vector<Saved> saved;
-  bool issued = false;
-  void keep(pdhg_handle *h) {
-    for (const Saved &s : saved) if (s.h == h) return;
-    saved.push_back(Saved{h, h->avg_version, {h->ev_cversion[0], h->ev_cversion[1]}, h->ev_rkey});
-  }
-  ~FleetMarks() {
-    if (issued) return;
-    for (const Saved &s : saved) {
-      s.h->avg_version = s.avg_version; s.h->ev_cversion[0] = s.cversion[0]; s.h->ev_cversion[1] = s.cversion[1]; s.h->ev_rkey = s.rkey;
-    }
-  }
-};
-
-// select_point + point_products of one eligible member, as bookkeeping: the buffers of `point`, the caches marked fresh
-// exactly as point_products marks them, and -- when the average has to be materialised or the products are stale -- an
-// item for fleet_point_products_kernel -- for a QP, with Q x into ev_cqx[k] (allocated on first use, which makes the
-// products stale), for fleet_qp_point_products_kernel.  (products == false: the average only, for the evaluation's distances.)
-static int fleet_stage_point(pdhg_handle *h, int point, bool products, FleetPointItems &items, FleetPointRef *ref,
-                             FleetMarks &marks) {
-  int rc = ev_alloc(h);
+// claim_point of one eligible member, and what the claim asks for -- the average materialised, the products computed -- as
+// an item for fleet_point_products_kernel or, for a QP, fleet_qp_point_products_kernel
+static int fleet_stage_point(pdhg_handle *h, int point, bool products, FleetPointItems &items, PointClaim *c, CheckMarks &marks) {
+  int rc = claim_point(h, point, products, &marks, c);
   if (rc) return rc;
-  marks.keep(h);
-  FleetPointArgs a{};
+  if (!c->need_div && !c->stale) return 0;
+  FleetQpPointArgs a{};
   a.n = (int)h->n; a.m = (int)h->m;
-  const double *px, *py;
-  if (point == PDHG_POINT_CURRENT) { px = h->x; py = h->y; }
-  else if (point == PDHG_POINT_RESTART) { px = h->x_r; py = h->y_r; }
-  else {
-    px = h->px_avg; py = h->py_avg;
-    if (h->avg_version != h->state_version) {
-      a.do_div = 1;
-      a.sum_x = h->sum_x; a.sum_y = h->sum_y; a.wx = h->sum_x_weights; a.wy = h->sum_y_weights;
-      a.avg_x = h->px_avg; a.avg_y = h->py_avg;
-      h->avg_version = h->state_version;
-    }
+  if (c->need_div) {
+    a.do_div = 1;
+    a.sum_x = h->sum_x; a.sum_y = h->sum_y; a.wx = h->sum_x_weights; a.wy = h->sum_y_weights;
+    a.avg_x = h->px_avg; a.avg_y = h->py_avg;
   }
-  const int k = point == PDHG_POINT_CURRENT ? 0 : (point == PDHG_POINT_AVERAGE ? 1 : 2);
-  if (products) {
-    bool stale;
-    if (k < 2) {
-      stale = h->ev_cversion[k] != h->state_version;
-      h->ev_cversion[k] = h->state_version;
-    } else {
-      const uint64_t key = (h->matrix_version << 32) + h->restart_version;
-      stale = h->ev_rkey != key;
-      h->ev_rkey = key;
-    }
-    if (h->has_q && !h->ev_cqx[k]) {
-      if ((rc = alloc_zero(&h->ev_cqx[k], h->n))) return rc;
-      stale = true;
-    }
-    a.do_products = stale ? 1 : 0;
-    h->pt_x = px; h->pt_y = py; h->pt_ax = h->ev_cax[k]; h->pt_aty = h->ev_caty[k]; h->pt_qx = h->has_q ? h->ev_cqx[k] : nullptr;
-  }
-  if (ref) *ref = FleetPointRef{px, py, h->ev_cax[k], h->ev_caty[k], h->has_q ? h->ev_cqx[k] : nullptr};
-  if (a.do_div || a.do_products) {
-    a.A = h->A.view(); a.T = h->At.view();
-    a.px = px; a.py = py; a.ax = h->ev_cax[k]; a.aty = h->ev_caty[k];
-    if (h->has_q) {
-      FleetQpPointArgs q{};
-      static_cast<FleetPointArgs &>(q) = a;
-      q.Q = h->Q.view(); q.qx = h->ev_cqx[k];
-      items.qp.push_back(q);
-    } else items.lp.push_back(a);
-  }
+  a.do_products = c->stale ? 1 : 0;
+  a.A = h->A.view(); a.T = h->At.view();
+  a.px = c->px; a.py = c->py; a.ax = c->ax; a.aty = c->aty;
+  if (h->has_q) {
+    a.Q = h->Q.view(); a.qx = c->qx;
+    items.qp.push_back(a);
+  } else items.lp.push_back(a);      // (the LP part of the block)
   return 0;
 }
 
@@ -143,30 +89,11 @@ static int fleet_check_launch(pdhg_handle *f, int which, const std::vector<Item>
 }
 
 // the point launches of a call: an empty part issues nothing; every cache marked fresh is filled once both have been issued
-static int fleet_point_launches(pdhg_handle *f, const FleetPointItems &items, FleetMarks &marks) {
+static int fleet_point_launches(pdhg_handle *f, const FleetPointItems &items, CheckMarks &marks) {
   int rc;
   if ((rc = fleet_check_launch(f, 0, items.lp, fleet_point_products_kernel, TPB, 0))) return rc;
   if ((rc = fleet_check_launch(f, 3, items.qp, fleet_qp_point_products_kernel, TPB, 0))) return rc;
   marks.issued = true;
-  return 0;
-}
-
-static int fleet_tr_lds_limit(int device, size_t lds) {
-  static size_t limit[64] = {};
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lock(mu);
-  size_t &cur = limit[device & 63];
-  if (cur < lds) {
-    HIP_TRY(hipFuncSetAttribute((const void *)fleet_tr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    cur = lds;
-  }
-  return 0;
-}
-
-static int fleet_point_error(pdhg_handle *h, int point, const std::string &who) {
-  if (point != PDHG_POINT_CURRENT && point != PDHG_POINT_AVERAGE && point != PDHG_POINT_RESTART)
-    return fail(-1, who + ": unknown point selector");
-  if (point == PDHG_POINT_AVERAGE && (h->sum_x_count == 0 || h->sum_y_count == 0)) return fail(-1, who + ": average is empty");
   return 0;
 }
 
@@ -186,7 +113,7 @@ int pdhg_fleet_eval_points(pdhg_handle *fleet, const int *points, double *out) {
     const std::string who = "pdhg_fleet_eval_points: member " + std::to_string(k);
     if ((rc = check_handle(h))) return rc;
     if (!h->has_original) return fail(-1, who + ": pdhg_set_original_problem has not been called");
-    if ((rc = fleet_point_error(h, points[k], who))) return rc;
+    if ((rc = point_error(h, points[k], who))) return rc;
   }
   HIP_TRY(hipSetDevice(fleet->device));
   struct Carried { int k; unsigned long long seq; bool have_avg; };
@@ -206,30 +133,20 @@ int pdhg_fleet_eval_points(pdhg_handle *fleet, const int *points, double *out) {
   FleetPointItems pitems;
   std::vector<FleetEvalArgs> eitems;
   std::vector<FleetQpEvalArgs> qeitems;
-  FleetMarks marks;
+  CheckMarks marks;
   for (Carried &c : carried) {
     pdhg_handle *h = F.mem[(size_t)c.k];
     const int point = points[c.k];
     { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
     if ((rc = ev_ensure_host(h))) return rc;
-    FleetPointRef pt{}, av{};
+    PointClaim pt, av;
     if ((rc = fleet_stage_point(h, point, true, pitems, &pt, marks))) return rc;
     c.have_avg = h->sum_x_count != 0 && h->sum_y_count != 0;
     if (c.have_avg && (rc = fleet_stage_point(h, PDHG_POINT_AVERAGE, false, pitems, &av, marks))) return rc;
-    FleetEvalArgs a{};
-    a.n = (int)h->n; a.m = (int)h->m; a.ne = (int)h->num_eq; a.grid = h->ev_grid; a.have_avg = c.have_avg ? 1 : 0;
-    a.pt_x = pt.px; a.pt_y = pt.py; a.pt_ax = pt.ax; a.pt_aty = pt.aty;
-    a.E = h->E; a.b_o = h->b_o; a.Dv = h->Dv; a.c_o = h->c_o; a.lb_o = h->lb_o; a.ub_o = h->ub_o;
-    a.avg_x = av.px; a.avg_y = av.py; a.x = h->x; a.y = h->y; a.x_r = h->x_r; a.y_r = h->y_r;
-    a.partials = h->ev_partials; a.scal = h->scal_dev;
-    a.host_out = h->ev_host;
-    a.seq = c.seq = ++h->ev_seq;
-    if (h->has_q) {
-      FleetQpEvalArgs q{};
-      static_cast<FleetEvalArgs &>(q) = a;
-      q.pt_qx = pt.qx;
-      qeitems.push_back(q);
-    } else eitems.push_back(a);
+    c.seq = ++h->ev_seq;
+    const FleetQpEvalArgs a = eval_args_of(h, pt, c.have_avg, h->ev_host, c.seq);
+    if (h->has_q) qeitems.push_back(a);
+    else eitems.push_back(a);                // (the LP part of the block)
   }
   // at most four launches: the LP members' points, the QP members', the LP evaluations, the QP evaluations
   if ((rc = fleet_point_launches(fleet, pitems, marks))) return rc;
@@ -240,26 +157,11 @@ int pdhg_fleet_eval_points(pdhg_handle *fleet, const int *points, double *out) {
     double r[28];
     if ((rc = ev_wait_host(h, 28, c.seq, r))) return rc;
     double *o = out + (size_t)24 * c.k;
-    // pdhg_eval_point's own statements on the 28 words
-    for (int q = 0; q < 6; ++q) h->chk_vals[q] = r[22 + q];
-    h->chk_state = h->state_version;
-    h->chk_restart = h->restart_version;
-    h->chk_point = points[c.k];
-    h->chk_have_avg = c.have_avg;
-    for (int q = 0; q < 8; ++q) o[q] = r[q];
-    for (int q = 0; q < 6; ++q) { o[8 + q] = r[8 + q]; o[14 + q] = r[8 + 7 + q]; }
-    o[20] = r[8 + 6]; o[21] = r[8 + 13]; o[22] = o[23] = 0.0;
+    eval_unpack(h, points[c.k], true, c.have_avg, r, o);
     fleet_store_eval(h, points[c.k], o);
   }
-  for (int k : single) {
-    pdhg_handle *h = F.mem[(size_t)k];
-    h->fc_eval.valid = false;                  // (its own call computes: never an answer from an earlier fleet call here)
-    F.chk_serving = true;                      // (... and is no miss of the caller's)
-    rc = pdhg_eval_point(h, points[k], out + (size_t)24 * k);
-    F.chk_serving = false;
-    if (rc) return rc;
-    fleet_store_eval(h, points[k], out + (size_t)24 * k);
-  }
+  for (int k : single)
+    if ((rc = serve_eval_by_own_call(F.chk_serving, F.mem[(size_t)k], points[k], out + (size_t)24 * k))) return rc;
   return 0;
 }
 
@@ -283,7 +185,7 @@ int pdhg_fleet_trust_region_bounds(pdhg_handle *fleet, int count, const int *mem
     pdhg_handle *h = F.mem[(size_t)member[i]];
     if ((rc = check_handle(h))) return rc;
     if (ranges[i] < 0 || ranges[i] > 2) return fail(-1, who + ": range must be 0, 1 or 2");
-    if ((rc = fleet_point_error(h, points[i], who))) return rc;
+    if ((rc = point_error(h, points[i], who))) return rc;
   }
   HIP_TRY(hipSetDevice(fleet->device));
   std::vector<int> carried, single;
@@ -296,38 +198,28 @@ int pdhg_fleet_trust_region_bounds(pdhg_handle *fleet, int count, const int *mem
   });
   if (!carried.empty()) {
     const size_t words = (size_t)(EV_HOST_SLOTS + 2);
-    if (F.chk_res_cap < carried.size()) {
-      HIP_TRY(hipStreamSynchronize(fleet->stream));
-      if (F.chk_res) (void)hipHostFree(F.chk_res);
-      F.chk_res = nullptr;
-      F.chk_res_cap = 0;
-      const size_t cap = std::max<size_t>(2 * carried.size(), 64);
-      HIP_TRY(hipHostMalloc((void **)&F.chk_res, cap * words * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
-      memset(F.chk_res, 0, cap * words * sizeof(double));
-      F.chk_res_cap = cap;
-    }
+    // (room to grow into: a fleet's rounds ask for about as many problems each)
+    const size_t want = F.chk_res_cap < carried.size() ? std::max<size_t>(2 * carried.size(), 64) : carried.size();
+    if ((rc = ensure_result_words(&F.chk_res, &F.chk_res_cap, want, fleet->stream))) return rc;
     FleetPointItems pitems;
     std::vector<TrSmallArgs> titems;
-    FleetMarks marks;
+    CheckMarks marks;
     size_t lds = 0;
     const unsigned long long seq = ++F.chk_seq;
     for (size_t j = 0; j < carried.size(); ++j) {
       const int i = carried[j];
       pdhg_handle *h = F.mem[(size_t)member[i]];
       { Shards L = shards_of(h); if ((rc = flush_pending(L))) return rc; }
-      FleetPointRef pt{};
+      PointClaim pt;
       if ((rc = fleet_stage_point(h, points[i], true, pitems, &pt, marks))) return rc;
       TrSmallArgs a{};
-      a.n = (int)h->n; a.m = (int)h->m; a.ne = (int)h->num_eq; a.range = ranges[i]; a.approximate = approximate[i] ? 1 : 0;
-      a.px = pt.px; a.py = pt.py; a.aty = pt.aty; a.qx = pt.qx; a.ax = pt.ax;
-      a.c = h->c; a.b = h->b; a.lb = h->lb; a.ub = h->ub;
-      a.wp = primal_weight_norm[i]; a.wd = dual_weight_norm[i]; a.radius = radii[i];
+      tr_problem_fill(a, h, pt, primal_weight_norm[i], dual_weight_norm[i], radii[i], ranges[i], approximate[i]);
       a.host_out = F.chk_res + j * words;
       a.seq = seq;
       titems.push_back(a);
       lds = std::max(lds, sizeof(double) * 3 * (size_t)(h->n + h->m));
     }
-    if ((rc = fleet_tr_lds_limit(fleet->device, lds))) return rc;
+    if ((rc = fleet_tr_lds.raise(fleet->device, lds))) return rc;
     // at most three launches: the LP members' points, the QP members', one trust-region launch for all problems
     if ((rc = fleet_point_launches(fleet, pitems, marks))) return rc;
     if ((rc = fleet_check_launch(fleet, 2, titems, fleet_tr_kernel, TRS_TPB, lds))) return rc;
@@ -340,16 +232,9 @@ int pdhg_fleet_trust_region_bounds(pdhg_handle *fleet, int count, const int *mem
                      approximate[i], out + (size_t)8 * i);
     }
   }
-  for (int i : single) {
-    pdhg_handle *h = F.mem[(size_t)member[i]];
-    for (pdhg_handle::FleetTrResult &r : h->fc_tr)           // (its own call computes)
-      if (fleet_tr_same(h, r, points[i], primal_weight_norm[i], dual_weight_norm[i], radii[i], ranges[i], approximate[i])) r.valid = false;
-    F.chk_serving = true;
-    rc = pdhg_trust_region_bound(h, points[i], primal_weight_norm[i], dual_weight_norm[i], radii[i], ranges[i], approximate[i],
-                                 out + (size_t)8 * i);
-    F.chk_serving = false;
-    if (rc) return rc;
-    fleet_store_tr(h, points[i], primal_weight_norm[i], dual_weight_norm[i], radii[i], ranges[i], approximate[i], out + (size_t)8 * i);
-  }
+  for (int i : single)
+    if ((rc = serve_tr_by_own_call(F.chk_serving, F.mem[(size_t)member[i]], points[i], primal_weight_norm[i], dual_weight_norm[i],
+                                   radii[i], ranges[i], approximate[i], out + (size_t)8 * i)))
+      return rc;
   return 0;
 }

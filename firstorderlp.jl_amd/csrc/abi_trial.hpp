@@ -792,7 +792,7 @@ int pdhg_restart_to_average(pdhg_handle *h0) {
   const Shards L = shards_of(h0);
   if ((rc = flush_pending(L))) return rc;
   bump_version(L);
-  if (h0->sum_x_count == 0 || h0->sum_y_count == 0) return fail(-1, "average is empty");
+  if ((rc = point_error(h0, PDHG_POINT_AVERAGE, ""))) return rc;      // (an empty average: host_checks.hpp)
   FOR_SHARDS(L, h) {
     const int64_t o = h->clo;
     hipLaunchKernelGGL(div_kernel, dim3(ew_grid(h->cn)), dim3(TPB), 0, h->stream, (int)h->cn, h->sum_x + o, h->sum_x_weights, h->x + o);

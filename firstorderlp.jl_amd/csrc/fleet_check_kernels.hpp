@@ -1,5 +1,5 @@
 // fleet_check_kernels.hpp -- part of the single translation unit pdhg_hip.hip (included there, after small_lp_kernel.hpp).
-// A FLEET'S CHECKS in shared launches (host_fleet_checks.hpp, abi_fleet_checks.hpp): between two batches of steps every
+// A FLEET'S CHECKS in shared launches (host_checks.hpp, abi_fleet_checks.hpp): between two batches of steps every
 // member of a fleet asks for a termination evaluation and up to five trust-region problems.  Per member that is about a
 // dozen launches of a few microseconds of work each and up to four trips to the host, the members taking them in turn.
 // Here one workgroup does one member's (or one problem's) work, and a launch carries one workgroup per item: the item is

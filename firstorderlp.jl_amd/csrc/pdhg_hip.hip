@@ -765,6 +765,7 @@ int launch_final(pdhg_handle *h, int n_int, int n_dy, int q_count, bool to_host 
 #include "host_trial_graph_build.hpp"
 #include "host_shards.hpp"
 #include "host_resolve.hpp"
+#include "host_checks.hpp"
 }  // namespace
 
 // ================================================================== C ABI

@@ -28,10 +28,11 @@ import numpy as np
 from . import _lib
 from .engine import _int_p, _MemberEngine, _MemberOwner, _d, _i, _pd, _pi
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams,
-                                          MalitskyPockStepsizeParameters, _check_inputs, _constant_step_estimate,
-                                          _device_scaled_problem, _drive_solves, _host_scaled_problem, _initial_point,
-                                          _pack_ratios, _pack_step_states, _rescales_on_device, _set_initial_point,
-                                          _Solve, _unpack_step_states, take_steps)
+                                          MalitskyPockStepsizeParameters, _check_inputs, _check_requests,
+                                          _constant_step_estimate, _device_scaled_problem, _drive_solves,
+                                          _host_scaled_problem, _initial_point, _pack_ratios, _pack_step_states,
+                                          _rescales_on_device, _set_initial_point, _Solve, _unpack_step_states,
+                                          take_steps)
 
 
 class HipPdhgFleet(_MemberOwner):
@@ -214,16 +215,7 @@ def _fleet_checks(fleet, solves, pending):
     arguments))] -- as ONE ``fleet.eval_points`` and / or ONE ``fleet.trust_region_bounds``.  The results stay with the
     members: each member's own evaluator call, which follows, finds them."""
     slot = {id(mb): k for k, mb in enumerate(solves)}
-    points = np.full(len(solves), -1, dtype=np.int32)
-    items = []
-    for mb, (method, arguments) in pending:
-        k = slot[id(mb)]
-        if method == "iteration_stats":
-            points[k] = arguments[0]
-        elif method == "bounds":
-            requests, primal_w, dual_w, norm, approximate = arguments
-            items.extend((k, point, primal_w, dual_w, radius, rng, approximate)
-                         for point, radius, rng in mb.ev.tr_problems(requests, norm))
+    points, items = _check_requests(pending, lambda mb: slot[id(mb)], len(solves))
     if (points >= 0).any():
         fleet.eval_points(points)
     if items:

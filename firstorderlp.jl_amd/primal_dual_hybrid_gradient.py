@@ -614,6 +614,24 @@ def _check_round(active, checks):
     return steps
 
 
+def _check_requests(pending, slot, members):
+    """A sweep's ``pending`` requests (``_check_round``) as the arguments of the shared check calls: (points, tr_items)
+    -- ``points[slot(solve)]`` = the point of the solve's ``"iteration_stats"`` request, -1 where it has none, over
+    ``members`` slots; ``tr_items`` = (slot, point, primal weight, dual weight, radius, range, approximate) for every
+    trust-region problem of the ``"bounds"`` requests, in the solves' order."""
+    points = np.full(members, -1, dtype=np.int32)
+    tr_items = []
+    for mb, (method, arguments) in pending:
+        k = slot(mb)
+        if method == "iteration_stats":
+            points[k] = arguments[0]
+        elif method == "bounds":
+            requests, primal_w, dual_w, norm, approximate = arguments
+            tr_items.extend((k, point, primal_w, dual_w, radius, rng, approximate)
+                            for point, radius, rng in mb.ev.tr_problems(requests, norm))
+    return points, tr_items
+
+
 def _drive_solves(solves, step, checks=None):
     """The outer loop of several solves side by side (``batch.optimize_batch``, ``fleet.optimize_many``): at each
     round every active solve evaluates and names its step count, a solve that terminated leaves, and

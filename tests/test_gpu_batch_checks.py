@@ -302,6 +302,53 @@ def test_a_product_with_a_long_row_is_served_per_member(rig_of, transpose):
     _check_eval(rig, rig.mixed_points(), "long " + ("column" if transpose else "row"))
 
 
+# ---- the average materialised as a side effect ----
+
+TINY = {
+    "lp2x3": lambda: _family(random_lp(2, 3, 2, seed=41), 2, seed=42),
+    "qp2x3": lambda: random_qp_family(2, 3, 2, seed=43, nnz_per_row=2),
+}
+
+
+@pytest.mark.parametrize("shape", sorted(TINY))
+def test_an_average_materialised_for_the_distances_is_the_members_own(rig_of, shape):
+    """An evaluation at CURRENT asks for no products at AVERAGE, yet materialises the average (for the distances) and
+    marks it fresh.  What the member then does at AVERAGE on its own -- the point, the distances, a search, whose
+    products it computes itself from that average -- is the twin's, and its products are then fresh for the batch too,
+    until the next step."""
+    K = 2
+    rig = rig_of(TINY[shape]())
+    p = rig.problems[0]
+    assert (p.num_constraints, p.num_variables, p.num_equalities) == (2, 3, 1) and rig.K == K
+    rig.step(4)
+    batch, twin = rig.batch, rig.twin
+    assert all(rig.have_average(k) for k in range(K))
+    before = batch.check_info()
+    batch.eval_points(np.full(K, CURRENT, dtype=np.int32))
+    assert _delta(batch, before)["carried"] == K
+    bound = (AVERAGE, 1.7, 0.6, 0.3, 0)
+    for k in range(K):
+        mem, tw = batch.members[k], twin.members[k]
+        for g, w in zip(mem.get_point(AVERAGE), tw.get_point(AVERAGE)):
+            assert _same(g, w), f"{shape}: member {k}: the average {g} != {w}"
+        assert _same(mem.distance_to_restart(AVERAGE), tw.distance_to_restart(AVERAGE)), f"{shape}: member {k}: distance"
+        for approximate in (False, True):
+            got, want = mem.trust_region_bound(*bound, approximate), tw.trust_region_bound(*bound, approximate)
+            assert _same(got, want), f"{shape}: member {k}: {got} != {want}"
+        before = batch.check_info()
+        batch.point_products([(k, AVERAGE)])                 # (the member's own bound has just computed them)
+        d = _delta(batch, before)
+        assert d["cached"] == 1 and d["launches"] == 0, (shape, k, d)
+    rig.step(1)
+    for k in range(K):
+        before = batch.check_info()
+        batch.point_products([(k, AVERAGE)])
+        d = _delta(batch, before)
+        assert d["cached"] == 0 and d["launches"] > 0, (shape, k, d)
+        got, want = batch.members[k].trust_region_bound(*bound), twin.members[k].trust_region_bound(*bound)
+        assert _same(got, want), f"{shape}: member {k} after a step: {got} != {want}"
+
+
 # ---- invalidation ----
 
 def _expect_miss(rig, k, point, label):

@@ -267,6 +267,42 @@ def test_five_problems_of_one_member_in_one_call(rig):
     assert fleet.info()["shared_launches"] >= 1 and set(fleet.info()) == {"members", "shared_launches", "carried", "single"}
 
 
+def _tiny_members():
+    """n = 3, m = 2 with one equality row: an LP, and the QP it becomes with a diagonal Q."""
+    lp = random_lp(2, 3, 2, seed=41)
+    qp = QuadraticProgrammingProblem(lp.variable_lower_bound, lp.variable_upper_bound, sp.diags([0.5, 1.0, 2.0]).tocsc(),
+                                     lp.objective_vector, 0.0, lp.constraint_matrix, lp.right_hand_side, lp.num_equalities)
+    return [("lp2x3", lp, True), ("qp2x3", qp, True)]
+
+
+def test_an_average_materialised_for_the_distances_is_the_members_own(gpu_required, monkeypatch):
+    """An evaluation at CURRENT asks for no products at AVERAGE, yet materialises the average (for the distances) and
+    marks it fresh.  What the member then does at AVERAGE on its own -- the point, the distances, a search, whose
+    products it computes itself from that average -- is the solo engine's, which never saw a shared call."""
+    monkeypatch.setenv("PDHG_SMALL_QP", "1")                 # (the QP rides in the shared launches too)
+    rig = _Rig(_tiny_members())
+    try:
+        for p in rig.problems:
+            assert (p.num_constraints, p.num_variables, p.num_equalities) == (2, 3, 1)
+        rig.step(4)
+        assert all(rig.have_average(k) for k in range(rig.K))
+        rig.fleet.eval_points(np.full(rig.K, CURRENT, dtype=np.int32))
+        info = rig.fleet.check_info()
+        assert info["carried"] == rig.K and info["single"] == 0, info
+        for k, name in enumerate(rig.names):
+            mem, solo = rig.fleet.members[k], rig.solos[k]
+            for g, w in zip(mem.get_point(AVERAGE), solo.get_point(AVERAGE)):
+                assert _same(g, w), f"{name}: the average {g} != {w}"
+            assert _same(mem.distance_to_restart(AVERAGE), solo.distance_to_restart(AVERAGE)), f"{name}: distance"
+            wp, wd = rig.weights(k)
+            for approximate in (False, True):
+                bound = (AVERAGE, wp, wd, 0.3, 0, approximate)
+                got, want = mem.trust_region_bound(*bound), solo.trust_region_bound(*bound)
+                assert _same(got, want), f"{name}: {got} != {want}"
+    finally:
+        rig.close()
+
+
 def test_stored_results_go_stale_with_the_member(rig):
     rig.step(10)
     rig.restart()
