@@ -66,6 +66,11 @@ BATCH_CHECKS_EXPORTS = [
     "pdhg_batch_point_products", "pdhg_batch_eval_points", "pdhg_batch_check_info",
 ]
 
+# every symbol include/pdhg_hip_fleet_rescale.h declares: the rescaling of a fleet's members in one shared launch
+FLEET_RESCALE_EXPORTS = [
+    "pdhg_fleet_rescale", "pdhg_fleet_rescale_info",
+]
+
 ABI_VERSION = 11
 UNIQUE_ID_BYTES = 128
 (K_PRIMAL, K_SPMV_DUAL, K_SPMV_ATY, K_FINAL, K_ACCEPT, K_ALLGATHER, K_REDUCE_SCATTER,
@@ -78,7 +83,8 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "hipcc")
     sources = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))] + \
               [os.path.join(INCLUDE, f) for f in ("pdhg_hip.h", "pdhg_hip_resolve.h", "pdhg_hip_batch_resolve.h",
-                                                 "pdhg_hip_matrix_update.h", "pdhg_hip_batch_checks.h")]
+                                                 "pdhg_hip_matrix_update.h", "pdhg_hip_batch_checks.h",
+                                                 "pdhg_hip_fleet_rescale.h")]
     if not force and os.path.exists(LIB_PATH) and \
             os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in sources):
         return LIB_PATH
@@ -113,7 +119,8 @@ def build_sanitized(kind="asan", force=False, verbose=False):
     path, flags = SANITIZED[kind]
     sources = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))] + \
               [os.path.join(INCLUDE, f) for f in ("pdhg_hip.h", "pdhg_hip_resolve.h", "pdhg_hip_batch_resolve.h",
-                                                 "pdhg_hip_matrix_update.h", "pdhg_hip_batch_checks.h")]
+                                                 "pdhg_hip_matrix_update.h", "pdhg_hip_batch_checks.h",
+                                                 "pdhg_hip_fleet_rescale.h")]
     if not force and os.path.exists(path) and os.path.getmtime(path) >= max(os.path.getmtime(f) for f in sources):
         return path
     cmd = [hipcc, "-O1", "-g"] + HIPCC_FLAGS[1:] + flags + ["-fno-gpu-sanitize", "-I", INCLUDE, "-o", path, SRC_PATH] + LINK_FLAGS
@@ -147,8 +154,8 @@ def lib():
     d, i64, i32 = ctypes.c_double, ctypes.c_int64, ctypes.c_int
     # a stale library (older ABI: different out[] lengths, missing entry points)
     # must fail here, not as a buffer overrun deep inside a solve
-    missing = [name for name in EXPORTS + RESOLVE_EXPORTS + BATCH_RESOLVE_EXPORTS + MATRIX_UPDATE_EXPORTS + BATCH_CHECKS_EXPORTS
-               if not hasattr(L, name)]
+    missing = [name for name in EXPORTS + RESOLVE_EXPORTS + BATCH_RESOLVE_EXPORTS + MATRIX_UPDATE_EXPORTS + BATCH_CHECKS_EXPORTS +
+               FLEET_RESCALE_EXPORTS if not hasattr(L, name)]
     L.pdhg_abi_version.restype = i32
     L.pdhg_abi_version.argtypes = []
     version = L.pdhg_abi_version() if not missing or "pdhg_abi_version" not in missing else None
@@ -332,6 +339,11 @@ def lib():
     L.pdhg_batch_eval_points.argtypes = [_vp, _int_p, _dp]
     L.pdhg_batch_check_info.restype = i32
     L.pdhg_batch_check_info.argtypes = [_vp, _ip]
+    # include/pdhg_hip_fleet_rescale.h (arrays of K pointers, K = the fleet's members)
+    L.pdhg_fleet_rescale.restype = i32
+    L.pdhg_fleet_rescale.argtypes = [_vp, _int_p, i32, i32, i32, d, _dpp, _dpp, _dp]
+    L.pdhg_fleet_rescale_info.restype = i32
+    L.pdhg_fleet_rescale_info.argtypes = [_vp, _ip]
     _lib = L
     return L
 

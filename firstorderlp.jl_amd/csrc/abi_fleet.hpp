@@ -23,6 +23,10 @@ static void fleet_release(pdhg_handle *h) {
     if (T.dev) (void)hipFree(T.dev);
     if (T.host) (void)hipHostFree(T.host);
   }
+  for (FleetState::Table *T : {&F->rsc_table, &F->rsc_out}) {
+    if (T->dev) (void)hipFree(T->dev);
+    if (T->host) (void)hipHostFree(T->host);
+  }
   delete F;
   h->fleet = nullptr;
 }

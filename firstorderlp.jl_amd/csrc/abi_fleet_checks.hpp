@@ -27,9 +27,22 @@ static bool fleet_check_eligible(pdhg_handle *h) {
          eval_shared_form_in_force() && !(se && se[0] == '0');
 }
 
-// the argument table of check kernel `which` with room for `items` entries of `bytes` each (fleet_reserve's way)
-static int fleet_check_table(pdhg_handle *f, int which, size_t items, size_t bytes) {
-  FleetState::Table &T = f->fleet->chk_table[which];
+// Does the member ride in the shared rescale launch (abi_fleet_rescale.hpp, fleet_rescale_kernel)?  One plain handle, not
+// profiled; every resident copy of A, A' (and Q, Q') a plain CSR -- no row segments, no tiled copy, no slabs, no sliced
+// jagged copy, no long rows: apply_scaling's scale_one has then one array per matrix to scale, and every row statistic is
+// row_op_kernel's alone; n + m within the four factor vectors a workgroup's LDS holds.  LPs and QPs alike, no switch.
+static bool fleet_rescale_plain_csr(const CsrDev &D) {
+  return D.segs.empty() && !D.tiled && D.slabs.empty() && !D.sj.on() && D.nlong == 0 && (D.rows == 0 || D.rowptr) &&
+         (D.nnz == 0 || (D.col && D.val));
+}
+static bool fleet_rescale_eligible(const pdhg_handle *h) {
+  if (h->grp || h->bat || h->owner || h->fleet || h->profile || !h->Achunk.empty()) return false;
+  if (h->has_q && !(fleet_rescale_plain_csr(h->Q) && fleet_rescale_plain_csr(h->Qt))) return false;
+  return h->n + h->m >= 1 && h->n + h->m <= TRS_MAX && fleet_rescale_plain_csr(h->A) && fleet_rescale_plain_csr(h->At);
+}
+
+// a fleet-owned table (device copy, pinned staging) with room for `items` entries of `bytes` each (fleet_reserve's way)
+static int fleet_table_reserve(pdhg_handle *f, FleetState::Table &T, size_t items, size_t bytes) {
   if (T.cap >= items * bytes) return 0;
   HIP_TRY(hipStreamSynchronize(f->stream));
   if (T.dev) (void)hipFree(T.dev);
@@ -41,6 +54,10 @@ static int fleet_check_table(pdhg_handle *f, int which, size_t items, size_t byt
   HIP_TRY(hipHostMalloc(&T.host, cap, hipHostMallocDefault));
   T.cap = cap;
   return 0;
+}
+// the argument table of check kernel `which`
+static int fleet_check_table(pdhg_handle *f, int which, size_t items, size_t bytes) {
+  return fleet_table_reserve(f, f->fleet->chk_table[which], items, bytes);
 }
 
 // the point items of a call: the LP members' and the QP members', each a launch of its kernel from its table

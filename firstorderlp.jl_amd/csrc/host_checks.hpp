@@ -221,6 +221,7 @@ struct DynLdsLimit {
   }
 };
 static DynLdsLimit tr_small_lds{(const void *)tr_small_kernel}, fleet_tr_lds{(const void *)fleet_tr_kernel};
+static DynLdsLimit fleet_rescale_lds{(const void *)fleet_rescale_kernel};      // (abi_fleet_rescale.hpp)
 
 // ---- a member a shared call does not carry -----------------------------------------------------------------------------
 

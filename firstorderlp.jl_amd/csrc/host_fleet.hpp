@@ -31,6 +31,10 @@ struct FleetState {
   void *rsv_dev = nullptr, *rsv_host = nullptr;
   size_t rsv_cap = 0;
   ResolveCounters rsv;
+  // the rescaling in one shared launch (abi_fleet_rescale.hpp): the argument table, the arena the members' factors and
+  // max |a| come back in (device, pinned copy) and what the calls did (`other` unused: the view rebuilds are rsv's)
+  Table rsc_table, rsc_out;
+  ResolveCounters rsc;
 };
 
 // ---- what a fleet's check calls leave in a member (pdhg_handle::fc_eval / fc_tr): pdhg_eval_point and

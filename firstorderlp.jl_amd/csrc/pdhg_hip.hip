@@ -38,6 +38,7 @@
 #include "pdhg_hip_batch_resolve.h"
 #include "pdhg_hip_matrix_update.h"
 #include "pdhg_hip_batch_checks.h"
+#include "pdhg_hip_fleet_rescale.h"
 
 // The kernels and layout builders live in the headers below; they form ONE
 // translation unit with this file (the tiled kernel is sensitive to code
@@ -57,6 +58,7 @@
 #include "tr_coop_kernel.hpp"
 #include "batch_kernels.hpp"
 #include "resolve_kernels.hpp"
+#include "fleet_rescale_kernels.hpp"
 #include "batch_resolve_kernels.hpp"
 #include "batch_check_kernels.hpp"
 #include "matrix_update_kernels.hpp"
@@ -893,4 +895,5 @@ static int batch_scale_members(pdhg_handle *h, const double *dv, const double *e
 #include "abi_batch_resolve.hpp"
 #include "abi_batch_checks.hpp"
 #include "abi_matrix_update.hpp"
+#include "abi_fleet_rescale.hpp"
 }  // extern "C"

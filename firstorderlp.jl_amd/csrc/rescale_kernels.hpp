@@ -11,15 +11,11 @@ enum { ROP_MAXABS = 0, ROP_SUMPOW = 1, ROP_SUMSQ_SCALED = 2 };
 
 // out[r] = max |a| ; sum |a|^p (+ structural zeros when p == 0: Julia's
 // mapreduce visits them and 0.0^0 == 1.0) ; sum (a * inv_scale[r])^2
+// The row body, shared with fleet_rescale_kernel (fleet_rescale_kernels.hpp): one wave per row, lanes stride the row from
+// k0 + lane; the total is in lane 0, which `out` belongs to.
 template <int OP>
-__global__ __launch_bounds__(TPB) void row_op_kernel(CsrView A, int cols, double pexp,
-                                                     const double *__restrict__ inv_scale,
-                                                     double *__restrict__ out, int long_thr) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int r = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
-  if (r >= A.rows) return;
-  const int k0 = A.rowptr[r], k1 = A.rowptr[r + 1];
-  if (k1 - k0 > long_thr) return;        // long rows: row_op_long_* below (one workgroup per 8192-entry chunk)
+__device__ __forceinline__ void row_op_row(const CsrView &A, int r, int k0, int k1, int lane, int cols, double pexp,
+                                           const double *inv_scale, double *out) {
   const double sc = (OP == ROP_SUMSQ_SCALED) ? inv_scale[r] : 1.0;
   double acc = 0.0;
   for (int k = k0 + lane; k < k1; k += WAVE) {
@@ -34,11 +30,32 @@ __global__ __launch_bounds__(TPB) void row_op_kernel(CsrView A, int cols, double
     out[r] = acc;
   }
 }
+template <int OP>
+__global__ __launch_bounds__(TPB) void row_op_kernel(CsrView A, int cols, double pexp,
+                                                     const double *__restrict__ inv_scale,
+                                                     double *__restrict__ out, int long_thr) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int r = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
+  if (r >= A.rows) return;
+  const int k0 = A.rowptr[r], k1 = A.rowptr[r + 1];
+  if (k1 - k0 > long_thr) return;        // long rows: row_op_long_* below (one workgroup per 8192-entry chunk)
+  row_op_row<OP>(A, r, k0, k1, lane, cols, pexp, inv_scale, out);
+}
 
 // val[k] = (val[k] * inv_a[ia]) * inv_b[ib] with ia/ib chosen so that the
 // multiplication order is always (a * (1/e_row_of_A)) * (1/d_col_of_A), as in
 // (Diagonal(1 ./ E) * A) * Diagonal(1 ./ D) (preprocess.jl:567-571).
 // transposed == false: CSR(A) (row -> E, col -> D); true: CSR(A') (row -> D, col -> E).
+// (the row body, shared with fleet_rescale_kernel)
+__device__ __forceinline__ void scale_csr_row(int r, int k0, int k1, int lane, const int *col, double *val,
+                                              const double *inv_e, const double *inv_d, int transposed) {
+  for (int k = k0 + lane; k < k1; k += WAVE) {
+    const int c = col[k];
+    const double ie = transposed ? inv_e[c] : inv_e[r];
+    const double id = transposed ? inv_d[r] : inv_d[c];
+    val[k] = (val[k] * ie) * id;
+  }
+}
 __global__ __launch_bounds__(TPB) void scale_csr_kernel(int rows, const int *__restrict__ rowptr,
                                                         const int *__restrict__ col, double *__restrict__ val,
                                                         const double *__restrict__ inv_e,
@@ -49,12 +66,7 @@ __global__ __launch_bounds__(TPB) void scale_csr_kernel(int rows, const int *__r
   if (r >= rows) return;
   const int k0 = rowptr[r], k1 = rowptr[r + 1];
   if (skip_long && k1 - k0 > skip_long) return;      // skip_long = the long-row threshold: scale_long_kernel does those rows chunk by chunk
-  for (int k = k0 + lane; k < k1; k += WAVE) {
-    const int c = col[k];
-    const double ie = transposed ? inv_e[c] : inv_e[r];
-    const double id = transposed ? inv_d[r] : inv_d[c];
-    val[k] = (val[k] * ie) * id;
-  }
+  scale_csr_row(r, k0, k1, lane, col, val, inv_e, inv_d, transposed);
 }
 
 // Rows longer than BLOCK_NNZ (a dense equality row, an intercept column: up to n entries)
@@ -154,26 +166,37 @@ __global__ __launch_bounds__(TPB) void scale_tiled_kernel(const int2 *__restrict
 // elementwise helpers on rescaling vectors
 //  mode 0: v = sqrt(v), zeros -> 1          (Ruiz / Pock-Chambolle factors)
 //  mode 1: v = sqrt(max(a, 0)) from a       (unused)  mode 2: inv = 1/v ; cum *= v
-__global__ __launch_bounds__(TPB) void resc_sqrt_kernel(int n, double *__restrict__ v) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
-    double t = sqrt(v[i]);
-    if (t == 0.0) t = 1.0;
-    v[i] = t;
-  }
+// (the element bodies below are shared with fleet_rescale_kernel)
+__device__ __forceinline__ double resc_sqrt_elem(double v) {
+  double t = sqrt(v);
+  if (t == 0.0) t = 1.0;
+  return t;
 }
+__global__ __launch_bounds__(TPB) void resc_sqrt_kernel(int n, double *__restrict__ v) {
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) v[i] = resc_sqrt_elem(v[i]);
+}
+// l2_norm (preprocess.jl:99-113): scale .* sqrt(sum (a/scale)^2)
+__device__ __forceinline__ double resc_l2norm_elem(double scale, double sumsq) { return scale * sqrt(sumsq); }
 __global__ __launch_bounds__(TPB) void resc_l2norm_kernel(int n, const double *__restrict__ scale,
                                                           double *__restrict__ sumsq_inout) {
-  // l2_norm (preprocess.jl:99-113): scale .* sqrt(sum (a/scale)^2)
   for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB)
-    sumsq_inout[i] = scale[i] * sqrt(sumsq_inout[i]);
+    sumsq_inout[i] = resc_l2norm_elem(scale[i], sumsq_inout[i]);
+}
+__device__ __forceinline__ void resc_zero_to_one_inv_elem(double *v, double *inv, int i, int do_zero_to_one) {
+  double t = v[i];
+  if (do_zero_to_one && t == 0.0) { t = 1.0; v[i] = t; }
+  inv[i] = 1.0 / t;
 }
 __global__ __launch_bounds__(TPB) void resc_zero_to_one_inv_kernel(int n, double *__restrict__ v,
                                                                    double *__restrict__ inv, int do_zero_to_one) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
-    double t = v[i];
-    if (do_zero_to_one && t == 0.0) { t = 1.0; v[i] = t; }
-    inv[i] = 1.0 / t;
-  }
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) resc_zero_to_one_inv_elem(v, inv, i, do_zero_to_one);
+}
+// scale_problem (preprocess.jl:555-573): c ./= D ; ub .*= D ; lb .*= D ; b ./= E
+__device__ __forceinline__ void resc_apply_col(double d, double *c, double *lb, double *ub, double *cum_d, int j) {
+  c[j] = c[j] / d; ub[j] = ub[j] * d; lb[j] = lb[j] * d; cum_d[j] = cum_d[j] * d;
+}
+__device__ __forceinline__ void resc_apply_row(double e, double *b, double *cum_e, int i) {
+  b[i] = b[i] / e; cum_e[i] = cum_e[i] * e;
 }
 __global__ __launch_bounds__(TPB) void resc_apply_vectors_kernel(int n, int m, const double *__restrict__ dv,
                                                                  const double *__restrict__ ev,
@@ -181,20 +204,14 @@ __global__ __launch_bounds__(TPB) void resc_apply_vectors_kernel(int n, int m, c
                                                                  double *__restrict__ ub, double *__restrict__ b,
                                                                  double *__restrict__ cum_d,
                                                                  double *__restrict__ cum_e) {
-  // scale_problem (preprocess.jl:555-573): c ./= D ; ub .*= D ; lb .*= D ; b ./= E
   const int tid = blockIdx.x * TPB + threadIdx.x, st = gridDim.x * TPB;
-  for (int j = tid; j < n; j += st) {
-    const double d = dv[j];
-    c[j] = c[j] / d; ub[j] = ub[j] * d; lb[j] = lb[j] * d; cum_d[j] = cum_d[j] * d;
-  }
-  for (int i = tid; i < m; i += st) {
-    const double e = ev[i];
-    b[i] = b[i] / e; cum_e[i] = cum_e[i] * e;
-  }
+  for (int j = tid; j < n; j += st) resc_apply_col(dv[j], c, lb, ub, cum_d, j);
+  for (int i = tid; i < m; i += st) resc_apply_row(ev[i], b, cum_e, i);
 }
 // a = max(a, b): column max over [A; Q] for the QP Ruiz step (preprocess.jl:425-433)
+__device__ __forceinline__ double resc_max_elem(double a, double b) { return fmax(a, b); }
 __global__ __launch_bounds__(TPB) void resc_max_kernel(int n, double *__restrict__ a, const double *__restrict__ b) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) a[i] = fmax(a[i], b[i]);
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) a[i] = resc_max_elem(a[i], b[i]);
 }
 
 __global__ __launch_bounds__(TPB) void fill_kernel(int n, double v, double *__restrict__ out) {

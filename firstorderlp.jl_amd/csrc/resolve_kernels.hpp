@@ -18,18 +18,19 @@ namespace {
 
 // one retained apply_scaling step: its factors into the record, the running products beside resc_apply_vectors_kernel's
 // (the same multiplications from 1.0 in the same order: the same bits as the arrays pdhg_rescale returns)
+// (the element bodies, shared with fleet_rescale_kernel)
+__device__ __forceinline__ void resolve_record_col(double d, double *rec_step, double *cum_d, int j) {
+  rec_step[j] = d; cum_d[j] = cum_d[j] * d;
+}
+__device__ __forceinline__ void resolve_record_row(double e, double *rec_step, double *cum_e, int n, int i) {
+  rec_step[(int64_t)n + i] = e; cum_e[i] = cum_e[i] * e;
+}
 __global__ __launch_bounds__(TPB) void resolve_record_kernel(int n, int m, const double *__restrict__ dv,
                                                              const double *__restrict__ ev, double *__restrict__ rec_step,
                                                              double *__restrict__ cum_d, double *__restrict__ cum_e) {
   const int tid = blockIdx.x * TPB + threadIdx.x, st = gridDim.x * TPB;
-  for (int j = tid; j < n; j += st) {
-    const double d = dv[j];
-    rec_step[j] = d; cum_d[j] = cum_d[j] * d;
-  }
-  for (int i = tid; i < m; i += st) {
-    const double e = ev[i];
-    rec_step[(int64_t)n + i] = e; cum_e[i] = cum_e[i] * e;
-  }
+  for (int j = tid; j < n; j += st) resolve_record_col(dv[j], rec_step, cum_d, j);
+  for (int i = tid; i < m; i += st) resolve_record_row(ev[i], rec_step, cum_e, n, i);
 }
 
 // One member of a replay.  in_* == nullptr: that vector keeps what it holds -- no load, no store.

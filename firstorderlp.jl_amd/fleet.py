@@ -14,7 +14,9 @@ terminates on its own, at the iterations ``optimize`` would.  Both drivers run t
 objective-bound estimates, the restart test -- in shared launches, one workgroup per member or trust-region problem
 (csrc/fleet_check_kernels.hpp), and each member then reads its own result; the restarts themselves stay per member.
 Under the same ``PDHG_SMALL_QP=1`` the shared check launches carry QP members as well (rows of ``Q`` of at most 256
-entries; the library decides per call, nothing changes here).
+entries; the library decides per call, nothing changes here).  With ``PDHG_FLEET_RESCALE=1`` (off by default) the members'
+rescaling before the first step goes the same way: one ``fleet.rescale`` -- one workgroup per member in one launch
+(csrc/fleet_rescale_kernels.hpp) -- instead of ``rescale`` and ``matrix_max_abs`` member after member, the same bits.
 
 ``HipPdhgFleet`` is the device side: one fleet handle that owns K ordinary member handles on one stream (``.members``:
 ``HipPdhgEngine`` views -- every single-LP method works on them, ``rescale`` included: a member's matrix is its own).
@@ -26,7 +28,7 @@ import time as _time
 import numpy as np
 
 from . import _lib
-from .engine import _int_p, _MemberEngine, _MemberOwner, _d, _i, _pd, _pi
+from .engine import _dp, _int_p, _MemberEngine, _MemberOwner, _d, _i, _pd, _pi
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams,
                                           MalitskyPockStepsizeParameters, _check_inputs, _check_requests,
                                           _constant_step_estimate, _device_scaled_problem, _drive_solves,
@@ -153,6 +155,37 @@ class HipPdhgFleet(_MemberOwner):
         _lib.check(self._L.pdhg_fleet_info(self._h, _pi(info)))
         return dict(zip(["check_launches", "carried", "single", "misses"], info[4:8].tolist()))
 
+    # ---- the rescaling in one shared launch (include/pdhg_hip_fleet_rescale.h) ----
+    def rescale(self, l_inf_ruiz_iterations, l2_norm_rescaling, pock_chambolle_alpha, members=None):
+        """``eng.rescale(...)`` and ``eng.matrix_max_abs()`` of the members named (indices; None: all), the members that
+        suit it in ONE launch, one workgroup per member: ``([(E, D), ...], [max_abs, ...])`` in the order named, the
+        same bits as the members' own calls.  The other members are left as they are."""
+        K = self.K
+        named = list(range(K)) if members is None else [int(k) for k in members]
+        if len(set(named)) != len(named) or any(not 0 <= k < K for k in named):
+            raise ValueError(f"members must be distinct indices below {K}")
+        active = np.zeros(K, dtype=np.int32)
+        active[named] = 1
+        Es = [np.empty(self.members[k].m) for k in named]
+        Ds = [np.empty(self.members[k].n) for k in named]
+        e_table, d_table = (_dp * K)(), (_dp * K)()
+        for k, E, D in zip(named, Es, Ds):
+            e_table[k], d_table[k] = _pd(E), _pd(D)
+        max_abs = np.zeros(K)
+        use_pc = pock_chambolle_alpha is not None
+        _lib.check(self._L.pdhg_fleet_rescale(self._live(), active.ctypes.data_as(_int_p), int(l_inf_ruiz_iterations),
+                                              int(bool(l2_norm_rescaling)), int(use_pc),
+                                              float(pock_chambolle_alpha) if use_pc else 0.0, e_table, d_table,
+                                              _pd(max_abs)))
+        return list(zip(Es, Ds)), [float(max_abs[k]) for k in named]
+
+    def rescale_info(self):
+        """dict(shared_launches, carried, single, view_rebuilds): shared rescale launches so far; members the last
+        ``rescale`` carried in its launch / served by their own calls; lazy rebuilds of bound views so far."""
+        info = np.zeros(4, dtype=np.int64)
+        _lib.check(self._L.pdhg_fleet_rescale_info(self._live(), _pi(info)))
+        return dict(zip(["shared_launches", "carried", "single", "view_rebuilds"], info.tolist()))
+
     # ---- re-solves in shared launches (include/pdhg_hip_resolve.h): ``_MemberOwner``'s, over these ----
     _noun, _resolve_other = "fleet", "view_rebuilds"
 
@@ -165,6 +198,27 @@ def _default_fleet_factory(problems):
 
 
 _default_fleet_factory.takes_original_problem = True
+
+
+def _fleet_rescales(fleet):
+    """Do the members rescale through ONE ``fleet.rescale``?  With ``PDHG_FLEET_RESCALE=1`` in the environment (read at
+    every call; off by default: the path is new) and a fleet that has the method; else member by member, every call
+    and launch as it always was."""
+    return os.environ.get("PDHG_FLEET_RESCALE", "0") == "1" and hasattr(fleet, "rescale")
+
+
+def _rescale_members(fleet, params, members=None):
+    """``(E, D)`` and max |a| of the members named (None: all) after their rescaling on the device: one
+    ``fleet.rescale`` (``_fleet_rescales``), or ``eng.rescale`` and ``eng.matrix_max_abs`` member after member."""
+    args = (params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
+    if _fleet_rescales(fleet):
+        return fleet.rescale(*args) if members is None else fleet.rescale(*args, members=members)
+    factors, max_abs = [], []
+    for k in (range(len(fleet.members)) if members is None else members):
+        eng = fleet.members[k]
+        factors.append(eng.rescale(*args))
+        max_abs.append(eng.matrix_max_abs())
+    return factors, max_abs
 
 
 def _step_fleet(fleet, solves, policy, requests):
@@ -254,11 +308,8 @@ def optimize_many(params, problems, fleet_factory=None, initial_solutions=None):
     try:
         if _rescales_on_device(factory):
             fleet = factory(problems)
-            scaled, max_abs = [], []
-            for p, eng in zip(problems, fleet.members):
-                E, D = eng.rescale(params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
-                scaled.append(_device_scaled_problem(p, eng, E, D))
-                max_abs.append(eng.matrix_max_abs())
+            factors, max_abs = _rescale_members(fleet, params)
+            scaled = [_device_scaled_problem(p, eng, E, D) for p, eng, (E, D) in zip(problems, fleet.members, factors)]
         else:
             scaled, max_abs = zip(*[_host_scaled_problem(params, p) for p in problems])
             fleet = factory([s.scaled_qp for s in scaled])

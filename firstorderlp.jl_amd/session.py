@@ -25,7 +25,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from .batch import _checks_hook, _default_batch_factory, _step_batch, check_batch
-from .fleet import _default_fleet_factory, _fleet_checks, _step_fleet
+from .fleet import _default_fleet_factory, _fleet_checks, _fleet_rescales, _rescale_members, _step_fleet
 from .preprocess import validate
 from .quadratic_programming import as_csc
 from .primal_dual_hybrid_gradient import (AdaptiveStepsizeParams, ConstantStepsizeParams, _check_inputs, _constant_step_estimate,
@@ -152,18 +152,20 @@ class _Member:
             return {k: changes.get(k) for k in _UPDATE_FIELDS}
         return {k: (getattr(host_scaled.scaled_qp, k) if k in changes else None) for k in _UPDATE_FIELDS}
 
-    def update_matrix(self, updated, host_scaled):
+    def update_matrix(self, updated, host_scaled, rescale=True):
         """New matrix values on the engine (``update_matrix_values``: every copy of every layout, the raw vectors), the
-        rescaling run again as at create, and what depends on the matrix measured again; ``committed`` follows."""
+        rescaling run again as at create, and what depends on the matrix measured again; ``committed`` follows.
+        ``rescale=False`` (device route): the group rescales its updated members in one call and hands each the result
+        (``rescaled``)."""
         def q(problem):              # (an update keeps the class of the problem: the engine has Q where `updated` has)
             return problem.objective_matrix.data if _has_objective_matrix(updated) else None
         if self.on_device:
             self.engine.update_matrix_values(updated.constraint_matrix.data, q(updated), updated.objective_vector,
                                              updated.right_hand_side, updated.variable_lower_bound,
                                              updated.variable_upper_bound)
-            self.E, self.D = self.engine.rescale(self.params.l_inf_ruiz_iterations, self.params.l2_norm_rescaling,
-                                                 self.params.pock_chambolle_alpha)
-            self.matrix_max_abs = self.engine.matrix_max_abs()
+            if rescale:
+                self.rescaled(self.engine.rescale(self.params.l_inf_ruiz_iterations, self.params.l2_norm_rescaling,
+                                                  self.params.pock_chambolle_alpha), self.engine.matrix_max_abs())
         else:
             # the host route: the engine lives in the host-rescaled problem's space and is not rescaled
             sq = host_scaled.scaled_qp
@@ -172,6 +174,10 @@ class _Member:
             data = sq.constraint_matrix.data
             self.matrix_max_abs = float(np.max(np.abs(data))) if len(data) else 0.0
         self.estimate = None                 # the constant policy's power method sees the matrix: it runs again
+
+    def rescaled(self, factors, matrix_max_abs):
+        """What the engine's rescaling returned: ``(E, D)`` and max |a| of the scaled matrix."""
+        (self.E, self.D), self.matrix_max_abs = factors, matrix_max_abs
 
     def apply(self, updated, changes, host_scaled):
         """One member's staged update on its own engine."""
@@ -326,7 +332,8 @@ class _GroupSession(_Session):
         """``updates``: one entry per problem -- ``None`` (keep the problem) or a dict with any of ``objective_vector``,
         ``right_hand_side``, ``variable_lower_bound``, ``variable_upper_bound`` and, where the group takes them
         (``PdhgSession.update``), the matrix keys.  A member with new matrix values is served on its own engine -- it
-        has a matrix of its own and rescales alone, as at create; the others still ride the shared vector launch.
+        has a matrix of its own and rescales alone, as at create (with ``PDHG_FLEET_RESCALE=1`` and a fleet that offers
+        ``rescale``: those members in one call, after their placements); the others still ride the shared vector launch.
         Every updated problem is validated before any device work; if one raises, the session is as it was."""
         members = self._live()
         updates = list(updates)
@@ -334,9 +341,13 @@ class _GroupSession(_Session):
             raise ValueError(f"updates has {len(updates)} entries for {len(members)} problems")
         self._check_update_keys(updates)
         staged = [None if u is None else mb.staged_update(**u) for mb, u in zip(members, updates)]
-        for mb, st in zip(members, staged):
-            if st is not None and _matrix_changed(st[1]):
-                mb.update_matrix(st[0], st[2])
+        changed = [k for k, st in enumerate(staged) if st is not None and _matrix_changed(st[1])]
+        shared = [k for k in changed if members[k].on_device] if self._group_takes("rescale", members) else []
+        for k in changed:
+            members[k].update_matrix(staged[k][0], staged[k][2], rescale=k not in shared)
+        if shared:       # the members given matrix values rescale in one call, after their placements
+            for k, factors, max_abs in zip(shared, *_rescale_members(self._owner, self.params, shared)):
+                members[k].rescaled(factors, max_abs)
         vectors = [None if st is None or not st[1] or _matrix_changed(st[1]) else mb.engine_vectors(st[1], st[2])
                    for mb, st in zip(members, staged)]
         if any(v is not None for v in vectors):
@@ -391,10 +402,19 @@ class PdhgFleetSession(_GroupSession):
         self.params = params
         members = None
         try:
-            # the members rescale one by one (_Member): each has a matrix of its own
+            # the members rescale one by one (_Member): each has a matrix of its own -- or, with PDHG_FLEET_RESCALE=1
+            # and a fleet that offers it, in one fleet.rescale after every member has retained
             if _rescales_on_device(factory):
                 self._owner = factory(problems)
-                members = [_Member(params, p, eng, True) for p, eng in zip(problems, self._owner.members)]
+                if _fleet_rescales(self._owner):
+                    for eng in self._owner.members:
+                        if hasattr(eng, "retain_rescaling"):
+                            eng.retain_rescaling()
+                    factors, max_abs = _rescale_members(self._owner, params)
+                    members = [_Member(params, p, eng, True, rescaled=(E, D, a))
+                               for p, eng, (E, D), a in zip(problems, self._owner.members, factors, max_abs)]
+                else:
+                    members = [_Member(params, p, eng, True) for p, eng in zip(problems, self._owner.members)]
             else:
                 host_scaled = [_host_scaled_problem(params, p) for p in problems]
                 self._owner = factory([s.scaled_qp for s, _ in host_scaled])
@@ -407,6 +427,8 @@ class PdhgFleetSession(_GroupSession):
     fleet = property(_GroupSession._group)
 
     def _group_takes(self, call, members):
+        if call == "rescale":
+            return _fleet_rescales(self._owner)
         return hasattr(self._owner, call)
 
     def _drive(self, members):
@@ -467,7 +489,7 @@ class PdhgBatchSession(_GroupSession):
                                  "share one matrix); open a new session, or use PdhgSession / PdhgFleetSession")
 
     def _group_takes(self, call, members):
-        return all(mb.on_device for mb in members) and hasattr(self._owner, "update_problem_vectors") and \
+        return call != "rescale" and all(mb.on_device for mb in members) and hasattr(self._owner, "update_problem_vectors") and \
             hasattr(self._owner, "warm_start")
 
     def _drive(self, members):
