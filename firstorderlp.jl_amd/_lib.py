@@ -71,6 +71,11 @@ FLEET_RESCALE_EXPORTS = [
     "pdhg_fleet_rescale", "pdhg_fleet_rescale_info",
 ]
 
+# every symbol include/pdhg_hip_batch_matrix_update.h declares: new matrix values for a batch on its kept sparsity pattern
+BATCH_MATRIX_UPDATE_EXPORTS = [
+    "pdhg_batch_update_matrix_values",
+]
+
 ABI_VERSION = 11
 UNIQUE_ID_BYTES = 128
 (K_PRIMAL, K_SPMV_DUAL, K_SPMV_ATY, K_FINAL, K_ACCEPT, K_ALLGATHER, K_REDUCE_SCATTER,
@@ -84,7 +89,7 @@ def build(force=False, verbose=False):
     sources = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))] + \
               [os.path.join(INCLUDE, f) for f in ("pdhg_hip.h", "pdhg_hip_resolve.h", "pdhg_hip_batch_resolve.h",
                                                  "pdhg_hip_matrix_update.h", "pdhg_hip_batch_checks.h",
-                                                 "pdhg_hip_fleet_rescale.h")]
+                                                 "pdhg_hip_fleet_rescale.h", "pdhg_hip_batch_matrix_update.h")]
     if not force and os.path.exists(LIB_PATH) and \
             os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in sources):
         return LIB_PATH
@@ -120,7 +125,7 @@ def build_sanitized(kind="asan", force=False, verbose=False):
     sources = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))] + \
               [os.path.join(INCLUDE, f) for f in ("pdhg_hip.h", "pdhg_hip_resolve.h", "pdhg_hip_batch_resolve.h",
                                                  "pdhg_hip_matrix_update.h", "pdhg_hip_batch_checks.h",
-                                                 "pdhg_hip_fleet_rescale.h")]
+                                                 "pdhg_hip_fleet_rescale.h", "pdhg_hip_batch_matrix_update.h")]
     if not force and os.path.exists(path) and os.path.getmtime(path) >= max(os.path.getmtime(f) for f in sources):
         return path
     cmd = [hipcc, "-O1", "-g"] + HIPCC_FLAGS[1:] + flags + ["-fno-gpu-sanitize", "-I", INCLUDE, "-o", path, SRC_PATH] + LINK_FLAGS
@@ -155,7 +160,7 @@ def lib():
     # a stale library (older ABI: different out[] lengths, missing entry points)
     # must fail here, not as a buffer overrun deep inside a solve
     missing = [name for name in EXPORTS + RESOLVE_EXPORTS + BATCH_RESOLVE_EXPORTS + MATRIX_UPDATE_EXPORTS + BATCH_CHECKS_EXPORTS +
-               FLEET_RESCALE_EXPORTS if not hasattr(L, name)]
+               FLEET_RESCALE_EXPORTS + BATCH_MATRIX_UPDATE_EXPORTS if not hasattr(L, name)]
     L.pdhg_abi_version.restype = i32
     L.pdhg_abi_version.argtypes = []
     version = L.pdhg_abi_version() if not missing or "pdhg_abi_version" not in missing else None
@@ -344,6 +349,9 @@ def lib():
     L.pdhg_fleet_rescale.argtypes = [_vp, _int_p, i32, i32, i32, d, _dpp, _dpp, _dp]
     L.pdhg_fleet_rescale_info.restype = i32
     L.pdhg_fleet_rescale_info.argtypes = [_vp, _ip]
+    # include/pdhg_hip_batch_matrix_update.h (the vectors as arrays of K pointers)
+    L.pdhg_batch_update_matrix_values.restype = i32
+    L.pdhg_batch_update_matrix_values.argtypes = [_vp, i64, _dp, i64, _dp, _dpp, _dpp, _dpp, _dpp]
     _lib = L
     return L
 

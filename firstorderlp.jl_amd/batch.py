@@ -13,7 +13,9 @@ are QPs that borrow one objective matrix too (``pdhg_batch_set_objective_matrix`
 members' check products and evaluations share launches (``point_products`` / ``eval_points``,
 include/pdhg_hip_batch_checks.h; ``_batch_checks``); every member's own evaluator call still runs, and finds them.  A batch that is solved again and
 again keeps its handle (``retain_rescaling`` / ``update_problem_vectors`` / ``warm_start``,
-include/pdhg_hip_batch_resolve.h; ``session.PdhgBatchSession`` drives them).
+include/pdhg_hip_batch_resolve.h; ``session.PdhgBatchSession`` drives them) and takes new matrix values on the kept
+sparsity pattern for all members at once (``update_matrix_values`` then ``rescale``,
+include/pdhg_hip_batch_matrix_update.h; ``PdhgBatchSession.update_matrix``).
 """
 import ctypes
 import os
@@ -181,6 +183,28 @@ class HipPdhgBatch(_MemberOwner):
         The batch keeps every rescaling step's factors once for all members (8 * steps * (n + m) bytes of device
         memory), which ``update_problem_vectors`` and ``warm_start`` need."""
         _lib.check(self._L.pdhg_batch_resolve_retain(self._live()))
+
+    def update_matrix_values(self, constraint_matrix_values, objective_matrix_values, objective_vectors, right_hand_sides,
+                             variable_lower_bounds, variable_upper_bounds):
+        """``pdhg_batch_update_matrix_values`` (include/pdhg_hip_batch_matrix_update.h): new values of the shared
+        constraint matrix in the order of the ``data`` the batch was created from, of the shared objective matrix
+        likewise (``None`` on an LP batch), and the four vectors of every member's ORIGINAL problem (K x n or K x m, as
+        in the constructor).  Call ``rescale`` next, as after create: until then every other call on the batch and on
+        its members is refused.  After that ``rescale`` every device array holds, bit for bit, what a fresh batch
+        created from the updated problems, retained and rescaled the same way holds."""
+        h = self._live()
+        a = _d(constraint_matrix_values).reshape(-1)
+        q = None if objective_matrix_values is None else _d(objective_matrix_values).reshape(-1)
+        ns, ms = [self.n] * self.K, [self.m] * self.K
+        tables = []
+        for name, rows, lens in (("objective_vectors", objective_vectors, ns), ("right_hand_sides", right_hand_sides, ms),
+                                 ("variable_lower_bounds", variable_lower_bounds, ns),
+                                 ("variable_upper_bounds", variable_upper_bounds, ns)):
+            if rows is None or any(row is None for row in rows):
+                raise ValueError(f"{name}: every member's vector is needed (the batch is rescaled afterwards)")
+            tables.append(self._pointer_table(name, [_d(row) for row in rows], lens))
+        _lib.check(self._L.pdhg_batch_update_matrix_values(h, len(a), _pd(a), 0 if q is None else len(q), _pd(q),
+                                                           *[t for t, _ in tables]))
 
 
 def _shared_q(problem):

@@ -221,6 +221,7 @@ int pdhg_create_batch(pdhg_handle **out, int count, int64_t m, int64_t n, int64_
 int pdhg_batch_set_objective_matrix(pdhg_handle *batch, int64_t q_nnz, const int64_t *q_colptr, const int64_t *q_rowval,
                                     const double *q_nzval, int index_base) {
   if (!batch_of(batch)) return fail(-1, "pdhg_batch_set_objective_matrix: not a batch handle");
+  if (int rcw = batch_awaits_rescale(batch, "pdhg_batch_set_objective_matrix: ")) return rcw;
   if (q_nnz < 0 || !q_colptr || (q_nnz > 0 && (!q_rowval || !q_nzval))) return fail(-1, "null input array");
   pdhg_handle *h = batch;
   BatchState &B = *h->bat;
@@ -238,6 +239,7 @@ int pdhg_batch_set_objective_matrix(pdhg_handle *batch, int64_t q_nnz, const int
   HIP_TRY(hipStreamSynchronize(h->stream));
   batch_drop_q(h);
   h->state_version += 1; h->matrix_version += 1;
+  h->csc_ascending = -1;               // (pdhg_batch_update_matrix_values looks at the new Q's columns too)
   for (pdhg_handle *m : B.mem) {
     // the launch paths were decided for the problem without (or with another) Q: decide again at the next trial
     // (the persistent one-launch trial stays off on a member: coop_mode is 0)
@@ -381,12 +383,14 @@ static int batch_trial(pdhg_handle *h, const double *step_size, const double *pr
 int pdhg_batch_trial_step(pdhg_handle *batch, const double *step_size, const double *primal_weight, double theta,
                           const int *active, double *out) {
   if (!batch_of(batch)) return fail(-1, "pdhg_batch_trial_step: not a batch handle");
+  if (int rcw = batch_awaits_rescale(batch, "pdhg_batch_trial_step: ")) return rcw;
   if (!step_size || !primal_weight || !active || !out) return fail(-1, "null argument");
   return batch_trial(batch, step_size, primal_weight, theta, active, out);
 }
 
 int pdhg_batch_accept(pdhg_handle *batch, const int *accept, const double *avg_weight) {
   if (!batch_of(batch)) return fail(-1, "pdhg_batch_accept: not a batch handle");
+  if (int rcw = batch_awaits_rescale(batch, "pdhg_batch_accept: ")) return rcw;
   if (!accept || !avg_weight) return fail(-1, "null argument");
   for (int k = 0; k < batch->bat->K; ++k) {
     if (!accept[k]) continue;
@@ -406,6 +410,7 @@ int pdhg_batch_take_steps_adaptive(pdhg_handle *batch, int64_t n_steps, double r
                                    int64_t *steps_done) {
   RoctxRange roctx_range("pdhg_batch_take_steps_adaptive");
   if (!batch_of(batch)) return fail(-1, "pdhg_batch_take_steps_adaptive: not a batch handle");
+  if (int rcw = batch_awaits_rescale(batch, "pdhg_batch_take_steps_adaptive: ")) return rcw;
   if (!step_size || !primal_weight || !total_number_iterations || !cumulative_kkt_passes || !numerical_error || !active ||
       !steps_done)
     return fail(-1, "null argument");

@@ -171,6 +171,7 @@ int pdhg_batch_point_products(pdhg_handle *batch, int count, const int *member, 
   RoctxRange roctx_range("pdhg_batch_point_products");
   int rc = batch_checks_begin(batch, "pdhg_batch_point_products");
   if (rc) return rc;
+  if ((rc = batch_awaits_rescale(batch, "pdhg_batch_point_products: "))) return rc;
   if (count < 1 || count > 3 * BATCH_MAX) return fail(-1, "pdhg_batch_point_products: count must be 1.." + std::to_string(3 * BATCH_MAX));
   if (!member || !point) return fail(-1, "null argument");
   pdhg_handle *h = batch;
@@ -201,6 +202,7 @@ int pdhg_batch_eval_points(pdhg_handle *batch, const int *points, double *out) {
   RoctxRange roctx_range("pdhg_batch_eval_points");
   int rc = batch_checks_begin(batch, "pdhg_batch_eval_points");
   if (rc) return rc;
+  if ((rc = batch_awaits_rescale(batch, "pdhg_batch_eval_points: "))) return rc;
   if (!points || !out) return fail(-1, "null argument");
   pdhg_handle *h = batch;
   BatchState &B = *h->bat;

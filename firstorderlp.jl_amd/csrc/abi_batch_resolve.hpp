@@ -17,6 +17,7 @@ static int batch_resolve_refuse(pdhg_handle *b, const std::string &who, bool nee
   if (!b) return fail(-1, who + ": null handle");
   if (!batch_of(b)) return fail(-1, who + ": not a batch handle");
   if (need_record && !b->rs) return fail(-1, who + ": pdhg_batch_resolve_retain was not called on this batch before pdhg_rescale");
+  if (need_record) return batch_awaits_rescale(b, who + ": ");       // (given new matrix values and not rescaled since)
   return 0;
 }
 

@@ -119,14 +119,16 @@ static int apply_scaling(pdhg_handle *h, RescaleTmp &t) {
   }
   HIP_TRY(hipGetLastError());
   if (int rcb = bounds_rebuild(h)) return rcb;             // lb / ub were rescaled in place: 0 and +-inf stay, the rest moves
-  if (h->bat) return batch_scale_members(h, t.dv, t.ev);   // the same step on every batch member's vectors
+  // the same step on every batch member's vectors -- unless the members await the rescale with their raw vectors staged
+  // (pdhg_batch_update_matrix_values): pdhg_rescale then replays the whole record on them in one launch at its end
+  if (h->bat && h->members_await_rescale == 0) return batch_scale_members(h, t.dv, t.ev);
   return 0;
 }
 
 int pdhg_rescale(pdhg_handle *h0, int l_inf_ruiz_iterations, int l2_norm_rescaling,
                  int use_pock_chambolle, double pock_chambolle_alpha,
                  double *constraint_rescaling_out, double *variable_rescaling_out) {
-  int rc = check_handle(h0, true, true);
+  int rc = check_handle(h0, true, true, true);
   if (rc) return rc;
   if (h0->owner) return fail(-1, "pdhg_rescale: a batch member shares its batch's matrix: rescale the batch handle");
   if (use_pock_chambolle && !(pock_chambolle_alpha >= 0.0 && pock_chambolle_alpha <= 2.0))
@@ -228,6 +230,8 @@ int pdhg_rescale(pdhg_handle *h0, int l_inf_ruiz_iterations, int l2_norm_rescali
     hipError_t e1 = hipGetLastError();
     if (e1 != hipSuccess) { cleanup(); return fail((int)e1, hipGetErrorString(e1)); }
   }
+  // a batch given new matrix values: the record just written, replayed on the members' staged raw vectors in one launch
+  if (h0->bat && h0->members_await_rescale == 1) RS(batch_replay_staged_members(h0));
   if (constraint_rescaling_out && h0->m_global > 0) {
     std::vector<double *> ptr((size_t)h0->world, nullptr);
     for (int i = 0; i < L.count; ++i) ptr[(size_t)L.p[i]->rank] = T[(size_t)i].cum_e;

@@ -19,6 +19,7 @@
 static int resolve_refuse(pdhg_handle *h, const std::string &who, bool need_record) {
   if (!h) return fail(-1, who + ": null handle");
   if (h->fleet) return fail(-1, who + ": a fleet handle holds no problem of its own: call the pdhg_fleet_ form, or this on a member");
+  if (int rcw = batch_awaits_rescale(h, who + ": ")) return rcw;
   if (h->bat) return fail(-1, who + ": a batch handle is not supported by this call: a batch takes the pdhg_batch_ forms of pdhg_hip_batch_resolve.h");
   if (h->owner) return fail(-1, who + ": a batch member is not supported (it shares its batch's matrix and rescaling: call the pdhg_batch_ forms of pdhg_hip_batch_resolve.h on its batch)");
   if (h->grp) return fail(-1, who + ": a shard group is not supported");

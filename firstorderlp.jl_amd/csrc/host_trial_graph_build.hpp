@@ -185,11 +185,26 @@ int graph_trial(pdhg_handle *h, const TrialArgs &ta, double out[5]) {
   return rcw;
 }
 
+// A batch handle, or a member of a batch, whose batch was given new matrix values and has not been rescaled since
+// (pdhg_batch_update_matrix_values): the members hold the vectors of the old scaling, the matrix the new raw values.
+// Every entry point but pdhg_rescale on the batch handle, pdhg_destroy and the info calls refuses such a handle.
+// rescales: the caller is pdhg_rescale, which a batch that awaits it accepts.
+int batch_awaits_rescale(const pdhg_handle *h, const std::string &who, bool rescales = false) {
+  const pdhg_handle *b = h->owner ? h->owner : h;
+  if (b->members_await_rescale == 2)
+    return fail(-1, who + "an update of the batch's matrix values failed on the device midway: its matrix and its members' vectors "
+                          "disagree; destroy the batch (pdhg_destroy)");
+  if (!b->members_await_rescale || rescales) return 0;
+  return fail(-1, who + "the batch was given new matrix values: rescale the batch first (pdhg_rescale on the batch handle)");
+}
+
 // queues_work: the entry point may put work on the shards' own streams (everything but a trial step and a lazy accept)
-int check_handle(pdhg_handle *h, bool queues_work = true, bool batch_ok = false) {
+// rescales: the entry point is pdhg_rescale, which a batch that awaits it (batch_awaits_rescale) accepts
+int check_handle(pdhg_handle *h, bool queues_work = true, bool batch_ok = false, bool rescales = false) {
   if (!h) return fail(-1, "null handle");
   if (h->fleet) return fail(-1, "a fleet handle runs no iterations of its own: call this on a member (pdhg_fleet_add)");
   if (h->bat && !batch_ok) return fail(-1, "a batch handle holds the shared matrix only: call this on a member (pdhg_batch_member)");
+  if (int rcw = batch_awaits_rescale(h, "", rescales)) return rcw;
   if (queues_work && h->grp && !h->grp->coop_dev.empty()) {
     DistGroup &g = *h->grp;
     if (g.join_pending) {          // the members' streams wait for the last persistent group launch (group_kernel.hpp)

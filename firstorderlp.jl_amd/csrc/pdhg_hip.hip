@@ -39,6 +39,7 @@
 #include "pdhg_hip_matrix_update.h"
 #include "pdhg_hip_batch_checks.h"
 #include "pdhg_hip_fleet_rescale.h"
+#include "pdhg_hip_batch_matrix_update.h"
 
 // The kernels and layout builders live in the headers below; they form ONE
 // translation unit with this file (the tiled kernel is sensitive to code
@@ -274,6 +275,11 @@ struct pdhg_handle {
   // from the result that call stored / launched by the member itself; serving: inside the batch call's own per-member calls
   int64_t bchk_served = 0, bchk_misses = 0;
   bool bchk_asked = false, bchk_serving = false;
+  // a batch handle: pdhg_batch_update_matrix_values (abi_batch_matrix_update.hpp) placed new values and staged the members'
+  // raw vectors; until pdhg_rescale on the batch handle has replayed its record on them, every other entry point on the
+  // batch and on its members is refused (batch_awaits_rescale).  0: no; 1: awaiting the rescale; 2: that call failed on the
+  // device after it had begun to place values -- matrix and vectors disagree for good, only pdhg_destroy proceeds
+  int members_await_rescale = 0;
 
   // ---- fleets of independent small LPs (abi_fleet.hpp).  A fleet handle owns `fleet` (its members, the argument table
   // and the shared tables of powers of a many-LP launch) and runs no iterations of its own; a member is a complete
@@ -882,6 +888,7 @@ int pdhg_create(pdhg_handle **out, int64_t m, int64_t n, int64_t nnz,
 static void batch_release(pdhg_handle *h);
 static void fleet_release(pdhg_handle *h);
 static int batch_scale_members(pdhg_handle *h, const double *dv, const double *ev);
+static int batch_replay_staged_members(pdhg_handle *h);     // (abi_batch_matrix_update.hpp)
 
 #include "abi_dist.hpp"
 #include "abi_trial.hpp"
@@ -896,4 +903,5 @@ static int batch_scale_members(pdhg_handle *h, const double *dv, const double *e
 #include "abi_batch_checks.hpp"
 #include "abi_matrix_update.hpp"
 #include "abi_fleet_rescale.hpp"
+#include "abi_batch_matrix_update.hpp"
 }  // extern "C"

@@ -19,6 +19,7 @@ the matrix share the record of its rescaling too (include/pdhg_hip_batch_resolve
 
 The reference has no warm start: a warm solve differs from a cold one in the starting point alone (see ``optimize``).
 """
+import copy
 import dataclasses
 
 import numpy as np
@@ -446,7 +447,8 @@ class PdhgBatchSession(_GroupSession):
     the adaptive or the constant policy).  A batch with ``retain_rescaling`` / ``update_problem_vectors`` / ``warm_start``
     of its own (``HipPdhgBatch``) keeps one record of the rescaling for all members and takes the updates and the warm
     starts of all members in one launch each; a factory that does not rescale on the device, or any other batch, is
-    served member by member through its engines' ``update_problem_vectors`` / ``warm_start``."""
+    served member by member through its engines' ``update_problem_vectors`` / ``warm_start``.  New matrix values on the
+    kept sparsity pattern, one matrix for all problems, go through ``update_matrix``."""
 
     def __init__(self, params, problems, batch_factory=None):
         problems = check_batch(problems, params)
@@ -481,12 +483,85 @@ class PdhgBatchSession(_GroupSession):
 
     def _check_update_keys(self, updates):
         # the members share one matrix, and its layouts are lent between their handles: new values for one member have
-        # no meaning, and new values for all of them are not built yet
+        # no meaning; new values for all of them go through update_matrix
         for k, u in enumerate(updates):
             given = [] if u is None else [key for pair in _MATRIX_FIELDS.items() for key in pair if u.get(key) is not None]
             if given:
-                raise ValueError(f"updates[{k}] gives {given[0]}: a batch session cannot change matrix values (its problems "
-                                 "share one matrix); open a new session, or use PdhgSession / PdhgFleetSession")
+                raise ValueError(f"updates[{k}] gives {given[0]}: a batch session cannot change matrix values per problem "
+                                 "(its problems share one matrix): give the new values of all of them to update_matrix, "
+                                 "or use PdhgSession / PdhgFleetSession")
+
+    def update_matrix(self, constraint_matrix_values=None, objective_matrix_values=None, constraint_matrix=None,
+                      objective_matrix=None, updates=None):
+        """New ENTRIES of the one constraint matrix (and the one objective matrix) of all problems, on the kept sparsity
+        pattern: values in the order of ``session.problems[0].constraint_matrix.data`` / ``.objective_matrix.data``, or
+        whole matrices of the same pattern, with ``PdhgSession.update``'s checks (another pattern raises ``ValueError``
+        naming the first column that differs; an LP stays an LP, a QP a QP).  ``updates``: optional vector updates per
+        problem, as ``update`` takes them, applied in the same call.
+
+        A batch that offers ``update_matrix_values`` (``HipPdhgBatch``) takes the values in place, once for all
+        members, is rescaled again as at create -- the members' vectors come back in one launch -- and its matrix is
+        measured again; no layout is built and nothing is allocated.  A batch without that call whose engines live in the
+        host-rescaled space (a factory without ``takes_original_problem``: the oracle batches of the CPU tests) is served
+        member by member through its engines' ``update_matrix_values``, in each engine's problem space
+        (``PdhgSession``); any other batch raises ``ValueError`` before any work.  Every updated problem
+        and the batch's preconditions (``check_batch``) are validated before any device work; if that raises, the
+        session is as it was.  The solve that follows is ``optimize_batch`` on the updated problems, bit for bit."""
+        members = self._live()
+        matrix = {"constraint_matrix_values": constraint_matrix_values, "objective_matrix_values": objective_matrix_values,
+                  "constraint_matrix": constraint_matrix, "objective_matrix": objective_matrix}
+        if all(v is None for v in matrix.values()):
+            raise ValueError("update_matrix needs new values of the constraint matrix or of the objective matrix "
+                             "(new vectors alone go through update)")
+        updates = [None] * len(members) if updates is None else list(updates)
+        if len(updates) != len(members):
+            raise ValueError(f"updates has {len(updates)} entries for {len(members)} problems")
+        self._check_update_keys(updates)
+        batch, params = self._owner, self.params
+        group = self._group_takes("update_matrix_values", members) and hasattr(batch, "update_matrix_values")
+        if not group:
+            # member by member, in the host-rescaled space of each engine: nothing rescales such engines together
+            if any(mb.on_device for mb in members):
+                raise ValueError("this batch rescales on the device and offers no update_matrix_values for all its members: "
+                                 "it cannot take new matrix values; open a new session")
+            lacking = [k for k, mb in enumerate(members) if not hasattr(mb.engine, "update_matrix_values")]
+            if lacking:
+                raise ValueError(f"the engine of problem {lacking[0]} has no update_matrix_values, and the batch has none "
+                                 "for all of them: this batch cannot take new matrix values; open a new session")
+        given = [{k: v for k, v in (u or {}).items() if v is not None} for u in updates]
+        # The matrix is checked and canonicalised ONCE, on problem 0 (the problems hold one matrix: check_batch said so when
+        # the session was opened); the other problems take the same matrix objects and only their own vectors are staged.
+        # A problem's constructor canonicalises both matrices again, and staging every problem through it made the tick
+        # of an 8-member batch LONGER than optimize_batch again on two of three families
+        # (profiles/batch_matrix_update_throughput.txt, section 1b).  The copies skip that constructor and nothing else:
+        # their vectors were validated when they were last set, the matrices with problem 0, and check_batch follows.
+        first = members[0].staged_update(**matrix, **given[0])
+        shared = {field: first[1][field] for field in _MATRIX_FIELDS if field in first[1]}
+
+        def staged_member(mb, vectors):
+            updated, changes = _updated_problem(mb.problem, **vectors) if vectors else (copy.copy(mb.problem), {})
+            for field, new in shared.items():
+                setattr(updated, field, new)
+            host_scaled = None if mb.on_device else _host_scaled_problem(mb.params, updated)[0]
+            return updated, {**changes, **shared}, host_scaled
+        staged = [first] + [staged_member(mb, vectors) for mb, vectors in zip(members[1:], given[1:])]
+        check_batch([st[0] for st in staged], self.params)
+        rescaling = (params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
+        if group:
+            first = staged[0][0]
+            q = first.objective_matrix.data if _has_objective_matrix(first) else None
+            batch.update_matrix_values(first.constraint_matrix.data, q, *[[getattr(st[0], k) for st in staged] for k in _UPDATE_FIELDS])
+            E, D = batch.rescale(*rescaling)
+            max_abs = batch.members[0].matrix_max_abs()
+            for mb in members:
+                mb.rescaled((E.copy(), D.copy()), max_abs)
+                mb.estimate = None
+        else:
+            for mb, (updated, _, host_scaled) in zip(members, staged):
+                mb.update_matrix(updated, host_scaled)
+        for mb, (updated, _, host_scaled) in zip(members, staged):
+            mb.committed(updated, host_scaled)
+        self._estimate = None                # the constant policy's power method sees the matrix: it runs again
 
     def _group_takes(self, call, members):
         return call != "rescale" and all(mb.on_device for mb in members) and hasattr(self._owner, "update_problem_vectors") and \

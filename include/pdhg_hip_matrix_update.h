@@ -33,7 +33,8 @@
  * over the column indices, made by a handle's first update and remembered: the one refusal that launches anything.
  *
  * Handle kinds.  Plain handles (those held as row segments included) and fleet members.  Shard groups are refused;
- * batch handles and batch members are refused too: their layouts are lent between handles (a follow-up).
+ * batch handles and batch members are refused too: their layouts are lent between handles, and a batch takes new values
+ * for all its members at once through the call that pdhg_hip_batch_matrix_update.h declares.
  */
 #ifndef PDHG_HIP_MATRIX_UPDATE_H_
 #define PDHG_HIP_MATRIX_UPDATE_H_

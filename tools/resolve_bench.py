@@ -38,6 +38,12 @@ another tick: every stored value of A is multiplied by 1 + 0.01 N(0, 1), and tho
 a cold or warm solve.  Beside each row, timed on one engine of the row's first problem (best of three): the
 ``update_matrix_values`` call alone, the ``rescale`` call alone, and a create of the same problem; and the durations of
 the placement kernels (mu_*_kernel, sj_fill_kernel) from a profiled child of their own.
+
+--matrix with --batch adds the batch legs to that table: ONE matrix tick for the whole family (the members share the
+matrix); (a) is `optimize_batch` again on the updated problems, (b) and (c) are ``PdhgBatchSession.update_matrix`` -- the
+values placed once, the batch rescaled, the members' vectors replayed in one launch -- and a cold or warm solve.  place /
+rescale / create are those of a ``HipPdhgBatch`` of the family, and the profiled child's kernels include the replay
+launch (batch_resolve_replay_kernel).
 """
 import argparse
 import dataclasses
@@ -58,7 +64,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 KERNELS = ("fleet_resolve_replay_kernel", "fleet_resolve_point_kernel", "resolve_replay_kernel", "resolve_point_kernel",
            "batch_resolve_replay_kernel", "batch_resolve_point_kernel")
 BATCH_RESOLVE_TILE = 4          # csrc/batch_resolve_kernels.hpp
-MATRIX_KERNELS = r"\b((?:mu_[a-z]+_kernel|sj_fill_kernel|scale_csr_kernel|scale_long_kernel|scale_tiled_kernel)(?:<[^>]*>)?)\("
+MATRIX_KERNELS = (r"\b((?:mu_[a-z]+_kernel|sj_fill_kernel|scale_csr_kernel|scale_long_kernel|scale_tiled_kernel|"
+                  r"batch_resolve_replay_kernel|batch_scale_vectors_kernel)(?:<[^>]*>)?)\(")
 
 
 def single_problem(name):
@@ -118,7 +125,10 @@ def series(problems, params, ticks, route, single, batch=False, matrix=False):
             session = PdhgSession(params, problems[0]) if single else (PdhgBatchSession if batch else PdhgFleetSession)(params, problems)
             session.solve()
         for tick in range(ticks):
-            if matrix:
+            if matrix and batch:             # the members share the matrix: one tick for all of them
+                updates = [tick_matrix(problems[0], tick, 0)] * len(problems)
+                updated = [with_matrix_values(p, u) for p, u in zip(problems, updates)] if route == "a" else None
+            elif matrix:
                 updates = [tick_matrix(p, tick, k) for k, p in enumerate(problems)]
                 updated = [with_matrix_values(p, u) for p, u in zip(problems, updates)] if route == "a" else None
             else:
@@ -131,7 +141,10 @@ def series(problems, params, ticks, route, single, batch=False, matrix=False):
                 session.update(**updates[0])
                 outs = [session.solve(warm_start=True if route == "c" else None)]
             else:
-                session.update(updates)
+                if matrix and batch:
+                    session.update_matrix(**updates[0])
+                else:
+                    session.update(updates)
                 outs = session.solve(warm_start=True if route == "c" else None)
             seconds.append(time.perf_counter() - t0)
             iterations.append(_iterations(outs))
@@ -187,6 +200,43 @@ def matrix_single_timings(problem, params):
     return 1e3 * min(place), 1e3 * min(rescale), 1e3 * min(create)
 
 
+def matrix_batch_timings(problems, params):
+    """``matrix_single_timings`` for a batch: ms of ``HipPdhgBatch.update_matrix_values`` alone, of the ``rescale`` that
+    follows (it ends in the replay launch) and of a create of the same family, best of three each; and, fourth, ms of
+    the ``rescale`` of a freshly created batch, which scales the members' vectors step by step (K launches and K
+    rebuilds of the bound views per step): what the replay launch stands in for."""
+    from firstorderlp_jl_amd import HipPdhgBatch
+    rescaling = (params.l_inf_ruiz_iterations, params.l2_norm_rescaling, params.pock_chambolle_alpha)
+    vectors = [[getattr(p, k) for p in problems] for k in ("objective_vector", "right_hand_side", "variable_lower_bound",
+                                                           "variable_upper_bound")]
+    create, place, rescale, fresh = [], [], [], []
+    batch = None
+    try:
+        for _ in range(3):
+            if batch is not None:
+                batch.close()
+            t0 = time.perf_counter()
+            batch = HipPdhgBatch.from_problems(problems)
+            create.append(time.perf_counter() - t0)
+            batch.retain_rescaling()
+            t0 = time.perf_counter()
+            batch.rescale(*rescaling)
+            fresh.append(time.perf_counter() - t0)
+        for tick in range(3):
+            u = tick_matrix(problems[0], tick, 0)
+            t0 = time.perf_counter()
+            batch.update_matrix_values(u["constraint_matrix_values"], u.get("objective_matrix_values"), *vectors)
+            t1 = time.perf_counter()
+            batch.rescale(*rescaling)
+            t2 = time.perf_counter()
+            place.append(t1 - t0)
+            rescale.append(t2 - t1)
+    finally:
+        if batch is not None:
+            batch.close()
+    return 1e3 * min(place), 1e3 * min(rescale), 1e3 * min(create), 1e3 * min(fresh)
+
+
 def matrix_problem(name, qp_shape):
     """A --matrix leg's single problem: --single's, or ``qp`` = one QP of ``random_qp_family`` at ``qp_shape``."""
     if name != "qp":
@@ -199,7 +249,15 @@ def matrix_problem(name, qp_shape):
 def matrix_child(name, K, ticks, qp_shape):
     """What the profiled child of a --matrix leg runs: `ticks` matrix updates and warm solves with a short iteration limit."""
     from fleet_bench import members, solve_params
-    from firstorderlp_jl_amd import PdhgFleetSession, PdhgSession
+    from firstorderlp_jl_amd import PdhgBatchSession, PdhgFleetSession, PdhgSession
+    if name.startswith("batch:"):
+        problems = batch_problems(name[len("batch:"):], K, qp_shape)
+        with PdhgBatchSession(solve_params(80), problems) as session:
+            session.solve()
+            for tick in range(ticks):
+                session.update_matrix(**tick_matrix(problems[0], tick, 0))
+                session.solve(warm_start=True)
+        return
     if K > 1:
         problems = members(name, K)
         with PdhgFleetSession(solve_params(80), problems) as session:
@@ -279,14 +337,17 @@ def matrix_legs(args, params, ks, emit):
     emit(f"{'problem':<15} {'K':>5} {'(a) ms':>9} {'spread':>6} {'it':>7} {'(b) ms':>9} {'spread':>6} {'it':>7} {'(c) ms':>9} {'spread':>6} {'it':>7} "
          f"{'a/b':>6} {'a/c':>6} {'place':>8} {'rescale':>8} {'create':>8}")
 
-    def row(name, K, problems, single):
-        got = measure(problems, params, args.ticks, args.reps, single, matrix=True)
-        place, rescale, create = matrix_single_timings(problems[0], params)
+    def row(name, K, problems, single, batch=False):
+        got = measure(problems, params, args.ticks, args.reps, single, batch, matrix=True)
+        place, rescale, create, *fresh = matrix_batch_timings(problems, params) if batch else matrix_single_timings(problems[0], params)
         a, b, c = got["a"], got["b"], got["c"]
         ahead = a[0] / b[0] > max(a[1], b[1])
         emit(f"{name:<15} {K:>5} {a[0]:>9.2f} {a[1]:>6.2f} {a[2]:>7.1f} {b[0]:>9.2f} {b[1]:>6.2f} {b[2]:>7.1f} {c[0]:>9.2f} {c[1]:>6.2f} "
              f"{c[2]:>7.1f} {a[0] / b[0]:>6.2f} {a[0] / c[0]:>6.2f} {place:>8.2f} {rescale:>8.2f} {create:>8.2f}"
              + ("" if a[2] == b[2] else "   # (a) and (b) DIFFER in iterations") + ("" if ahead else "   # (b) is NOT ahead of (a) by more than the spread"))
+        if fresh:
+            emit(f"# {name}: the rescale of a freshly created batch, members scaled step by step: {fresh[0]:.2f} ms (best of 3); "
+                 f"the rescale after update_matrix_values above, members replayed in one launch: {rescale:.2f} ms")
 
     def kernels(name, K, extra):
         if args.no_profile:
@@ -303,6 +364,11 @@ def matrix_legs(args, params, ks, emit):
         for K in ks:
             row(shape, K, problems[:K], False)
         kernels(shape, min(args.profile_k, max(ks)), (args.matrix_qp_shape or "-",))
+    for config in [s for s in args.batch.split(",") if s]:
+        problems = batch_problems(config, args.batch_k, args.batch_qp_shape)
+        row("batch:" + config, args.batch_k, problems, False, batch=True)
+        del problems
+        kernels("batch:" + config, args.batch_k, (args.batch_qp_shape,))
     for name in [s for s in args.single.split(",") if s] + (["qp"] if args.matrix_qp_shape else []):
         row(name, 1, [matrix_problem(name, args.matrix_qp_shape)], True)
         kernels(name, 1, (args.matrix_qp_shape or "-",))
@@ -347,7 +413,8 @@ def main(argv=None):
         lines.append(line)
 
     emit(f"# tools/resolve_bench.py --shapes {args.shapes} --ks {args.ks} --single {args.single} --ticks {args.ticks} --reps {args.reps} "
-         f"--iteration-limit {args.iteration_limit}" + (f" --matrix --matrix-qp-shape {args.matrix_qp_shape}" if args.matrix else ""))
+         f"--iteration-limit {args.iteration_limit}" + (f" --matrix --matrix-qp-shape {args.matrix_qp_shape}" if args.matrix else "")
+         + (f" --batch {args.batch} --batch-k {args.batch_k} --batch-qp-shape {args.batch_qp_shape}" if args.batch else ""))
     ks = [int(k) for k in args.ks.split(",") if k]
     if args.matrix:
         matrix_legs(args, params, ks, emit)
