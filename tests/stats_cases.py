@@ -54,3 +54,10 @@ def check_ci(ci, expected, tol):
             assert got == want, f
         else:
             assert abs(got - want) <= tol * max(1.0, abs(want)), (f, got, want)
+
+
+def check_ii(ii, expected, tol):
+    for f in II_FIELDS:
+        want = expected.get(f, 0.0)
+        got = getattr(ii, f)
+        assert abs(got - want) <= tol * max(1.0, abs(want)), (f, got, want)

@@ -33,8 +33,9 @@ def test_bound_optimal_objective_device(gpu_required, monkeypatch, case, small_e
 @pytest.mark.parametrize("case", __import__("tests.stats_cases", fromlist=["CASES"]).CASES, ids=lambda c: c[0])
 def test_convergence_information_device(gpu_required, case):
     """test/test_iteration_stats.jl:118-308: the ConvergenceInformation part through
-    pdhg_eval_point (the device path evaluates the rays at the iterate itself, as
-    optimize does, so the InfeasibilityInformation of those cases is host-only)."""
+    pdhg_eval_point.  The device path evaluates the rays at the iterate itself, as
+    optimize does: the InfeasibilityInformation of those cases is checked by
+    test_infeasibility_information_device, with the iterate set to the case's rays."""
     from tests import stats_cases as S
     name, lp, x, y, xr, yr, want_ci, want_ii = case
     eng = HipPdhgEngine.from_problem(lp)
@@ -47,6 +48,29 @@ def test_convergence_information_device(gpu_required, case):
     st = ev.iteration_stats(POINT_CURRENT, tc, True, 6, 5.0, 1.5, 1.0, 1.0, PointType.POINT_TYPE_CURRENT_ITERATE)
     S.check_ci(st.convergence_information[0], want_ci, 1e-14)
     assert st.iteration_number == 5
+
+
+@pytest.mark.parametrize("device_ids", [None, [0, 0]], ids=["one_handle", "shard_group"])
+@pytest.mark.parametrize("case", __import__("tests.stats_cases", fromlist=["CASES"]).CASES, ids=lambda c: c[0])
+def test_infeasibility_information_device(gpu_required, case, device_ids):
+    """test/test_iteration_stats.jl:118-308: the InfeasibilityInformation part.  The iterate is set to the case's rays
+    (x_ray, y_ray); the device takes the rays at the iterate, so this is the reference's
+    compute_infeasibility_information on those rays: all five fields, unlisted ones 0."""
+    from tests import stats_cases as S
+    from firstorderlp_jl_amd.termination import construct_termination_criteria
+    from firstorderlp_jl_amd.solve_log import PointType
+    name, lp, x, y, xr, yr, want_ci, want_ii = case
+    kw = {} if device_ids is None else {"device_ids": device_ids}
+    eng = HipPdhgEngine.from_problem(lp, **kw)
+    if device_ids is not None:
+        assert eng.dist_info()["world"] == len(device_ids)
+    sp_ = ScaledQpProblem(lp, lp, np.ones(lp.num_constraints), np.ones(lp.num_variables))
+    ev = DeviceEvaluator(eng, sp_, cached_quadratic_program_info(lp))
+    eng.set_current(np.array(xr), np.array(yr))
+    tc = construct_termination_criteria(eps_optimal_absolute=1e-6, eps_optimal_relative=1e-6)
+    st = ev.iteration_stats(POINT_CURRENT, tc, True, 6, 5.0, 1.5, 1.0, 1.0, PointType.POINT_TYPE_CURRENT_ITERATE)
+    S.check_ii(st.infeasibility_information[0], want_ii, 1e-14)
+    eng.close()
 
 
 # ---- round 4: the search as ONE persistent launch (csrc/tr_coop_kernel.hpp) against the pass-by-pass form ------------
